@@ -8,6 +8,7 @@ top-hat, n_ion with the exponential-MFP top-hat), first-snapshot path, inputs al
 resident in HBM when the timed region starts.
 
   python bench.py                      # N = 1
+  python bench.py --dump-outputs DIR   # also writes the last timed step's output arrays as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -77,7 +78,55 @@ def parse_args():
     ap.add_argument("--force-shard", action="store_true",
                     help="run the sharded code path (shard phase, RCCL reduce, finish phase) even "
                          "with one rank: a smoke test of the multi-GPU plumbing, not a benchmark")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: large grids as a fixed, seeded sample)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6 - 2**16  # 64 MB in all (decimal, so also under 64 MiB), .npy headers included
+DUMP_SAMPLE_SEED = 20260101
+
+
+def dump_outputs(dirname, arrays: dict) -> None:
+    """Write every array of `arrays` (torch tensors, numpy arrays or numbers; None is skipped) as
+    DIR/<name>.npy: float32 when the array is float32 or narrower, float64 otherwise.  Small arrays are
+    written whole and the rest of the budget is shared evenly over the large ones; an array with more elements
+    than its share is written as the sample at the flat indices
+    sorted(unique(numpy.random.default_rng(DUMP_SAMPLE_SEED).integers(0, size, share))), which depend on
+    nothing but the array's size: two builds given the same arguments write the same cells."""
+    import numpy as np
+
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    flat = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if hasattr(a, "detach"):  # torch tensor: sampled on its device, only the sample is copied
+            a = a.detach().reshape(-1)
+            narrow = a.dtype.is_floating_point and a.element_size() <= 4
+        else:
+            a = np.asarray(a).reshape(-1)
+            narrow = a.dtype.kind == "f" and a.dtype.itemsize <= 4
+        flat[name] = (a, np.dtype(np.float32 if narrow else np.float64))
+    budget, left = DUMP_BUDGET_BYTES, len(flat)
+    for name, (a, dt) in sorted(flat.items(), key=lambda kv: kv[1][0].shape[0] * kv[1][1].itemsize):
+        keep = budget // left // dt.itemsize
+        budget, left = budget - min(keep, a.shape[0]) * dt.itemsize, left - 1
+        if a.shape[0] > keep:
+            idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, a.shape[0], keep))
+            if hasattr(a, "detach"):
+                import torch
+
+                idx = torch.from_numpy(idx).to(a.device)
+            a = a[idx]
+        if hasattr(a, "detach"):
+            a = (a.float() if dt == np.float32 else a.double()).cpu().numpy()
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a, dtype=dt))
 
 
 def algorithmic_bytes_per_radius(n_cells: int, G: int) -> float:
@@ -396,6 +445,8 @@ def run_icpf(args, torch, pkg):
         step(True)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {**state["ics"], **{f"perturbed_{k}": v for k, v in state["out"].items()}})
     ic_ms, pf_ms = sum(t_ic) / len(t_ic), sum(t_pf) / len(t_pf)
     nk = dim * dim * (dim // 2 + 1)
     ic_bytes = 68 * 8.0 * nk
@@ -679,6 +730,13 @@ def main():
     if sharded and getattr(wl, "slab", False):
         ms_slab_resident = timed(lambda: wl.step_sharded(shard_c, gather=False), args.steps, 1)
         step()  # (the report / buffers of the headline form)
+    if args.dump_outputs and rank == owner:  # the owner holds the finished box in every sharded form
+        rep = last_report.get("rep")
+        dump_outputs(args.dump_outputs, {
+            "neutral_fraction": buffers.neutral_fraction, "z_reion": buffers.z_reion,
+            "kinetic_temperature": buffers.kinetic_temperature, "unnormalised_nion": buffers.unnormalised_nion,
+            **({"global_xH": [rep.global_xH], "mean_f_coll_out": [rep.mean_f_coll_out],
+                "f_coll_grid_mean": list(rep.f_coll_grid_mean)[:spec.n_radii]} if rep is not None else {})})
     cells = float(n) ** 3
     value = cells / (ms_per_step * 1e-3)
 

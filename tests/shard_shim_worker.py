@@ -40,7 +40,7 @@ class Ctx:
     def __init__(self):
         dist.init_process_group("gloo")
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
-        torch.cuda.set_device(0)
+        torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
         self.lib = pkg.load(require_gpu=True)
         self.shim = C.CDLL(os.environ["C21CM_RCCL_LIB"])
         self.failures, self.done, self.info = [], [], {}

@@ -7,7 +7,9 @@ GPU and the library binds tests/shim/librccl_shim.so instead of librccl (C21CM_R
 channels with RCCL's group and rendezvous semantics, checked on their own in tests/test_rccl_shim.py.  Only the
 transport differs from the 8-GPU run; xGMI timings remain unmeasured.
 
-tests/shard_shim_worker.py holds the cases; every rank compares with the single pass it computes itself."""
+tests/shard_shim_worker.py holds the cases; every rank compares with the single pass it computes itself.  Ranks are
+dealt round-robin over the visible GPUs; a world that would put more than four ranks on one GPU (six processes with
+the test process and the launcher: the suite's bound per GPU) skips itself, naming the GPUs it needs."""
 
 import json
 import os
@@ -21,9 +23,19 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 SHIM = ROOT / "tests" / "shim" / "librccl_shim.so"
+# the suite keeps at most this many processes on one GPU at once; besides the ranks dealt to it, this process and
+# the torch.distributed.run launcher hold it
+MAX_PROCESSES_PER_GPU = 6
 
 
 def launch(world, cases, tmp_path, timeout=1500):
+    import torch
+
+    gpus = torch.cuda.device_count()
+    ranks_per_gpu = MAX_PROCESSES_PER_GPU - 2
+    if -(-world // max(1, gpus)) > ranks_per_gpu:
+        pytest.skip(f"needs {-(-world // ranks_per_gpu)} GPUs for {world} ranks (at most {ranks_per_gpu} ranks "
+                    f"on one GPU beside the test process and the launcher), found {gpus}")
     if not SHIM.exists():
         subprocess.run(["make", "-C", str(SHIM.parent)], check=True)
     with socket.socket() as s:
