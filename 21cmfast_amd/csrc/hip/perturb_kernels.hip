@@ -53,6 +53,17 @@ __device__ __forceinline__ int wrap_idx(int i, int n) {
     return i < 0 ? i + n : i;
 }
 
+// A deposit position (in output cells) is converted to int only below 2^30: (int)floor of a NaN, an Inf or
+// anything beyond INT_MAX is undefined.  A position that fails !(|pos| < 2^30) takes cell 0 instead, and its
+// weights pos - 0 keep the NaN / Inf (the fp64 deposits carry it to the output as the reference's double grid
+// does; the fixed-point deposit raises its flag).  No valid input comes near: |pos| < 2^30 output cells.
+constexpr double kPosLimit = 1073741824.;  // 2^30
+__device__ __forceinline__ double safe_floor(double pos, bool &bad) {
+    if (fabs(pos) < kPosLimit) return floor(pos);
+    bad = true;
+    return 0.;
+}
+
 struct CicParams {
     int dens_dim[3], vel_dim[3], out_dim[3];
     double dim_ratio_vel, dim_ratio_out;
@@ -97,7 +108,8 @@ cic_scatter_kernel(CicParams p, const float *__restrict__ dens, const float *__r
             pos += (double)v[a] * p.vdf[a];
             if (p.lpt2) pos -= (double)v2[a] * p.vdf2[a];
             pos *= p.dim_ratio_out;
-            const double fl = floor(pos);
+            bool bad = false;  // (the NaN / Inf stays in dist: a non-finite output)
+            const double fl = safe_floor(pos, bad);
             const int ipos = (int)fl;
             const double dist = pos - (double)ipos;
             i0[a] = wrap_idx(ipos, p.out_dim[a]);
@@ -229,7 +241,8 @@ cic_scatter_tiled_kernel(CicTileParams q, const float *__restrict__ dens,
                 pos += (double)v[a] * p.vdf[a];
                 if (p.lpt2) pos -= (double)v2[a] * p.vdf2[a];
                 pos *= p.dim_ratio_out;
-                const double fl = floor(pos);
+                bool bad = false;  // (the NaN / Inf stays in the weights: a non-finite output)
+                const double fl = safe_floor(pos, bad);
                 ipos[a] = (int)fl;
                 const double dist = pos - (double)ipos[a];
                 w0[a] = 1. - dist;
@@ -351,6 +364,7 @@ constexpr double kFixScale = 17592186044416.;       // 2^44
 constexpr double kFixMagic = 6755399441055744.;     // 1.5 * 2^52: x + magic holds rint(x) in its low bits
 constexpr long long kFixMagicBits = 0x4338000000000000LL;
 constexpr double kFixFastLimit = 128.;              // |term| 2^44 < 2^51: the magic-number conversion is exact
+constexpr double kFixTermLimit = 262144.;           // 2^18: a queued particle's term (or mass) beyond it is flagged
 __device__ __forceinline__ long long to_fixed_fast(double term) {  // one fma and an integer subtraction
     return __double_as_longlong(fma(term, kFixScale, kFixMagic)) - kFixMagicBits;
 }
@@ -418,7 +432,7 @@ cic_cell_kernel(CicCellParams q, const float *__restrict__ dens, const float *__
                 }
             int rel[3][F];
             double w1[3][F];
-            bool inside = true;
+            bool inside = true, bad = false;
 #pragma unroll
             for (int a = 0; a < 3; a++) {
                 const double disp = (double)v[a] * p.vdf[a];
@@ -429,7 +443,7 @@ cic_cell_kernel(CicCellParams q, const float *__restrict__ dens, const float *__
                     pos += disp;
                     if (LPT2) pos -= disp2;
                     pos *= p.dim_ratio_out;
-                    const double fl = floor(pos);
+                    const double fl = safe_floor(pos, bad);
                     const int ip = (int)fl;
                     w1[a][j] = pos - (double)ip;
                     int r = ip - t0[a];
@@ -439,6 +453,31 @@ cic_cell_kernel(CicCellParams q, const float *__restrict__ dens, const float *__
                     inside = inside && r >= 0 && r + 1 < q.td[a] &&
                              (unsigned)(r - rel[a][0]) <= 1u;
                 }
+            }
+            float dmax = 0.f;  // FIXED: bound of the cell's particle masses
+            if constexpr (FIXED) {
+#pragma unroll
+                for (int jx = 0; jx < F; jx++)
+#pragma unroll
+                    for (int jy = 0; jy < F; jy++)
+#pragma unroll
+                        for (int jz = 0; jz < F; jz++) dmax = fmaxf(dmax, fabsf(dn[jx][jy][jz]));
+                float dsum = 0.f;  // (fmaxf drops a NaN, a sum keeps it; Inf stays Inf)
+#pragma unroll
+                for (int jx = 0; jx < F; jx++)
+#pragma unroll
+                    for (int jy = 0; jy < F; jy++)
+#pragma unroll
+                        for (int jz = 0; jz < F; jz++) dsum += fabsf(dn[jx][jy][jz]);
+                // 2^18 mean particle masses in ONE velocity cell's particles: no physical field gets near it
+                if (!(dsum < 3.0e38f) || (1.0 + (double)dmax * fabs(p.init_growth)) * (double)F3 > 262144.)
+                    bad = true;
+            }
+            // a flagged cell (non-finite / absurd mass or position) leaves through the queued path, which checks
+            // every term before it becomes an integer; its weights keep the NaN / Inf for the fp64 accumulation
+            if (bad) {
+                if constexpr (FIXED) atomicOr(&g_cic_fixed_bad, 1);
+                inside = false;
             }
             if (!inside) {
                 queue[atomicAdd(&nq, 1)] = e;
@@ -467,25 +506,6 @@ cic_cell_kernel(CicCellParams q, const float *__restrict__ dens, const float *__
                     }
                 }
             double acc[3][3][3];
-            float dmax = 0.f;  // FIXED: bound of the cell's particle masses
-            if constexpr (FIXED) {
-#pragma unroll
-                for (int jx = 0; jx < F; jx++)
-#pragma unroll
-                    for (int jy = 0; jy < F; jy++)
-#pragma unroll
-                        for (int jz = 0; jz < F; jz++) dmax = fmaxf(dmax, fabsf(dn[jx][jy][jz]));
-                float dsum = 0.f;  // (fmaxf drops a NaN, a sum keeps it; Inf stays Inf)
-#pragma unroll
-                for (int jx = 0; jx < F; jx++)
-#pragma unroll
-                    for (int jy = 0; jy < F; jy++)
-#pragma unroll
-                        for (int jz = 0; jz < F; jz++) dsum += fabsf(dn[jx][jy][jz]);
-                // 2^18 mean particle masses in ONE velocity cell's particles: no physical field gets near it
-                if (!(dsum < 3.0e38f) || (1.0 + (double)dmax * fabs(p.init_growth)) * (double)F3 > 262144.)
-                    atomicOr(&g_cic_fixed_bad, 1);
-            }
             const bool small = (1.0 + (double)dmax * fabs(p.init_growth)) * (double)F3 < kFixFastLimit;
 #pragma unroll
             for (int jx = 0; jx < F; jx++) {
@@ -567,6 +587,7 @@ cic_cell_kernel(CicCellParams q, const float *__restrict__ dens, const float *__
             int s[3];
             size_t bo[3][2];
             double w[3][2];
+            bool bad = false;
 #pragma unroll
             for (int a = 0; a < 3; a++) {
                 s[a] = F * m[a] + q.lo + j[a];
@@ -575,7 +596,7 @@ cic_cell_kernel(CicCellParams q, const float *__restrict__ dens, const float *__
                 pos += (double)v[a] * p.vdf[a];
                 if (LPT2) pos -= (double)v2[a] * p.vdf2[a];
                 pos *= p.dim_ratio_out;
-                const double fl = floor(pos);
+                const double fl = safe_floor(pos, bad);
                 const int ip = (int)fl;
                 const double dist = pos - (double)ip;
                 w[a][0] = 1. - dist;
@@ -586,17 +607,25 @@ cic_cell_kernel(CicCellParams q, const float *__restrict__ dens, const float *__
             }
             const double mass =
                 1.0 + (double)dens[((size_t)s[0] * d1 + (size_t)s[1]) * d2 + s[2]] * p.init_growth;
+            // (defensive: the tile side has already flagged every cell with a bad position or mass before it
+            //  queued it; what these checks add is that no NaN / Inf / absurd term reaches the int conversion)
+            if constexpr (FIXED)
+                if (bad || !(fabs(mass) < kFixTermLimit)) atomicOr(&g_cic_fixed_bad, 1);
 #pragma unroll
             for (int a = 0; a < 2; a++)
 #pragma unroll
                 for (int b = 0; b < 2; b++)
 #pragma unroll
                     for (int c = 0; c < 2; c++) {
-                        const double term = mass * ((w[0][a] * w[1][b]) * w[2][c]);
-                        if constexpr (FIXED)
+                        double term = mass * ((w[0][a] * w[1][b]) * w[2][c]);
+                        if constexpr (FIXED) {
+                            if (!(fabs(term) < kFixTermLimit)) {  // NaN / Inf / absurd: flagged, never converted
+                                atomicOr(&g_cic_fixed_bad, 1);
+                                term = 0.;
+                            }
                             atomicAdd(reinterpret_cast<unsigned long long *>(out) + bo[0][a] + bo[1][b] + bo[2][c],
                                       (unsigned long long)to_fixed(term));
-                        else
+                        } else
                             unsafeAtomicAdd(out + bo[0][a] + bo[1][b] + bo[2][c], term);
                     }
         }
@@ -989,6 +1018,12 @@ extern "C" int c21hip_cic_fixed_status(int *bad, void *stream) {
     return 0;
 }
 
+namespace {
+int g_cic_last_path = 0;  // c21hip_cic_last_path: 1 cell, 2 tiled, 3 direct
+}
+
+extern "C" int c21hip_cic_last_path(void) { return g_cic_last_path; }
+
 extern "C" int c21hip_cic_scatter(const float *hires_density, const int dens_dim[3],
                                   const float *const vel[3], const float *const vel2[3],
                                   const int vel_dim[3], double *out, const int out_dim[3],
@@ -998,6 +1033,7 @@ extern "C" int c21hip_cic_scatter(const float *hires_density, const int dens_dim
     fill_cic_params(p, dens_dim, vel_dim, out_dim, box_len, box_len_z, growth, init_growth, lpt2);
     const size_t total = (size_t)dens_dim[0] * dens_dim[1] * dens_dim[2];
     if (fixed_out) *fixed_out = 0;
+    g_cic_last_path = 0;  // (set again by the launch that follows; an early error leaves no stale path)
     {
         // C21CM_CIC = cell (default: per velocity cell, LDS tile) | tiled (per particle, LDS tile;
         // rounds 1-3) | direct (global atomics); tiny grids take the direct kernel
@@ -1039,6 +1075,7 @@ extern "C" int c21hip_cic_scatter(const float *hires_density, const int dens_dim
                     else
                         launch_cell<4, 0, true>(q, lds, blocks, lpt2, hires_density, vel, vel2, out, (hipStream_t)stream);
                     LAUNCH_CHECK();
+                    g_cic_last_path = 1;
                     return 0;
                 }
                 if (f == 1)
@@ -1050,6 +1087,7 @@ extern "C" int c21hip_cic_scatter(const float *hires_density, const int dens_dim
                 else
                     launch_cell<4, 0>(q, lds, blocks, lpt2, hires_density, vel, vel2, out, (hipStream_t)stream);
                 LAUNCH_CHECK();
+                g_cic_last_path = 1;
                 return 0;
             }
         }
@@ -1064,6 +1102,7 @@ extern "C" int c21hip_cic_scatter(const float *hires_density, const int dens_dim
                                    lpt2 ? vel2[2] : nullptr, (const float *)nullptr, out,
                                    (double *)nullptr, (double *)nullptr);
                 LAUNCH_CHECK();
+                g_cic_last_path = 2;
                 return 0;
             }
         }
@@ -1073,6 +1112,7 @@ extern "C" int c21hip_cic_scatter(const float *hires_density, const int dens_dim
                        lpt2 ? vel2[0] : nullptr, lpt2 ? vel2[1] : nullptr,
                        lpt2 ? vel2[2] : nullptr, out);
     LAUNCH_CHECK();
+    g_cic_last_path = 3;
     return 0;
 }
 

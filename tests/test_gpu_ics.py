@@ -11,7 +11,9 @@ import importlib
 import numpy as np
 import pytest
 
+from cic_reference import cic_last_path, density_error, oracle_threads
 from test_oracle_ics import LOWRES_FIELDS, ics_spec
+from test_oracle_perturb import perturb_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -24,6 +26,7 @@ def api(gpu_lib):
 def compare(got, ref, names=None):
     for k in names or ref.keys():
         a = got[k] if isinstance(got[k], np.ndarray) else got[k].cpu().numpy()
+        assert np.isfinite(ref[k]).all(), k  # (assert_allclose passes where both sides are NaN)
         scale = np.abs(ref[k]).max()
         np.testing.assert_allclose(a, ref[k], atol=3e-5 * scale + 1e-12, rtol=1e-4, err_msg=k)
 
@@ -205,13 +208,15 @@ def test_relative_velocities_through_the_entry_point(gpu_lib, api, oracle, tmp_p
 
 
 @pytest.mark.parametrize("dim,hii,dim_z,hii_z", [(1024, 512, 128, 64), (1536, 512, 192, 64)])
-def test_split_pipeline_on_x_blocked_spectra(api, monkeypatch, dim, hii, dim_z, hii_z):
+def test_split_pipeline_on_x_blocked_spectra(api, oracle, monkeypatch, dim, hii, dim_z, hii_z):
     """DIM >= 1024: the main block of a split spectrum is stored x-blocked ([x / 8][y][x % 8][k_z]); the
     element-wise kernels of the split IC pipeline (k^2 division, top-hat, fold by 2 and by 3 -- the
     reference's default DIM = 3 HII_DIM at HII_DIM = 512) map memory lines to wavenumbers through
     split_layout.h.  On a thin 1024 x 1024 x 128 / 1536 x 1536 x 192 box with a given density the
     split pipeline agrees with the padded one (rocFFT, full-size transforms + gathers) to transform
-    round-off, for every output."""
+    round-off, for every output, and with the oracle (density_is_input); the PerturbedField of its output
+    (cell deposit, F = 2 / F = 3: the reference's default geometry) agrees with the oracle's.  (Thinner boxes
+    would leave the split pipeline: 512 x 512 x 32 or x 16 output grids are not native transform sizes.)"""
     import torch
 
     L = 1.5 * hii
@@ -236,4 +241,60 @@ def test_split_pipeline_on_x_blocked_spectra(api, monkeypatch, dim, hii, dim_z, 
         x, y = out["split"][k], out["padded"][k]
         assert np.abs(y).max() > 0, k
         np.testing.assert_allclose(x, y, atol=3e-5 * np.abs(y).max(), rtol=1e-4, err_msg=k)
+    # ... and the split pipeline meets the oracle, whose PerturbedField then meets the cell kernel's (F = 2, 3)
+    monkeypatch.delenv("C21CM_ICS")
+    lib = api.load()
+    assert lib.c21hip_native_fft_supported(dim, dim, dim_z) and lib.c21hip_native_fft_supported(hii, hii, hii_z)
+    oracle.set_threads(oracle_threads())
+    ref_start = oracle.new_ics_arrays(spec)
+    ref_start["hires_density"][...] = dens.cpu().numpy()
+    del dens
+    ref = oracle.ics_grids(spec, ref_start)
+    compare(out["split"], ref, LOWRES_FIELDS)
+    compare_perturbed(api, oracle, spec, out["split"])
+    lib.c21cm_release_device_cache()
+
+
+def compare_perturbed(api, oracle, spec, ics_host):
+    """Both sides' PerturbedField (2LPT, 3D velocities) on the same ICs: the device ICs copied to the host.
+    The library runs on the device and must take the cell deposit; density at 2e-6 max|delta|, rtol 0 (as
+    tests/test_gpu_perturb.py; observed 2.4e-7 to 3.1e-7 at config 2 and on the x-blocked boxes), velocities
+    at its 2e-5 max|v|, rtol 1e-4."""
+    import torch
+
+    pspec = perturb_spec(2, dim=spec.dim, dim_z=spec.dim_z, hii_dim=spec.hii_dim, hii_dim_z=spec.hii_dim_z,
+                         box_len=spec.box_len, box_len_z=spec.box_len_z, growth_factor=0.127,
+                         init_growth_factor=0.0042, dDdt_over_D=2e-17, keep_3d_velocities=1)
+    ics_dev = {k: torch.from_numpy(v).cuda() for k, v in ics_host.items()}
+    got = {k: v.cpu().numpy() for k, v in api.perturb_grids(pspec, ics_dev).items()}
+    assert cic_last_path(api) == "cell"
+    del ics_dev
+    torch.cuda.empty_cache()
+    ref = oracle.perturb_grids(pspec, ics_host)
+    assert np.isfinite(ref["density"]).all() and ref["density"].std() > 0
+    err = density_error(got["density"], ref["density"])
+    print(f"\n[PerturbedField DIM {spec.dim} x {spec.dim} x {spec.dim_z}] max|ddelta|/max|delta| vs oracle: {err:.2e}")
+    assert err <= 2e-6
+    for k in ref:
+        if k != "density":
+            assert np.isfinite(ref[k]).all(), k
+            scale = np.abs(ref[k]).max()
+            np.testing.assert_allclose(got[k], ref[k], atol=2e-5 * scale + 1e-9, rtol=1e-4, err_msg=k)
+
+
+@pytest.mark.parametrize("stream", ["gsl", "philox"])
+def test_config2_full_size_vs_oracle(api, oracle, stream):
+    """BASELINE config 2 at its own size (DIM 512, HII_DIM 256, 2LPT) against the oracle: the default
+    reference-compatible GSL stream (rng_stream 1, N_THREADS 2) and Philox, the stream bench.py --mode icpf
+    times.  Every output field at the module's 3e-5 max|field|; then the device ICs, copied to the host, go
+    through both sides' PerturbedField (the cell deposit at F = 2)."""
+    spec = ics_spec(512, 256, box_len=384.0, seed=12345)
+    if stream == "gsl":
+        spec.rng_stream, spec.rng_threads = 1, 2
+    got = {k: v.cpu().numpy() for k, v in api.ics_grids(spec, device="cuda").items()}
     api.load().c21cm_release_device_cache()
+    oracle.set_threads(oracle_threads())
+    ref = oracle.ics_grids(spec)
+    assert set(ref) == set(got)
+    compare(got, ref)
+    compare_perturbed(api, oracle, spec, got)

@@ -10,6 +10,8 @@ import importlib
 import numpy as np
 import pytest
 
+from cic_reference import (CELL_GEOMETRIES, cic_last_path, density_error, geometry_ics, oracle_threads,
+                           perturbed_density_f64)
 from test_oracle_perturb import expected_density, fake_ics, perturb_spec
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +47,7 @@ def random_ics(n, N, seed, hires_vel=False):
 
 def compare(got, ref):
     for k in ref:
+        assert np.isfinite(ref[k]).all(), k  # (assert_allclose passes where both sides are NaN)
         scale = np.abs(ref[k]).max()
         np.testing.assert_allclose(got[k], ref[k], atol=2e-5 * scale + 1e-9, rtol=1e-4,
                                    err_msg=k)
@@ -242,3 +245,146 @@ def test_deposit_implementations_agree(api, n, N, nz, hires, monkeypatch):
     for mode in ("cell", "tiled"):
         np.testing.assert_allclose(out[mode], out["direct"], atol=3e-7 * scale, rtol=2e-6,
                                    err_msg=mode)
+
+
+# ---- the default deposit (cic_cell_kernel) against the oracle and a float64 numpy CIC -----------------
+
+DENSITY_TOL = 2e-6  # x max|delta|, rtol 0
+
+
+@pytest.mark.parametrize("disp", [0.4, 5.0, "wrap2"])
+@pytest.mark.parametrize("algorithm", [2, 1])
+@pytest.mark.parametrize("n,nz,f,hires", CELL_GEOMETRIES)
+def test_cell_deposit_geometries_vs_references(api, oracle, n, nz, f, hires, algorithm, disp):
+    """The default deposit (cic_cell_kernel, F = DIM / HII_DIM = 1 ... 4, asserted to have run) against the
+    oracle and, on the low-resolution branch, against a plain float64 numpy CIC (tests/cic_reference.py):
+    cubic and non-cubic boxes, partial bricks, 2LPT on and off, displacements well inside the tile halo
+    (0.4 cells rms), beyond it (5 cells: the queued global path) and beyond two box lengths (particles wrap
+    twice), and the first velocity plane, whose sources wrap, moving three times as far.
+    Density: atol 2e-6 max|delta|, rtol 0 -- the deposit is exact to ~1e-12, what is left is the float
+    rounding of the deposit and the float32 transforms.  Observed on an MI355X: at most 3.5e-7 max|delta|
+    against numpy, 3.4e-7 against the oracle on the low-resolution branch and 8.4e-7 on the hi-res one (two
+    more float32 transforms and the top-hat filter).  Velocities keep the module's tolerance."""
+    if disp == "wrap2":
+        disp = 2.5 * max(n, nz)
+    spec, ics = geometry_ics(n, nz, f, hires, disp, seed=100 * n + 10 * f + nz + algorithm)
+    spec.perturb_algorithm = algorithm
+    got = api.perturb_grids(spec, ics)
+    assert cic_last_path(api) == "cell"
+    ref = oracle.perturb_grids(spec, ics)
+    assert np.isfinite(ref["density"]).all() and ref["density"].std() > 0
+    err_oracle = density_error(got["density"], ref["density"])
+    msg = f"oracle {err_oracle:.2e}"
+    if not hires:
+        exact = perturbed_density_f64(spec, ics)
+        err_exact = density_error(got["density"], exact)
+        err_pin = density_error(ref["density"], exact)
+        msg += f", numpy {err_exact:.2e} (oracle vs numpy {err_pin:.2e})"
+        assert err_exact <= DENSITY_TOL, msg
+        assert err_pin <= DENSITY_TOL, msg
+    print(f"\n[cell deposit n={n} nz={nz} F={f} hires={hires} alg={algorithm} disp={disp}] max|ddelta|/max|delta|: {msg}")
+    assert err_oracle <= DENSITY_TOL, msg
+    compare({k: v for k, v in got.items() if k != "density"},
+            {k: v for k, v in ref.items() if k != "density"})
+
+
+def test_cell_deposit_default_geometry_full_size(api, oracle):
+    """The reference's default geometry at size: HII_DIM 256, DIM 768 (F = 3) on the cell kernel with
+    synthetic device ICs, perturb only, against the oracle (density at the tight bound above; observed
+    3.2e-7 max|delta|)."""
+    import torch
+
+    n, N = 256, 768
+    g = torch.Generator(device="cuda").manual_seed(768)
+    ics = {}
+    for ax in "xyz":
+        ics[f"lowres_v{ax}"] = 2.0 * torch.randn((n,) * 3, generator=g, device="cuda")
+        ics[f"lowres_v{ax}_2LPT"] = 1.0 * torch.randn((n,) * 3, generator=g, device="cuda")
+    d = torch.randn((N,) * 3, generator=g, device="cuda")
+    ics["hires_density"] = (d - d.mean()).contiguous()
+    del d
+    spec = perturb_spec(2, dim=N, dim_z=N, hii_dim=n, hii_dim_z=n, box_len=384.0, box_len_z=384.0,
+                        growth_factor=0.127, init_growth_factor=0.0042, dDdt_over_D=2e-17,
+                        keep_3d_velocities=1)
+    got = {k: v.cpu().numpy() for k, v in api.perturb_grids(spec, ics).items()}
+    assert cic_last_path(api) == "cell"
+    host = {k: v.cpu().numpy() for k, v in ics.items()}
+    del ics
+    torch.cuda.empty_cache()
+    oracle.set_threads(oracle_threads())
+    ref = oracle.perturb_grids(spec, host)
+    err = density_error(got["density"], ref["density"])
+    print(f"\n[cell deposit 256 / 768] max|ddelta|/max|delta| vs oracle: {err:.2e}")
+    assert err <= DENSITY_TOL
+    compare({k: v for k, v in got.items() if k != "density"},
+            {k: v for k, v in ref.items() if k != "density"})
+
+
+# ---- non-finite inputs on the cell kernel: status 7, never a finite wrong field --------------------------
+
+POISON_N = {1: 32, 2: 24, 3: 24, 4: 24}  # HII_DIM per F: the cell kernel's geometry, >= 2^15 particles
+QUEUED_CELL = (5, 6, 7)
+
+
+def poison(ics, f, kind, value):
+    """A copy of `ics` with one poisoned input.  kinds: v{x,y,z} / v{x,y,z}_2LPT (one velocity cell),
+    queued_density (a hi-res density under a velocity cell moved 60x as far: the queued path)."""
+    out = {k: v.copy() for k, v in ics.items()}
+    m = QUEUED_CELL
+    if kind == "queued_density":
+        for ax in "xyz":
+            out[f"lowres_v{ax}"][m] *= 60.0
+        lo = -(f // 2)
+        out["hires_density"][tuple(f * c + lo + (f - 1) for c in m)] = value
+    else:
+        out[f"lowres_{kind}"][m] = value
+    return out
+
+
+NAN, INF = float("nan"), float("inf")
+NONFINITE_POISONS = [("vx", NAN), ("vy", INF), ("vz", -INF), ("vx", -INF), ("vy", NAN), ("vz", INF),
+                     ("vy_2LPT", NAN), ("vz_2LPT", -INF), ("queued_density", NAN), ("queued_density", INF)]
+
+
+def poison_case(f):
+    n = POISON_N[f]
+    spec, ics = geometry_ics(n, n, f, False, 1.0, seed=f)
+    return spec, ics
+
+
+@pytest.mark.parametrize("f", [1, 2, 3, 4])
+def test_non_finite_positions_are_an_error_on_the_cell_kernel(api, oracle, f):
+    """A NaN / +-Inf velocity component (x, y, z), 2LPT component, hi-res density of a cell on the queued path,
+    or an absurd finite velocity (1e30) make the fixed-point cell deposit return InfinityorNaNError (7) -- the
+    position is tested before any int conversion, a queued term before it becomes an integer -- and the next
+    clean call matches the oracle again."""
+    spec, ics = poison_case(f)
+    ref = oracle.perturb_grids(spec, ics)
+    for kind, value in NONFINITE_POISONS + [("vx", 1e30), ("vz_2LPT", -1e30)]:
+        with pytest.raises(RuntimeError, match="status 7"):
+            api.perturb_grids(spec, poison(ics, f, kind, value))
+        assert cic_last_path(api) == "cell", (kind, value)
+        got = api.perturb_grids(spec, ics)
+        assert density_error(got["density"], ref["density"]) <= DENSITY_TOL, (kind, value)
+    compare(got, ref)
+
+
+@pytest.mark.parametrize("mode", ["double", "tiled", "direct"])
+@pytest.mark.parametrize("f", [1, 2, 3, 4])
+def test_non_finite_positions_never_give_a_finite_field(api, f, mode, monkeypatch):
+    """The fp64 deposits (C21CM_CIC_ACC=double, C21CM_CIC=tiled|direct): a NaN / Inf position still forms its
+    index from a safe cell, and the NaN / Inf flows on into the weights -- the output is non-finite (or the
+    call returns status 7), never a finite field."""
+    spec, ics = poison_case(f)
+    if mode == "double":
+        monkeypatch.setenv("C21CM_CIC_ACC", "double")
+    else:
+        monkeypatch.setenv("C21CM_CIC", mode)
+    for kind, value in NONFINITE_POISONS:
+        try:
+            out = api.perturb_grids(spec, poison(ics, f, kind, value))
+        except RuntimeError as e:
+            assert "status 7" in str(e), (kind, value)
+            continue
+        assert cic_last_path(api) == ("cell" if mode == "double" else mode)
+        assert not np.isfinite(out["density"]).all(), (kind, value)

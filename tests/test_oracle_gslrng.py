@@ -123,3 +123,21 @@ def test_product_host_stream_equals_oracle(olib, pkg, n_threads, shape):
     assert olib.oracle_gsl_mode_deviates(777, nx + 3, nx, ny, nz, b2.ctypes.data) == 0
     np.testing.assert_array_equal(a2, b2)
     assert lib.c21_gsl_mode_deviates(777, 0, nx, ny, nzc, a.ctypes.data) == 3
+
+
+@pytest.mark.parametrize("n_threads", [1, 2, 16])
+def test_product_host_stream_equals_oracle_at_config2_size(olib, pkg, n_threads):
+    """The same pin at the size the IC pipeline draws for BASELINE config 2 (DIM = 512: 512 x 512 x 257 modes,
+    two float64 arrays of 1.08 GB): bit for bit, for one, two and sixteen N_THREADS streams."""
+    lib = pkg.load()
+    lib.c21_gsl_mode_deviates.restype = C.c_int
+    lib.c21_gsl_mode_deviates.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]
+    nx = ny = nz = 512
+    nzc = nz // 2 + 1
+    a = np.zeros((nx, ny, nzc, 2))
+    assert lib.c21_gsl_mode_deviates(12345, n_threads, nx, ny, nzc, a.ctypes.data) == 0
+    b = np.zeros_like(a)
+    assert olib.oracle_gsl_mode_deviates(12345, n_threads, nx, ny, nz, b.ctypes.data) == 0
+    assert np.array_equal(a, b), f"{int((a != b).sum())} deviates differ"
+    assert 0.99 < a[::7, ::5].std() < 1.01
