@@ -683,6 +683,28 @@ int c21hip_apply_first_cross(const unsigned char *first_cross, const float *prev
                              int first_snapshot, double redshift, float *xH, float *z_reion,
                              size_t ntot, void *stream);
 
+/* ---- lightcone_kernels.hip : rectilinear lightcone slabs and the dv/dr correction (lightconers.py,
+ * rsds.py) ---- */
+#define C21HIP_LC_MAX_FIELDS 16
+typedef struct c21hip_lc_slice { /* one slice of a node pair's run, built by the host */
+    int plane;                   /* node-box plane along the line of sight, in [0, d_para) */
+    int pad_;
+    double w_lo, w_hi;           /* weights of the low- and high-redshift box */
+} c21hip_lc_slice;
+/* slices j in [0, run) of every column: dst[q][col*dst_stride + dst_off + j] from plane tab[j].plane
+ * of lo[q] / hi[q] (boxes of n_cols columns of d_para planes); bit q of mean_max: z_reion's rule */
+int c21hip_lightcone_slab(const float *const *lo, const float *const *hi, float *const *dst,
+                          int n_fields, unsigned mean_max, size_t n_cols, int run, int d_para,
+                          long dst_stride, long dst_off, const c21hip_lc_slice *tab, double w_norm,
+                          void *stream);
+/* brightness_temp corrected in place by the line-of-sight gradient of vel (n_slices >= 3);
+ * hubble: H(z) [1/s] per slice, device; tau: USE_TS_FLUCT only */
+int c21hip_lightcone_dvdr(float *bt, const float *vel, const float *tau, const double *hubble,
+                          size_t n_cols, int n_slices, double dx, double max_dvdr, int use_ts,
+                          void *stream);
+int c21hip_d2h_2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width,
+                  size_t height, void *stream);
+
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */
 typedef struct c21hip_ts_args { /* the scalars of c21cm_ts_spec, passed by value */

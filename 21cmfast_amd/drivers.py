@@ -3,7 +3,9 @@ loop of ``run_coeval`` (reference: src/py21cmfast/drivers/coeval.py:560-890) as 
 ``Inputs`` below, and the bookkeeping that sits between the C entry points of the
 spin-temperature path for the Lagrangian source models
 (reference: src/py21cmfast/drivers/single_field.py:382-470 ``interp_halo_boxes`` and :473-636
-``compute_xray_source_field``).  A py21cmfast installation keeps using its own drivers on top of
+``compute_xray_source_field``), and the rectilinear lightcone of ``run_lightcone``
+(reference: src/py21cmfast/lightconers.py, drivers/lightcone.py) with its slabs and dv/dr correction on
+the device.  A py21cmfast installation keeps using its own drivers on top of
 the library; this module is for callers without it (tests, tools, stand-alone runs).
 
 The reference does this bookkeeping in Python with astropy: the shells of the X-ray / Lyman-alpha
@@ -355,6 +357,37 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
     ``inspect(z, ctx)``: test hook called after every snapshot with the structs its
     ComputeIonizedBox call was given (``ctx["new_ion"]()`` allocates another output box)."""
     lib = lib or load(require_gpu=True)
+    out_redshifts = [float(np.float32(z)) for z in out_redshifts]
+    all_redshifts, is_node = required_redshifts(inputs, out_redshifts)
+    wanted = set(out_redshifts)
+    result, history = {}, []
+    mini = bool(inputs.astro_options.USE_MINI_HALOS)
+    snaps = _snapshots(inputs, all_redshifts, is_node, inputs.evolution_required, data_path=data_path,
+                       device=device, lib=lib, progress=progress, halo_catalogs=halo_catalogs,
+                       inspect=inspect, history=history)
+    ics = None
+    for z, boxes, ion, ts, ics in snaps:
+        if z in wanted:
+            snap = {k: boxes[k] for k in keep if k in boxes}
+            snap["mean_f_coll"], snap["Q_HI"] = ion.mean_f_coll, ts.Q_HI
+            if mini:
+                snap["mean_f_coll_MINI"] = ion.mean_f_coll_MINI
+                snap["log10_Mturnover_ave"] = ion.log10_Mturnover_ave
+                snap["log10_Mturnover_MINI_ave"] = ion.log10_Mturnover_MINI_ave
+            result[z] = snap
+    result["history"] = history
+    result["initial_conditions"] = ics
+    return result
+
+
+def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, device, lib, progress,
+               halo_catalogs, inspect, history):
+    """The per-snapshot body shared by ``run_coeval`` and ``run_lightcone``: yields
+    ``(z, boxes, ion, ts, ics)`` for every redshift of ``all_redshifts`` (descending), ``boxes`` the
+    snapshot's arrays by name, ``ion`` / ``ts`` its IonizedBox / TsBox structs.  A node (``z in
+    is_node``) becomes the next snapshot's "previous" one when ``chain`` is true (run_coeval: only
+    for evolution runs, coeval.py:878-884; a lightcone: always).  Appends the global signal
+    (z, mean dT_b, mean x_HI, mean T_s) of every snapshot to ``history``."""
     from . import grid_api as api
 
     so, mo, ao, ap = (inputs.simulation_options, inputs.matter_options, inputs.astro_options,
@@ -417,16 +450,12 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
         arr = {k: new() for k in TS_FIELDS + (("J_21_LW",) if mini else ())}
         return arr, S.TsBoxStruct(**{k: fp(v) for k, v in arr.items()})
 
-    out_redshifts = [float(np.float32(z)) for z in out_redshifts]
-    all_redshifts, is_node = required_redshifts(inputs, out_redshifts)
-    wanted = set(out_redshifts)
     prev_ion_arr, prev_ion = new_ion()
     prev_ts_arr, prev_ts = new_ts()
     prev_pf_arr = None
     prev_z, prev_xHI = 0.0, None
     prev_means = (0.0, 0.0)
     z_halos, hboxes = [], []
-    result, history = {}, []
     for z in all_redshifts:
         pf_arr = {"density": new(), "velocity_z": new()}
         pf = S.PerturbedFieldStruct(**{k: fp(v) for k, v in pf_arr.items()})
@@ -495,20 +524,212 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
             inspect(z, dict(prev_z=prev_z, pf=pf, prev_pf=prev_pf, prev_ion=prev_ion, ts=ts, hb=hb,
                             icss=icss, ion=ion, ion_arr=ion_arr, ts_arr=ts_arr, pf_arr=pf_arr,
                             new_ion=new_ion))
-        if z in wanted:
-            boxes = {**pf_arr, **hb_arr, **ts_arr, **ion_arr, **bt_arr}
-            snap = {k: boxes[k] for k in keep if k in boxes}
-            snap["mean_f_coll"], snap["Q_HI"] = ion.mean_f_coll, ts.Q_HI
-            if mini:
-                snap["mean_f_coll_MINI"] = ion.mean_f_coll_MINI
-                snap["log10_Mturnover_ave"] = ion.log10_Mturnover_ave
-                snap["log10_Mturnover_MINI_ave"] = ion.log10_Mturnover_MINI_ave
-            result[z] = snap
+        yield z, {**pf_arr, **hb_arr, **ts_arr, **ion_arr, **bt_arr}, ion, ts, ics
         if z in is_node:
             prev_means = (ion.mean_f_coll, ion.mean_f_coll_MINI)
-        if inputs.evolution_required and z in is_node:  # only nodes are the next one's "previous"
+        if chain and z in is_node:  # only nodes are the next one's "previous"
             prev_ts_arr, prev_ts, prev_ion_arr, prev_ion, prev_pf_arr, prev_z = (
                 ts_arr, ts, ion_arr, ion, pf_arr, z)
-    result["history"] = history
-    result["initial_conditions"] = ics
-    return result
+
+
+# =============================================================================================
+# Rectilinear lightcones (reference: src/py21cmfast/lightconers.py:36-319,483-529 and
+# drivers/lightcone.py:172-181,249-277,544-575).  The slabs and the dv/dr correction are HIP
+# kernels (csrc/hip/lightcone_kernels.hip); the geometry below is the host's.
+# =============================================================================================
+class RectilinearLightconer:
+    """Slices at comoving distances ``lc_distances`` [Mpc] along the last axis of the node boxes
+    (RectilinearLightconer, lightconers.py:483-529).  ``index_offset`` (default: the number of
+    slices) places the back of the lightcone on the back of the node box; ``interp_kinds`` maps a
+    quantity to "mean" (default) or "mean_max" (``z_reion``).  ``cosmo``: a FlatCosmology, by
+    default that of the default CosmoParams."""
+
+    def __init__(self, lc_distances, quantities=("brightness_temp",), cosmo=None, index_offset=None,
+                 interp_kinds=None):
+        self.lc_distances = np.asarray(lc_distances, float)
+        if self.lc_distances.ndim != 1 or len(self.lc_distances) == 0:
+            raise ValueError("lc_distances must be a non-empty 1-D array")
+        if np.any(self.lc_distances < 0):
+            raise ValueError("lc_distances must be non-negative")
+        if cosmo is None:
+            cp = S.default_cosmo_params()
+            cosmo = FlatCosmology(cp.hlittle, cp.OMm)
+        self.cosmo = cosmo
+        self.quantities = tuple(quantities)
+        self.index_offset = len(self.lc_distances) if index_offset is None else int(index_offset)
+        self.interp_kinds = {"z_reion": "mean_max"} if interp_kinds is None else dict(interp_kinds)
+        for k, v in self.interp_kinds.items():
+            if v not in ("mean", "mean_max"):
+                raise ValueError(f"interp_kinds[{k!r}] must be 'mean' or 'mean_max'")
+        self._lc_redshifts = None
+
+    @classmethod
+    def between_redshifts(cls, min_redshift, max_redshift, resolution, quantities=("brightness_temp",),
+                          cosmo=None, **kw):
+        """Regular comoving-distance slices ``resolution`` [Mpc] apart from ``min_redshift`` to
+        past ``max_redshift`` (lightconers.py:116-131)."""
+        if cosmo is None:
+            cp = S.default_cosmo_params()
+            cosmo = FlatCosmology(cp.hlittle, cp.OMm)
+        d0 = cosmo.comoving_distance(float(min_redshift))
+        d1 = cosmo.comoving_distance(float(max_redshift))
+        res = float(resolution)
+        return cls(np.arange(d0, d1 + res, res), quantities=quantities, cosmo=cosmo, **kw)
+
+    @property
+    def lc_redshifts(self) -> np.ndarray:
+        """Redshift of every slice: z at the two ends, np.interp on a 100-point log grid in between
+        (lightconers.py:89-101, drivers/lightcone.py:172-181)."""
+        if self._lc_redshifts is None:
+            d = self.lc_distances
+            zmin = self.cosmo.z_at_comoving_distance(d.min())
+            zmax = self.cosmo.z_at_comoving_distance(d.max())
+            zgrid = np.logspace(np.log10(zmin), np.log10(zmax), 100)
+            self._lc_redshifts = np.interp(d, self.cosmo.comoving_distance(zgrid), zgrid)
+        return self._lc_redshifts
+
+    def get_shape(self, simulation_options) -> tuple:
+        return (int(simulation_options.HII_DIM), int(simulation_options.HII_DIM), len(self.lc_distances))
+
+    def lightcone_dimensions(self, simulation_options) -> tuple:
+        """(x, y, line of sight) extent in Mpc (LightCone.lightcone_dimensions)."""
+        so = simulation_options
+        cell = float(so.BOX_LEN) / float(so.HII_DIM)
+        return (float(so.BOX_LEN), float(so.BOX_LEN), len(self.lc_distances) * cell)
+
+    def slab_tables(self, z_lo, z_hi, cell_size, d_para):
+        """The slices between the nodes at ``z_lo`` < ``z_hi`` and how to fill them
+        (make_lightcone_slices :189-207, coeval_subselect :505-515, redshift_interpolation :307-309):
+        returns (i0, plane, w_lo, w_hi, w_norm), or None when no slice lies between the two.
+        Distances are in pixels of ``cell_size`` [Mpc]; ``plane`` indexes the node boxes' last axis
+        (``d_para`` planes, wrapped)."""
+        pix = self.lc_distances / float(cell_size)
+        dc_lo = self.cosmo.comoving_distance(float(z_lo)) / float(cell_size)
+        dc_hi = self.cosmo.comoving_distance(float(z_hi)) / float(cell_size)
+        dcmin, dcmax = min(dc_lo, dc_hi), max(dc_lo, dc_hi)
+        # tolerance at the low-redshift end: the last slice may sit exactly on the lowest node
+        idx = np.nonzero((pix >= dcmin * (1 - 1e-6)) & (pix < dcmax))[0]
+        if len(idx) == 0:
+            return None
+        if np.any(np.diff(idx) != 1):
+            raise ValueError("lc_distances must be increasing")
+        lcd = pix[idx]
+        lcidx = np.array([int(v) for v in (pix.max() - lcd + 1)], np.int64)
+        plane = np.mod(-lcidx + self.index_offset, int(d_para)).astype(np.int32)
+        w_lo = np.abs(dc_hi - lcd)
+        w_hi = np.abs(dc_lo - lcd)
+        return int(idx[0]), plane, w_lo, w_hi, abs(dc_lo - dc_hi)
+
+
+def lightcone_fields(inputs: Inputs) -> set:
+    """Names of the (HII_DIM, HII_DIM, HII_D_PARA) fields a run with these inputs produces per node,
+    plus ``los_velocity`` (the line-of-sight velocity, i.e. ``velocity_z``)."""
+    mo, ao = inputs.matter_options, inputs.astro_options
+    lagrangian, ts_on, mini = mo.SOURCE_MODEL >= 2, bool(ao.USE_TS_FLUCT), bool(ao.USE_MINI_HALOS)
+    out = {"density", "velocity_z", "los_velocity", "brightness_temp"} | set(ION_FIELDS)
+    if mo.MINIMIZE_MEMORY:
+        out -= {"kinetic_temperature", "mean_free_path"}
+    if ao.RECOMB_MODEL == 0:
+        out.discard("cumulative_recombinations")
+    if mini and not lagrangian:  # one grid per radius
+        out.discard("unnormalised_nion")
+    if ts_on:
+        out |= set(TS_FIELDS) | {"tau_21"} | ({"J_21_LW"} if mini else set())
+    if lagrangian:
+        out |= {"n_ion", "halo_sfr"} | ({"halo_xray"} if ts_on else set())
+        out |= ({"whalo_sfr"} if ao.RECOMB_MODEL else set()) | ({"halo_sfr_mini"} if mini else set())
+    return out
+
+
+def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshifts, *, data_path=None,
+                  device=None, lib=None, include_dvdr_in_tau21=True, halo_catalogs=None, progress=None):
+    """Evolve the node boxes as ``run_coeval`` does and assemble a rectilinear lightcone between
+    every pair of nodes on the MI355X (generate_lightcone, drivers/lightcone.py:544-575,596-720).
+    Unlike ``run_coeval`` every node is the next one's "previous" snapshot, with or without
+    evolution (coeval.py:878-884).  With ``include_dvdr_in_tau21`` (the reference's default) the
+    ``brightness_temp`` lightcone is corrected by the line-of-sight velocity gradient at the end
+    (rsds.py:16-103): the ``los_velocity`` (and, with USE_TS_FLUCT, ``tau_21``) lightcones are built
+    for it and returned too.
+
+    ``device="cuda"`` keeps node boxes and lightcones in HBM; None returns numpy arrays built by the
+    same kernels.  Returns a dict: ``lightcones`` {quantity: (HII_DIM, HII_DIM, n_slices)},
+    ``lightcone_distances`` [Mpc], ``lightcone_redshifts``, ``node_redshifts`` (descending),
+    ``global_quantities`` {quantity: per-node box means (fp64)} and ``history`` as run_coeval's."""
+    so, ao, cp = inputs.simulation_options, inputs.astro_options, inputs.cosmo_params
+    nodes64 = sorted((float(z) for z in node_redshifts), reverse=True)
+    if len(nodes64) < 2:
+        raise ValueError("a lightcone needs at least two node redshifts")
+    if len(set(np.float32(nodes64))) != len(nodes64):
+        raise ValueError("node redshifts must be distinct")
+    cosmo = lightconer.cosmo
+    if not (math.isclose(cosmo.h, cp.hlittle, rel_tol=1e-12) and math.isclose(cosmo.Om0, cp.OMm, rel_tol=1e-12)):
+        raise ValueError("the lightconer's cosmology is not the one of the input parameters")
+    lcd = lightconer.lc_distances
+    d_node_min, d_node_max = cosmo.comoving_distance(nodes64[-1]), cosmo.comoving_distance(nodes64[0])
+    if not (d_node_min <= lcd.min() and lcd.max() <= d_node_max):
+        lcz = lightconer.lc_redshifts
+        raise ValueError(f"the lightcone ({lcz.min():.4f} .. {lcz.max():.4f}) is not inside the node "
+                         f"redshifts ({nodes64[-1]} .. {nodes64[0]}); extend the node redshifts")
+    produced = lightcone_fields(inputs)
+    unknown = [q for q in lightconer.quantities if q not in produced]
+    if unknown:
+        raise ValueError(f"{unknown} are not computed for these inputs; possible: {sorted(produced)}")
+    quantities = list(dict.fromkeys(lightconer.quantities))
+    if include_dvdr_in_tau21:
+        if "brightness_temp" not in quantities:
+            raise ValueError("include_dvdr_in_tau21 corrects the brightness_temp lightcone: request it")
+        if ao.USE_TS_FLUCT and "tau_21" not in quantities:
+            quantities.append("tau_21")
+        if "los_velocity" not in quantities:
+            quantities.append("los_velocity")
+    lib = lib or load(require_gpu=True)
+    from . import grid_api as api
+
+    source = {q: ("velocity_z" if q == "los_velocity" else q) for q in quantities}
+    n, d_para = int(so.HII_DIM), int(so.NON_CUBIC_FACTOR * so.HII_DIM)
+    shape, cell = lightconer.get_shape(so), float(so.BOX_LEN) / float(so.HII_DIM)
+    mean_max = tuple(q for q in quantities if lightconer.interp_kinds.get(source[q], "mean") == "mean_max")
+    if device is not None:
+        import torch
+
+        lcs = {q: torch.zeros(shape, dtype=torch.float32, device=device) for q in quantities}
+
+        def mean(a):
+            return float(a.double().mean())
+
+        def full(a):
+            return a if tuple(a.shape) == (n, n, d_para) else a.expand(n, n, d_para).contiguous()
+    else:
+        lcs = {q: np.zeros(shape, np.float32) for q in quantities}
+
+        def mean(a):
+            return float(a.mean(dtype=np.float64))
+
+        def full(a):
+            return a if a.shape == (n, n, d_para) else np.ascontiguousarray(np.broadcast_to(a, (n, n, d_para)))
+
+    nodes32 = [float(np.float32(z)) for z in nodes64]
+    z64 = dict(zip(nodes32, nodes64))
+    glob = {q: np.zeros(len(nodes32)) for q in lightconer.quantities if q != "los_velocity"}
+    history = []
+    prev, prev_z = None, None
+    snaps = _snapshots(inputs, nodes32, set(nodes32), True, data_path=data_path, device=device, lib=lib,
+                       progress=progress, halo_catalogs=halo_catalogs, inspect=None, history=history)
+    for iz, (z, boxes, _ion, _ts, _ics) in enumerate(snaps):
+        for q in glob:
+            glob[q][iz] = mean(boxes[q])
+        cur = {q: full(boxes[source[q]]) for q in quantities}
+        if prev is not None:
+            tab = lightconer.slab_tables(z64[z], z64[prev_z], cell, d_para)
+            if tab is not None:
+                i0, plane, w_lo, w_hi, w_norm = tab
+                api.lightcone_slices(lcs, cur, prev, i0, plane, w_lo, w_hi, w_norm, mean_max=mean_max)
+        prev, prev_z = cur, z
+    lcz = lightconer.lc_redshifts
+    if include_dvdr_in_tau21:  # _finalize_lightcone_at_last_redshift (drivers/lightcone.py:265-277)
+        hubble = cosmo.H0_cgs * cosmo.efunc(lcz)
+        api.lightcone_dvdr(lcs["brightness_temp"], lcs["los_velocity"], hubble, cell,
+                           float(inputs.astro_params.MAX_DVDR),
+                           tau_21=lcs["tau_21"] if ao.USE_TS_FLUCT else None)
+    return {"lightcones": lcs, "lightcone_distances": lcd.copy(), "lightcone_redshifts": lcz,
+            "node_redshifts": tuple(nodes64), "global_quantities": glob, "history": history}

@@ -772,3 +772,79 @@ def ts_first_grids(spec: S.TsFirstSpec, density, stream=None) -> dict:
     check(load().c21cm_ts_first_grids(C.byref(spec), _vptr(density), C.byref(box), _stream(stream)),
           "c21cm_ts_first_grids")
     return out
+
+
+LC_MAX_FIELDS = 16  # C21CM_LC_MAX_FIELDS
+
+
+def _f32_dense(a, what):
+    ok = (a.is_contiguous() and str(a.dtype) == "torch.float32") if _is_torch(a) else (
+        a.dtype == np.float32 and a.flags["C_CONTIGUOUS"])
+    if not ok:
+        raise ValueError(f"{what} must be a C-contiguous float32 array")
+
+
+def lightcone_slices(lightcones: dict, box_lo: dict, box_hi: dict, i0: int, plane, w_lo, w_hi,
+                     w_norm: float, mean_max=("z_reion",), stream=None):
+    """Fill slices [i0, i0 + len(plane)) of every lightcone in ``lightcones`` (name -> array of shape
+    (HII_DIM, HII_DIM, n_slices)) from the node boxes ``box_lo[name]`` / ``box_hi[name]`` (shape
+    (HII_DIM, HII_DIM, HII_D_PARA)) that bracket them (reference: lightconers.py:162-319):
+    (w_lo box_lo + w_hi box_hi) / w_norm at plane ``plane[j]`` of the boxes, fp64, stored as fp32;
+    fields named in ``mean_max`` take the larger value where the two boxes differ in sign.  The
+    tables come from ``drivers.RectilinearLightconer.slab_tables``.  Arrays may be numpy or torch CUDA
+    tensors, mixed freely; a numpy lightcone receives only the slices of this call."""
+    plane = np.ascontiguousarray(plane, np.int32)
+    w_lo = np.ascontiguousarray(w_lo, np.float64)
+    w_hi = np.ascontiguousarray(w_hi, np.float64)
+    run = len(plane)
+    if len(w_lo) != run or len(w_hi) != run:
+        raise ValueError("plane, w_lo and w_hi must have the same length")
+    names = list(lightcones)
+    if not names:
+        raise ValueError("no lightcone to fill")
+    first = lightcones[names[0]]
+    n, _, n_slices = (int(x) for x in first.shape)
+    d_para = int(box_lo[names[0]].shape[-1])
+    for k in names:
+        if tuple(lightcones[k].shape) != (n, n, n_slices):
+            raise ValueError(f"lightcone {k!r} has shape {tuple(lightcones[k].shape)}")
+        _f32_dense(lightcones[k], f"lightcone {k!r}")
+        for b in (box_lo[k], box_hi[k]):
+            _f32_dense(b, f"node box of {k!r}")
+            if tuple(b.shape) != (n, n, d_para):
+                raise ValueError(f"node box of {k!r} has shape {tuple(b.shape)}, not {(n, n, d_para)}")
+    lib = load()
+    lib.c21cm_lightcone_slab_grids.restype = C.c_int
+    for c0 in range(0, len(names), LC_MAX_FIELDS):
+        chunk = names[c0:c0 + LC_MAX_FIELDS]
+        ptrs = [(C.c_void_p * len(chunk))(*[_vptr(d[k]).value for k in chunk])
+                for d in (box_lo, box_hi, lightcones)]
+        spec = S.LightconeSpec(
+            hii_dim=n, hii_d_para=d_para, n_slices=n_slices, i0=int(i0), i1=int(i0) + run,
+            n_fields=len(chunk), mean_max=sum(1 << q for q, k in enumerate(chunk) if k in mean_max),
+            plane=plane.ctypes.data_as(C.POINTER(C.c_int)), w_lo=w_lo.ctypes.data_as(S.c_double_p),
+            w_hi=w_hi.ctypes.data_as(S.c_double_p), w_norm=float(w_norm))
+        check(lib.c21cm_lightcone_slab_grids(C.byref(spec), *ptrs, _stream(stream)),
+              "c21cm_lightcone_slab_grids")
+
+
+def lightcone_dvdr(brightness_temp, los_velocity, hubble, dx: float, max_dvdr: float, tau_21=None,
+                   stream=None):
+    """Correct a brightness-temperature lightcone in place for the line-of-sight velocity gradient
+    (reference: rsds.py:16-103 with periodic = False).  ``hubble``: H(z) [1/s] of every slice;
+    ``tau_21`` given: the USE_TS_FLUCT form, else the Taylor form clipped at +-max_dvdr H."""
+    n, _, n_slices = (int(x) for x in brightness_temp.shape)
+    for a in (brightness_temp, los_velocity, tau_21):
+        if a is not None:
+            _f32_dense(a, "brightness_temp / los_velocity / tau_21")
+        if a is not None and tuple(a.shape) != (n, n, n_slices):
+            raise ValueError("los_velocity / tau_21 must have the shape of brightness_temp")
+    hubble = np.ascontiguousarray(hubble, np.float64)
+    if hubble.shape != (n_slices,):
+        raise ValueError(f"hubble must hold one H(z) per slice ({n_slices})")
+    spec = S.DvdrSpec(hii_dim=n, n_slices=n_slices, dx=float(dx), max_dvdr=float(max_dvdr),
+                      use_ts_fluct=int(tau_21 is not None), hubble=hubble.ctypes.data_as(S.c_double_p))
+    lib = load()
+    lib.c21cm_lightcone_dvdr_grids.restype = C.c_int
+    check(lib.c21cm_lightcone_dvdr_grids(C.byref(spec), _vptr(brightness_temp), _vptr(los_velocity),
+                                         _vptr(tau_21), _stream(stream)), "c21cm_lightcone_dvdr_grids")

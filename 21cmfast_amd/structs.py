@@ -335,6 +335,37 @@ class BrightnessSpec(_Base):
     ]
 
 
+class LightconeSpec(_Base):
+    """``c21cm_lightcone_spec`` (include/c21cm_grid.h): the slab of one node pair."""
+
+    _fields_ = [
+        ("hii_dim", C.c_int),
+        ("hii_d_para", C.c_int),
+        ("n_slices", C.c_int),
+        ("i0", C.c_int),
+        ("i1", C.c_int),
+        ("n_fields", C.c_int),
+        ("mean_max", C.c_uint),
+        ("plane", C.POINTER(C.c_int)),
+        ("w_lo", c_double_p),
+        ("w_hi", c_double_p),
+        ("w_norm", C.c_double),
+    ]
+
+
+class DvdrSpec(_Base):
+    """``c21cm_dvdr_spec`` (include/c21cm_grid.h): the dv/dr correction of a brightness lightcone."""
+
+    _fields_ = [
+        ("hii_dim", C.c_int),
+        ("n_slices", C.c_int),
+        ("dx", C.c_double),
+        ("max_dvdr", C.c_double),
+        ("use_ts_fluct", C.c_int),
+        ("hubble", c_double_p),
+    ]
+
+
 def brightness_spec(n_cells, redshift, cosmo=None, use_ts_fluct=False) -> "BrightnessSpec":
     """The two float constants of BrightnessTemperatureBox.c:43-49 for a CosmoParams struct
     (default cosmology if None)."""

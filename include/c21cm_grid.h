@@ -708,6 +708,47 @@ typedef struct c21cm_ts_first_spec {
 int c21cm_ts_first_grids(const c21cm_ts_first_spec *spec, const float *density, TsBox *out,
                          void *stream);
 
+/* ---- Rectilinear lightcone (lightconers.py:162-319,483-529; drivers/lightcone.py:544-575) ----
+ * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS lightcones from the two node boxes
+ * that bracket them: value = (w_lo[j] box_lo + w_hi[j] box_hi) / w_norm at plane plane[j] of the
+ * boxes (fp64, stored as fp32); bit f of mean_max selects z_reion's rule (where box_lo * box_hi < 0
+ * the larger of the two).  The host derives the per-slice tables (coeval_subselect,
+ * redshift_interpolation); the kernel never does.  Node boxes are float[hii_dim][hii_dim][hii_d_para],
+ * lightcones float[hii_dim][hii_dim][n_slices]; each pointer may be host or device memory (a host
+ * lightcone receives the run of slices as a 2-D copy). */
+#define C21CM_LC_MAX_FIELDS 16
+typedef struct c21cm_lightcone_spec {
+    int hii_dim;        /* columns per side */
+    int hii_d_para;     /* planes of a node box along the line of sight */
+    int n_slices;       /* length of the lightcone */
+    int i0, i1;         /* slices filled by this call, 0 <= i0 < i1 <= n_slices */
+    int n_fields;       /* 1 .. C21CM_LC_MAX_FIELDS */
+    unsigned mean_max;  /* bit f: field f interpolates with mean_max */
+    const int *plane;   /* host, i1 - i0 entries, each in [0, hii_d_para) */
+    const double *w_lo; /* host, i1 - i0: |dc_hi - d| (pixels) */
+    const double *w_hi; /* host, i1 - i0: |dc_lo - d| */
+    double w_norm;      /* |dc_lo - dc_hi| > 0 */
+} c21cm_lightcone_spec;
+
+int c21cm_lightcone_slab_grids(const c21cm_lightcone_spec *spec, const float *const *box_lo,
+                               const float *const *box_hi, float *const *lightcone, void *stream);
+
+/* brightness_temp lightcone corrected in place by the line-of-sight velocity gradient
+ * (rsds.py:16-103, periodic = False): np.gradient(los_velocity, dx, edge_order = 2) along the last
+ * axis, then 1/|1 + clip(dv/dx, +-max_dvdr H)/H| or, with use_ts_fluct, the fp64 tau_21 form
+ * (1 - e^(-tau/g)) / (1 - e^(-tau)), 1 where tau < 1e-10.  n_slices >= 3. */
+typedef struct c21cm_dvdr_spec {
+    int hii_dim;
+    int n_slices;
+    double dx;             /* BOX_LEN / HII_DIM [Mpc] */
+    double max_dvdr;       /* AstroParams.MAX_DVDR */
+    int use_ts_fluct;      /* tau_21 required */
+    const double *hubble;  /* host, n_slices: H(z) of every slice [1/s] */
+} c21cm_dvdr_spec;
+
+int c21cm_lightcone_dvdr_grids(const c21cm_dvdr_spec *spec, float *brightness_temp,
+                               const float *los_velocity, const float *tau_21, void *stream);
+
 /* Library management */
 const char *c21cm_version(void);
 int c21cm_device_synchronize(void);

@@ -1,0 +1,153 @@
+"""Time run_lightcone on the device and the lightcone kernels by themselves (GPU box only).
+
+(1) For each HII_DIM and with / without USE_TS_FLUCT: a device-resident run_lightcone (E-INTEGRAL,
+    BOX_LEN = 1.5 HII_DIM, DIM = 2 HII_DIM, nodes from Z_HEAT_MAX = 35 down to z_end, ZPRIME_STEP_FACTOR
+    apart, the lightcone from the lowest node + 0.2 to the highest - 0.2 at the cell size, five
+    fields) with the slab and dv/dr calls timed (host tables, launch and the synchronisation that
+    ends each call included), their share of the run, the bytes the kernels move by contract
+    (12 B per lightcone cell and field for the slabs, 12 / 16 B per cell for dv/dr) and the
+    lightcone's footprint.
+(2) The slab kernel alone at HII_DIM = 512 (5 fields, runs of 8 .. 256 slices, HII_D_PARA = 512)
+    and the dv/dr kernel over a 512^2 x 1024 lightcone, timed with events over repeated launches.
+
+    python tools/time_lightcone.py [--sizes 256,512] [--z-end 6] [--step 1.02] [--out FILE]
+Run it under rocprofv3 --kernel-trace --stats for the kernel table.
+"""
+import argparse
+import importlib
+import json
+import pathlib
+import sys
+import time
+
+import numpy as np
+import torch
+
+root = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(root))
+D = importlib.import_module("21cmfast_amd.drivers")
+api = importlib.import_module("21cmfast_amd.grid_api")
+pkg = importlib.import_module("21cmfast_amd")
+DATA = root / "tests" / "golden" / "reference" / "_data"
+FIELDS = ("density", "velocity_z", "neutral_fraction", "z_reion", "brightness_temp")
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--sizes", default="256,512")
+ap.add_argument("--ts", default="0,1")
+ap.add_argument("--z-end", type=float, default=6.0)
+ap.add_argument("--step", type=float, default=1.02)
+ap.add_argument("--skip-runs", action="store_true")
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+lib = pkg.load(require_gpu=True)
+
+# ---- wrap the two lightcone calls of run_lightcone with wall-clock timers
+acc = {"slab_s": 0.0, "slab_calls": 0, "slab_bytes": 0, "dvdr_s": 0.0, "dvdr_bytes": 0}
+_slices, _dvdr = api.lightcone_slices, api.lightcone_dvdr
+
+
+def timed_slices(lightcones, box_lo, box_hi, i0, plane, *a, **kw):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _slices(lightcones, box_lo, box_hi, i0, plane, *a, **kw)
+    torch.cuda.synchronize()
+    acc["slab_s"] += time.perf_counter() - t0
+    acc["slab_calls"] += 1
+    first = next(iter(lightcones.values()))
+    acc["slab_bytes"] += 12 * first.shape[0] * first.shape[1] * len(plane) * len(lightcones)
+
+
+def timed_dvdr(bt, vel, hubble, dx, max_dvdr, tau_21=None, **kw):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _dvdr(bt, vel, hubble, dx, max_dvdr, tau_21=tau_21, **kw)
+    torch.cuda.synchronize()
+    acc["dvdr_s"] += time.perf_counter() - t0
+    acc["dvdr_bytes"] += (16 if tau_21 is not None else 12) * bt.numel()
+
+
+api.lightcone_slices, api.lightcone_dvdr = timed_slices, timed_dvdr
+res = {"runs": [], "kernels": {}}
+if not args.skip_runs:
+    for n in (int(s) for s in args.sizes.split(",")):
+        for ts in (bool(int(t)) for t in args.ts.split(",")):
+            for k in list(acc):
+                acc[k] = 0
+            inputs = D.Inputs(random_seed=12345, HII_DIM=n, DIM=2 * n, BOX_LEN=1.5 * n, SOURCE_MODEL=1,
+                              USE_TS_FLUCT=ts, USE_LYA_HEATING=False, HII_FILTER=0, USE_EXP_FILTER=False,
+                              CELL_RECOMB=False, R_BUBBLE_MAX=30.0, ZPRIME_STEP_FACTOR=args.step,
+                              Z_HEAT_MAX=35.0, N_THREADS=16)
+            nodes = D.get_logspaced_redshifts(args.z_end, args.step, 35.0)
+            lc = D.RectilinearLightconer.between_redshifts(nodes[-1] + 0.2, nodes[0] - 0.2, 1.5, quantities=FIELDS)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            out = D.run_lightcone(inputs, lc, nodes, data_path=DATA, device="cuda", lib=lib)
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            n_lc = sum(v.numel() * 4 for v in out["lightcones"].values())
+            row = {"hii_dim": n, "use_ts_fluct": ts, "n_nodes": len(nodes), "n_slices": len(lc.lc_distances),
+                   "lightcone_fields": sorted(out["lightcones"]), "run_s": round(wall, 3),
+                   "slab_s": round(acc["slab_s"], 4), "slab_calls": acc["slab_calls"],
+                   "dvdr_s": round(acc["dvdr_s"], 4),
+                   "share_of_run": round((acc["slab_s"] + acc["dvdr_s"]) / wall, 5),
+                   "slab_contract_GB": round(acc["slab_bytes"] / 1e9, 3),
+                   "slab_GBps_wall": round(acc["slab_bytes"] / max(acc["slab_s"], 1e-12) / 1e9, 1),
+                   "dvdr_contract_GB": round(acc["dvdr_bytes"] / 1e9, 3),
+                   "dvdr_GBps_wall": round(acc["dvdr_bytes"] / max(acc["dvdr_s"], 1e-12) / 1e9, 1),
+                   "lightcone_GB": round(n_lc / 1e9, 3),
+                   "peak_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 3)}
+            print(json.dumps(row), flush=True)
+            res["runs"].append(row)
+            del out
+            torch.cuda.empty_cache()
+api.lightcone_slices, api.lightcone_dvdr = _slices, _dvdr
+
+# ---- the kernels alone at 512
+n, d_para, nf, reps = 512, 512, len(FIELDS), 10
+g = torch.Generator(device="cuda").manual_seed(1)
+lo = {k: torch.rand((n, n, d_para), device="cuda", generator=g) for k in FIELDS}
+hi = {k: torch.rand((n, n, d_para), device="cuda", generator=g) for k in FIELDS}
+ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+for run in (8, 32, 64, 128, 256):
+    lcs = {k: torch.zeros((n, n, 2 * run), device="cuda") for k in FIELDS}
+    plane = ((np.arange(run) + d_para - run // 2) % d_para).astype(np.int32)  # consecutive, wrapping
+    w = np.linspace(0.1, 0.9, run)
+    api.lightcone_slices(lcs, lo, hi, run // 2, plane, w, 1 - w, 1.0)
+    torch.cuda.synchronize()
+    ev0.record()
+    for _ in range(reps):
+        api.lightcone_slices(lcs, lo, hi, run // 2, plane, w, 1 - w, 1.0)
+    ev1.record()
+    torch.cuda.synchronize()
+    ms = ev0.elapsed_time(ev1) / reps
+    byt = 12 * n * n * run * nf
+    row = {"run_slices": run, "fields": nf, "ms_per_call": round(ms, 4), "contract_MB": round(byt / 1e6, 1),
+           "TBps_call": round(byt / ms / 1e9, 3)}
+    print(json.dumps(row), flush=True)
+    res["kernels"][f"slab_run{run}"] = row
+    del lcs
+del lo, hi
+torch.cuda.empty_cache()
+n_s = 1024
+bt = torch.rand((n, n, n_s), device="cuda", generator=g)
+vel = (torch.rand((n, n, n_s), device="cuda", generator=g) - 0.5) * 1e-17
+tau = torch.rand((n, n, n_s), device="cuda", generator=g) * 0.1
+H = 2.2e-18 * np.ones(n_s)
+for name, t in (("dvdr_taylor", None), ("dvdr_tau21", tau)):
+    api.lightcone_dvdr(bt, vel, H, 1.5, 0.2, tau_21=t)
+    torch.cuda.synchronize()
+    ev0.record()
+    for _ in range(reps):
+        api.lightcone_dvdr(bt, vel, H, 1.5, 0.2, tau_21=t)
+    ev1.record()
+    torch.cuda.synchronize()
+    ms = ev0.elapsed_time(ev1) / reps
+    byt = (16 if t is not None else 12) * n * n * n_s
+    row = {"cells": n * n * n_s, "ms_per_call": round(ms, 4), "contract_MB": round(byt / 1e6, 1),
+           "TBps_call": round(byt / ms / 1e9, 3)}
+    print(name, json.dumps(row), flush=True)
+    res["kernels"][name] = row
+if args.out:
+    pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    pathlib.Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
