@@ -9,6 +9,7 @@ resident in HBM when the timed region starts.
 
   python bench.py                      # N = 1
   python bench.py --dump-outputs DIR   # also writes the last timed step's output arrays as DIR/<name>.npy
+  python bench.py --full               # also everything else the line can carry (below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,10 +18,16 @@ max-reduces the per-cell first-crossing mask (uint8) onto the rank that owns rad
 with one RCCL reduce over xGMI, and that rank finishes (partial ionisation, temperatures,
 sum xH).  Total work is fixed as N grows -> "scaling": "strong".
 
-Rank 0 prints ONE JSON line.  Extra objects:
-  roofline      algorithmic bytes / measured time of the dominant unit, vs 8 TB/s HBM3E
+Rank 0 prints ONE JSON line.  A plain run does what the headline needs: set-up, the cold call of
+the size, the placement walk the headline is timed with, the warm-up and the timed steps; its
+`roofline` is the whole R loop's.  --full adds what takes runs of its own:
+  roofline      per-kernel: algorithmic bytes / in-loop time of the dominant pass kernel, vs 8 TB/s
+  default_allocation, abi, abi_ms, h2d_d2h_ms
+                the library's default allocations; the workload through ComputeIonizedBox
   cpu_baseline  the CPU oracle (oracle/liboracle21.so, "port") timed on this host on a
-                bounded sample of the same workload (smaller box, same 40 radii)
+                bounded sample of the same workload (smaller box, same 40 radii), and parity_<n>
+  single_gpu_same_run, speedup, config4, ms_per_step_slab_resident
+                sharded runs: the unsharded pass of the same run, BASELINE config 4
 """
 
 from __future__ import annotations
@@ -66,8 +73,8 @@ def parse_args():
                          "RCCL communicator (c21cm_ionize_sharded, the product path; nccl backend "
                          "only), torch = torch.distributed.reduce between the two C phases")
     ap.add_argument("--config4-dim", type=int, default=1024,
-                    help="sharded runs (N > 1 or --force-shard) also time BASELINE config 4 -- this "
-                         "HII_DIM x 40 radii sharded over the ranks, with its own same-run single-GPU "
+                    help="sharded runs (N > 1 or --force-shard) with --full also time BASELINE config 4 -- "
+                         "this HII_DIM x 40 radii sharded over the ranks, with its own same-run single-GPU "
                          "time -- and report it as the `config4` object; 0 skips it")
     ap.add_argument("--config4-steps", type=int, default=3)
     ap.add_argument("--no-abi", action="store_true",
@@ -81,6 +88,11 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
                          "(float32 / float64, at most 64 MB in all: large grids as a fixed, seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel roofline, the "
+                         "library's default allocations, the ABI timings, the CPU baseline with its parity "
+                         "check, and in sharded runs the same-run single-GPU time and config 4 (the --no-* "
+                         "and --config4-* options select among these)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -488,7 +500,7 @@ def run_icpf(args, torch, pkg):
             out["roofline"]["actual_hbm_frac"] = pmc["hbm_bytes_per_step"] / (ms * 1e-3) / 8e12
         except (OSError, ValueError, KeyError):
             pass
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         oracle = importlib.import_module("oracle.oracle")
         cores = min(os.cpu_count() or 1, 64)
         oracle.set_threads(cores)
@@ -704,30 +716,27 @@ def main():
     first_call_ms = (time.perf_counter() - t_cold) * 1e3
     # Where the work spectra sit in HBM (csrc/host/placement.c).  The library allocates plainly unless asked (a walk
     # costs 0.01-5 s once per process and box size and buys 1-4 ms per 512^3 call: the caller's decision).  This
-    # benchmark measures steady-state throughput, so it asks -- after timing the library's default as well:
-    # `default_allocation` = plain hipMalloc, the headline = with the second spectrum of each two-grid sweep placed
-    # by timed launches (C21CM_WS_PLACE=0 in the environment keeps the plain allocations for the headline too).
+    # benchmark measures steady-state throughput, so it asks -- with --full after timing the library's default as
+    # well: `default_allocation` = plain hipMalloc, the headline = with the second spectrum of each two-grid sweep
+    # placed by timed launches (C21CM_WS_PLACE=0 in the environment keeps the plain allocations for the headline too).
     default_alloc = None
-    if os.environ.get("C21CM_WS_PLACE", "") == "" and not sharded:
-        ms_plain = timed(step, max(3, args.steps // 2), 1)
-        default_alloc = {"ms_per_step": ms_plain, "value": float(n) ** 3 / (ms_plain * 1e-3), "unit": "cells/s",
-                         "what": "the library's default: plain allocations, no placement walk"}
+    if os.environ.get("C21CM_WS_PLACE", "") == "":
+        if args.full and not sharded:
+            ms_plain = timed(step, max(3, args.steps // 2), 1)
+            default_alloc = {"ms_per_step": ms_plain, "value": float(n) ** 3 / (ms_plain * 1e-3), "unit": "cells/s",
+                             "what": "the library's default: plain allocations, no placement walk"}
+        # sharded, every rank opts in for its own device (a walk only happens where the rank has the GPU to itself)
         os.environ.setdefault("C21CM_WS_PLACE_MS", "20000")  # (a throughput run waits for its walk; default 300 ms)
         api.placement_set(1)
         t_walk = time.perf_counter()
         step()
         torch.cuda.synchronize()
-        default_alloc["placement_call_ms"] = (time.perf_counter() - t_walk) * 1e3
-    elif os.environ.get("C21CM_WS_PLACE", "") == "":
-        # sharded: every rank opts in for its own device (a walk only happens where the rank has the GPU to itself)
-        os.environ.setdefault("C21CM_WS_PLACE_MS", "20000")
-        api.placement_set(1)
-        step()
-        torch.cuda.synchronize()
+        if default_alloc:
+            default_alloc["placement_call_ms"] = (time.perf_counter() - t_walk) * 1e3
     placement = api.placement_report()
     ms_per_step = timed(step, args.steps, args.warmup)
     ms_slab_resident = None
-    if sharded and getattr(wl, "slab", False):
+    if args.full and sharded and getattr(wl, "slab", False):
         ms_slab_resident = timed(lambda: wl.step_sharded(shard_c, gather=False), args.steps, 1)
         step()  # (the report / buffers of the headline form)
     if args.dump_outputs and rank == owner:  # the owner holds the finished box in every sharded form
@@ -759,7 +768,7 @@ def main():
 
     # ---- sharded runs: the single-GPU time of the SAME run, and BASELINE config 4
     same_run, config4 = None, None
-    if sharded:
+    if args.full and sharded:
         saved_rep = dict(last_report)
         ms_single = single_gpu_same_run(wl, max(2, min(args.steps, 5)))
         last_report.clear()
@@ -816,7 +825,7 @@ def main():
         # against the 8 TB/s peak as the contract says
         roof = {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS, "achievable_GBs": args.achievable_gbs,
                 "traffic": None}
-        kern = None if (world > 1 or args.no_kernel_roofline or not native) else \
+        kern = None if (not args.full or world > 1 or args.no_kernel_roofline or not native) else \
             kernel_roofline(args, spec, torch)
         if kern:
             # The launch durations INSIDE the step: one more step with HIP events around every pass
@@ -954,8 +963,8 @@ def main():
                 # where the work spectra sit in HBM (csrc/host/placement.c; decided once, in the warm-up)
                 "work_spectra_placement": "plain hipMalloc (the library's default)"
                 if (placement or {}).get("outcome", "").startswith(("off", "other", "another")) or not placement
-                else "second spectrum of each two-grid sweep chosen by timed launches (opt-in: c21cm_placement_set(1)); "
-                     "the library's default is timed in default_allocation",
+                else "second spectrum of each two-grid sweep chosen by timed launches (opt-in: c21cm_placement_set(1))"
+                     + ("; the library's default is timed in default_allocation" if default_alloc else ""),
                 "global_xH": global_xh,
             },
             "roofline": roof,
@@ -970,14 +979,14 @@ def main():
             out["config4"] = config4
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_abi and mode == W.FCOLL_STARS:
+    if args.full and rank == 0 and world == 1 and not args.no_abi and mode == W.FCOLL_STARS:
         try:
             out["abi"] = abi_timing(n, args, torch, pkg, W)
             out["abi_ms"] = out["abi"]["device_arrays_ms"]
             out["h2d_d2h_ms"] = out["abi"]["h2d_d2h_ms"]
         except Exception as exc:  # noqa: BLE001 -- a diagnostic, never the reason a bench line is lost
             out["abi"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         def gpu_run(spec_c):
             """the HIP pass on the oracle sample's spec: inputs as host copies + outputs"""
             nn = spec_c.hii_dim

@@ -717,7 +717,7 @@ def test_bench_sharded_plumbing_on_one_rank():
 
     root = Path(__file__).resolve().parent.parent
     base = [sys.executable, str(root / "bench.py"), "--hii-dim", "128", "--steps", "2", "--warmup",
-            "1", "--no-cpu-baseline", "--no-kernel-roofline", "--no-abi", "--config4-dim", "256"]
+            "1", "--full", "--no-cpu-baseline", "--no-kernel-roofline", "--no-abi", "--config4-dim", "256"]
     outs = []
     for extra in ([], ["--force-shard"]):
         p = subprocess.run(base + extra, capture_output=True, text=True, timeout=600)
@@ -761,7 +761,7 @@ def test_bench_two_ranks_on_one_gpu():
     from pathlib import Path
 
     root = Path(__file__).resolve().parent.parent
-    common = ["--hii-dim", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    common = ["--hii-dim", "128", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--no-kernel-roofline", "--no-abi", "--config4-dim", "256"]
     p = subprocess.run([sys.executable, str(root / "bench.py")] + common, capture_output=True,
                        text=True, timeout=600)
@@ -781,6 +781,42 @@ def test_bench_two_ranks_on_one_gpu():
     assert two["n_gpus"] == 2 and "sharded x2" in two["config"]["parallelism"]
     assert two["config"]["global_xH"] == single["config"]["global_xH"]
     check_sharded_bench_objects(two, world=2, config4_dim=256)
+
+
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest():
+    """A plain bench.py run carries the headline and nothing that takes runs of its own; --full adds the
+    per-kernel roofline, the library-default allocation timing and the ABI timing (the CPU leg is left out here
+    for time) around the same timed steps, with the same result."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    base = [sys.executable, str(root / "bench.py"), "--hii-dim", "128", "--steps", "2", "--warmup", "1"]
+    env = dict(os.environ)
+    env.pop("C21CM_WS_PLACE", None)
+    lines = []
+    for extra in ([], ["--full", "--no-cpu-baseline"]):
+        p = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = p.stdout.strip().splitlines()
+        assert len(out) == 1, p.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    plain, full = lines
+    for ln in lines:
+        assert ln["metric"].startswith("IonizeBox cells/sec (128^3 HII_DIM, ")
+        assert ln["unit"] == "cells/s" and ln["higher_is_better"] is True and ln["dtype"] == "f32"
+        assert ln["steps"] == 2 and ln["warmup"] == 1 and ln["n_gpus"] == 1
+        assert ln["value"] == pytest.approx(128.0 ** 3 / (ln["ms_per_step"] * 1e-3))
+        assert ln["roofline"]["r_loop"]["ms"] > 0
+    assert plain["config"]["global_xH"] == full["config"]["global_xH"]
+    assert not {"default_allocation", "abi", "abi_ms", "h2d_d2h_ms", "cpu_baseline"} & set(plain)
+    assert not [k for k in plain if k.startswith("parity_")]
+    assert plain["roofline"]["kernel"] == "R loop (all kernels)" and "other_kernels" not in plain["roofline"]
+    assert full["default_allocation"]["ms_per_step"] > 0 and "abi" in full
+    assert full["roofline"]["other_kernels"] and "cpu_baseline" not in full
 
 
 @pytest.mark.parametrize("mode,n,nz,device_resident", [

@@ -94,8 +94,8 @@ def test_bench_ranks_through_the_c_exchange(world):
     and the communicator's own rank count -- and global x_HI equals the single-GPU run's."""
     from test_gpu_ionize import check_sharded_bench_objects
 
-    common = ["--hii-dim", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-roofline",
-              "--no-abi", "--config4-dim", "256"]
+    common = ["--hii-dim", "128", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--no-kernel-roofline", "--no-abi", "--config4-dim", "256"]
     env = dict(os.environ, C21CM_WS_PLACE="0")
     p = subprocess.run([sys.executable, str(ROOT / "bench.py")] + common, capture_output=True, text=True,
                        timeout=600, env=env)

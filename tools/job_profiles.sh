@@ -6,6 +6,7 @@ TAG=${1:-r06}
 WHAT=${2:-"bench pmc icpf ts sizes eul shard misc"}
 REPO=$PWD
 OUT=$REPO/gpurun_out/profiles_$TAG
+ERR=$(dirname "$OUT")  # stderr of the runs below, beside the evidence folder
 export TMPDIR=/tmp
 mkdir -p $OUT
 has() { [[ " $WHAT " == *" $1 "* ]]; }
@@ -30,12 +31,12 @@ pmc_clean() { find gpurun_out/pmc_$1_FETCH_SIZE gpurun_out/pmc_$1_WRITE_SIZE -na
 
 if has bench; then
     tools/bin/copy_bench > $OUT/${TAG}_copy_bench.txt 2>&1
-    stats bench python $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline
+    stats bench python $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
     cp gpurun_out/prof_bench.out $OUT/${TAG}_bench_under_rocprof.json
     mv $OUT/${TAG}_bench_kernel_stats.csv $OUT/${TAG}_kernel_stats.csv
 fi
 if has pmc; then
-    pmc 512 python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-roofline --no-abi
+    pmc 512 python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-roofline --no-abi
     python tools/collect_pmc.py $PMC_F $PMC_W $OUT/pmc_$TAG.json $OUT/${TAG}_pmc
     pmc_clean 512
     cp $OUT/pmc_$TAG.json profiles/   # (on the GPU box only: the bench lines below read THIS run's counters)
@@ -46,12 +47,12 @@ if has icpf; then
     python tools/collect_pmc.py $PMC_F $PMC_W $OUT/pmc_icpf_$TAG.json $OUT/${TAG}_icpf_pmc total:3
     pmc_clean icpf
     cp $OUT/pmc_icpf_$TAG.json profiles/
-    timeout 300 python bench.py --mode icpf > $OUT/${TAG}_bench_icpf.json 2> gpurun_out/bench_icpf.err
+    timeout 300 python bench.py --full --mode icpf > $OUT/${TAG}_bench_icpf.json 2> $ERR/bench_icpf.err
 fi
 if has bench; then
-    python bench.py --steps 10 --warmup 3 > $OUT/bench_${TAG}_final.json 2> gpurun_out/bench_final.err
-    timeout 300 python bench.py --mode erfc > $OUT/${TAG}_bench_erfc.json 2> gpurun_out/bench_erfc.err
-    stats erfc python $REPO/bench.py --mode erfc --steps 5 --warmup 2 --no-cpu-baseline --no-abi
+    python bench.py --full --steps 10 --warmup 3 > $OUT/bench_${TAG}_final.json 2> $ERR/bench_final.err
+    timeout 300 python bench.py --full --mode erfc > $OUT/${TAG}_bench_erfc.json 2> $ERR/bench_erfc.err
+    stats erfc python $REPO/bench.py --full --mode erfc --steps 5 --warmup 2 --no-cpu-baseline --no-abi
 fi
 if has ts; then
     # per-kernel times of a spin-temperature evolution at config 5's grid, and the run's own timing line
@@ -61,14 +62,14 @@ if has ts; then
 fi
 if has sizes; then
     # north_star's 256^3 -> 1024^3 sweep on one GPU
-    timeout 300 python bench.py --hii-dim 256 --no-cpu-baseline --no-abi > $OUT/bench_${TAG}_256.json 2> gpurun_out/bench_256.err
-    stats 1024 python $REPO/bench.py --hii-dim 1024 --steps 2 --warmup 1 --no-cpu-baseline --no-abi --no-kernel-roofline
-    pmc 1024 python $REPO/bench.py --hii-dim 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-abi --no-kernel-roofline
+    timeout 300 python bench.py --full --hii-dim 256 --no-cpu-baseline --no-abi > $OUT/bench_${TAG}_256.json 2> $ERR/bench_256.err
+    stats 1024 python $REPO/bench.py --full --hii-dim 1024 --steps 2 --warmup 1 --no-cpu-baseline --no-abi --no-kernel-roofline
+    pmc 1024 python $REPO/bench.py --full --hii-dim 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-abi --no-kernel-roofline
     python tools/collect_pmc.py $PMC_F $PMC_W $OUT/pmc1024_$TAG.json $OUT/${TAG}_1024_pmc 1024
     pmc_clean 1024
     cp $OUT/pmc1024_$TAG.json profiles/
     # (with the CPU leg: the oracle runs the 1024^3 box on the same fields -> parity_1024 in the line; ~3 min on 64 threads)
-    timeout 2000 python bench.py --hii-dim 1024 --steps 3 --warmup 1 --no-abi > $OUT/bench_${TAG}_1024.json 2> gpurun_out/bench_1024.err
+    timeout 2000 python bench.py --full --hii-dim 1024 --steps 3 --warmup 1 --no-abi > $OUT/bench_${TAG}_1024.json 2> $ERR/bench_1024.err
 fi
 if has eul; then
     # Eulerian models through the drop-in entry point: fused table sweep + pair sweeps (default), round 5's loop
@@ -83,12 +84,12 @@ if has eul; then
 fi
 if has shard; then
     # the sharded code path: one rank over real RCCL; 2, 3 and 8 ranks on the one GPU over the test transport
-    timeout 600 python bench.py --force-shard --steps 5 --warmup 2 --no-cpu-baseline --no-abi --config4-dim 1024 --config4-steps 2 \
+    timeout 600 python bench.py --full --force-shard --steps 5 --warmup 2 --no-cpu-baseline --no-abi --config4-dim 1024 --config4-steps 2 \
         > $OUT/bench_${TAG}_force_shard_one_rank.json 2> gpurun_out/bench_force_shard.err
     make -C tests/shim > /dev/null
     for N in 2 3 8; do
       C21CM_RCCL_LIB=$REPO/tests/shim/librccl_shim.so RCCL_SHIM_SLOT_KB=256 C21CM_WS_PLACE=0 timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-        --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --backend gloo --steps 3 --warmup 1 --no-cpu-baseline \
+        --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --full --gpus $N --backend gloo --steps 3 --warmup 1 --no-cpu-baseline \
         --no-abi --no-kernel-roofline --config4-dim 256 2> gpurun_out/bench_shim_$N.err | grep "^{" > $OUT/bench_${TAG}_shim_transport_${N}_ranks_one_gpu.json
     done
     PYTHONPATH=. timeout 600 python tools/time_slab_finish.py 1024 8 2>/dev/null | tail -1 > $OUT/${TAG}_slab_finish_pieces_1024x8.json
