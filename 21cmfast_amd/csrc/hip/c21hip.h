@@ -705,6 +705,18 @@ int c21hip_lightcone_dvdr(float *bt, const float *vel, const float *tau, const d
 int c21hip_d2h_2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width,
                   size_t height, void *stream);
 
+/* ---- rsd_kernels.hip : redshift-space distortions along the line of sight (rsds.py:184-255) ---- */
+#define C21HIP_RSD_MAX_FIELDS 16
+#define C21HIP_RSD_MAX_LDS (159 * 1024) /* dynamic LDS of one workgroup: 160 KiB less the static part */
+/* LDS bytes of one launch for nf fields of n-slice columns; *cpb: columns per workgroup */
+size_t c21hip_rsd_lds_bytes(int n, int nf, int *cpb);
+/* out[q] = the shift of in[q] (columns of n slices, the line of sight fastest) by vel * disp_scale[j]
+ * pixels on a grid of m sub-cells; out[q] may alias in[q].  Device pointers only; *bad |= 1 where a
+ * field or velocity value is not finite (the caller clears and reads it) */
+int c21hip_rsd_shift(const float *const *in, float *const *out, int nf, const float *vel,
+                     const double *disp_scale, size_t n_cols, int n, int m, int periodic, int *bad,
+                     void *stream);
+
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */
 typedef struct c21hip_ts_args { /* the scalars of c21cm_ts_spec, passed by value */

@@ -591,6 +591,23 @@ class RectilinearLightconer:
     def get_shape(self, simulation_options) -> tuple:
         return (int(simulation_options.HII_DIM), int(simulation_options.HII_DIM), len(self.lc_distances))
 
+    def extended(self, n_low: int, n_high: int) -> "RectilinearLightconer":
+        """This lightconer with ``n_low`` / ``n_high`` more slices at the low- / high-redshift end,
+        spaced as its own end slices; ``index_offset`` is kept, as the reference's attrs.evolve keeps
+        it (lightconers.py:395-400), so the node-box planes of the slices follow the new back."""
+        n_low, n_high = int(n_low), int(n_high)
+        if n_low < 0 or n_high < 0:
+            raise ValueError("the buffer slice counts must be >= 0")
+        d = self.lc_distances
+        if (n_low or n_high) and len(d) < 2:
+            raise ValueError("a lightcone of one slice has no spacing to extend it by")
+        if not (n_low or n_high):
+            return self
+        lo = d[0] - (d[1] - d[0]) * np.arange(n_low, 0, -1)
+        hi = d[-1] + (d[-1] - d[-2]) * np.arange(1, n_high + 1)
+        return RectilinearLightconer(np.concatenate([lo, d, hi]), quantities=self.quantities, cosmo=self.cosmo,
+                                     index_offset=self.index_offset, interp_kinds=self.interp_kinds)
+
     def lightcone_dimensions(self, simulation_options) -> tuple:
         """(x, y, line of sight) extent in Mpc (LightCone.lightcone_dimensions)."""
         so = simulation_options
@@ -642,7 +659,8 @@ def lightcone_fields(inputs: Inputs) -> set:
 
 
 def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshifts, *, data_path=None,
-                  device=None, lib=None, include_dvdr_in_tau21=True, halo_catalogs=None, progress=None):
+                  device=None, lib=None, include_dvdr_in_tau21=True, apply_rsds=False, n_rsd_subcells=4,
+                  rsd_buffer_slices=(0, 0), halo_catalogs=None, progress=None):
     """Evolve the node boxes as ``run_coeval`` does and assemble a rectilinear lightcone between
     every pair of nodes on the MI355X (generate_lightcone, drivers/lightcone.py:544-575,596-720).
     Unlike ``run_coeval`` every node is the next one's "previous" snapshot, with or without
@@ -650,6 +668,14 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
     ``brightness_temp`` lightcone is corrected by the line-of-sight velocity gradient at the end
     (rsds.py:16-103): the ``los_velocity`` (and, with USE_TS_FLUCT, ``tau_21``) lightcones are built
     for it and returned too.
+
+    ``apply_rsds`` adds ``<quantity>_with_rsds`` for every lightcone, ``los_velocity`` (and ``tau_21``)
+    included: each moved along the line of sight by its peculiar velocity on ``n_rsd_subcells``
+    sub-cells per slice, without periodicity, after the dv/dr correction (rsds.py:106-255,
+    drivers/lightcone.py:279-303).  The lightcone is then built ``rsd_buffer_slices`` = (low-z,
+    high-z) slices longer, as wide as its end slices, and every lightcone is trimmed back to the
+    requested distances afterwards; mass moved past the extended ends is lost.  The reference sizes
+    that buffer from CLASS's v_b rms, which is not available here: the caller chooses it.
 
     ``device="cuda"`` keeps node boxes and lightcones in HBM; None returns numpy arrays built by the
     same kernels.  Returns a dict: ``lightcones`` {quantity: (HII_DIM, HII_DIM, n_slices)},
@@ -661,6 +687,18 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
         raise ValueError("a lightcone needs at least two node redshifts")
     if len(set(np.float32(nodes64))) != len(nodes64):
         raise ValueError("node redshifts must be distinct")
+    if not isinstance(n_rsd_subcells, (int, np.integer)) or isinstance(n_rsd_subcells, bool):
+        raise ValueError("n_rsd_subcells must be an integer")
+    if apply_rsds and n_rsd_subcells < 1:
+        raise ValueError("n_rsd_subcells must be at least 1")
+    buf = tuple(int(b) for b in rsd_buffer_slices)
+    if len(buf) != 2 or min(buf) < 0:
+        raise ValueError("rsd_buffer_slices must be two counts >= 0 (low-z, high-z)")
+    requested = lightconer
+    if apply_rsds:
+        lightconer = lightconer.extended(*buf)
+    else:
+        buf = (0, 0)
     cosmo = lightconer.cosmo
     if not (math.isclose(cosmo.h, cp.hlittle, rel_tol=1e-12) and math.isclose(cosmo.Om0, cp.OMm, rel_tol=1e-12)):
         raise ValueError("the lightconer's cosmology is not the one of the input parameters")
@@ -680,6 +718,11 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
             raise ValueError("include_dvdr_in_tau21 corrects the brightness_temp lightcone: request it")
         if ao.USE_TS_FLUCT and "tau_21" not in quantities:
             quantities.append("tau_21")
+        if "los_velocity" not in quantities:
+            quantities.append("los_velocity")
+    if apply_rsds:
+        if lightconer.lc_distances.size < 2:
+            raise ValueError("apply_rsds needs a lightcone of at least 2 slices")
         if "los_velocity" not in quantities:
             quantities.append("los_velocity")
     lib = lib or load(require_gpu=True)
@@ -726,10 +769,22 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
                 api.lightcone_slices(lcs, cur, prev, i0, plane, w_lo, w_hi, w_norm, mean_max=mean_max)
         prev, prev_z = cur, z
     lcz = lightconer.lc_redshifts
+    hubble = cosmo.H0_cgs * cosmo.efunc(lcz)
     if include_dvdr_in_tau21:  # _finalize_lightcone_at_last_redshift (drivers/lightcone.py:265-277)
-        hubble = cosmo.H0_cgs * cosmo.efunc(lcz)
         api.lightcone_dvdr(lcs["brightness_temp"], lcs["los_velocity"], hubble, cell,
                            float(inputs.astro_params.MAX_DVDR),
                            tau_21=lcs["tau_21"] if ao.USE_TS_FLUCT else None)
+    if apply_rsds:  # drivers/lightcone.py:279-303: every quantity, shifted by the unshifted velocity
+        shifted = {q + "_with_rsds": (torch.zeros(shape, dtype=torch.float32, device=device) if device is not None
+                                      else np.zeros(shape, np.float32)) for q in quantities}
+        api.rsd_shift({q: lcs[q] for q in quantities}, lcs["los_velocity"], 1.0 / (hubble * cell),
+                      n_sub=int(n_rsd_subcells), periodic=False,
+                      out={q: shifted[q + "_with_rsds"] for q in quantities})
+        lcs.update(shifted)
+    if buf != (0, 0):  # trim (drivers/lightcone.py:303-317)
+        keep = slice(buf[0], buf[0] + len(requested.lc_distances))
+        lcs = {k: (v[..., keep].contiguous() if device is not None else np.ascontiguousarray(v[..., keep]))
+               for k, v in lcs.items()}
+        lcd, lcz = lcd[keep], requested.lc_redshifts
     return {"lightcones": lcs, "lightcone_distances": lcd.copy(), "lightcone_redshifts": lcz,
             "node_redshifts": tuple(nodes64), "global_quantities": glob, "history": history}

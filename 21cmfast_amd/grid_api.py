@@ -848,3 +848,43 @@ def lightcone_dvdr(brightness_temp, los_velocity, hubble, dx: float, max_dvdr: f
     lib.c21cm_lightcone_dvdr_grids.restype = C.c_int
     check(lib.c21cm_lightcone_dvdr_grids(C.byref(spec), _vptr(brightness_temp), _vptr(los_velocity),
                                          _vptr(tau_21), _stream(stream)), "c21cm_lightcone_dvdr_grids")
+
+
+def rsd_shift(fields, los_velocity, disp_scale, n_sub: int = 4, periodic: bool = False, out=None,
+              stream=None):
+    """Move every cell of each array in ``fields`` along the last axis by ``los_velocity *
+    disp_scale[j]`` pixels (reference: rsds.py:184-255 rsds_shift): the displacement is interpolated
+    linearly onto ``n_sub`` sub-cells per slice, each sub-cell is deposited by linear cloud-in-cell and
+    the sub-cells are summed back; ``periodic`` wraps the line of sight, else what leaves it is lost.
+    ``fields``: a dict (name -> array) or a sequence of float32 arrays of the shape of ``los_velocity``
+    (..., n_slices); ``disp_scale``: pixels per unit of velocity, one per slice.  ``out`` (same kind
+    as ``fields``; default: new arrays where each field lives) may be ``fields`` itself.  Arrays may
+    be numpy or torch CUDA tensors, mixed freely; returns ``out``."""
+    named = isinstance(fields, dict)
+    names = list(fields) if named else list(range(len(fields)))
+    if not names:
+        raise ValueError("no field to shift")
+    shape = tuple(int(x) for x in los_velocity.shape)
+    if len(shape) < 1:
+        raise ValueError("los_velocity must have a line-of-sight axis")
+    n_slices = shape[-1]
+    n_cols = int(np.prod(shape[:-1], dtype=np.int64))
+    _f32_dense(los_velocity, "los_velocity")
+    if out is None:
+        made = {k: _new_like(fields[k], 0.0) for k in names}
+        out = made if named else [made[k] for k in names]
+    for k in names:
+        for a, what in ((fields[k], "field"), (out[k], "output")):
+            _f32_dense(a, f"{what} {k!r}")
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{what} {k!r} has shape {tuple(a.shape)}, not that of los_velocity {shape}")
+    disp_scale = np.ascontiguousarray(np.broadcast_to(np.asarray(disp_scale, np.float64), (n_slices,)))
+    spec = S.RsdSpec(n_cols=n_cols, n_slices=n_slices, n_fields=len(names), n_sub=int(n_sub),
+                     periodic=int(bool(periodic)), disp_scale=disp_scale.ctypes.data_as(S.c_double_p))
+    ins = (C.c_void_p * len(names))(*[_vptr(fields[k]).value for k in names])
+    outs = (C.c_void_p * len(names))(*[_vptr(out[k]).value for k in names])
+    lib = load()
+    lib.c21cm_rsd_shift_grids.restype = C.c_int
+    check(lib.c21cm_rsd_shift_grids(C.byref(spec), ins, outs, _vptr(los_velocity), _stream(stream)),
+          "c21cm_rsd_shift_grids")
+    return out

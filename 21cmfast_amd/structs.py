@@ -366,6 +366,19 @@ class DvdrSpec(_Base):
     ]
 
 
+class RsdSpec(_Base):
+    """``c21cm_rsd_spec`` (include/c21cm_grid.h): the redshift-space shift of columns of slices."""
+
+    _fields_ = [
+        ("n_cols", C.c_longlong),
+        ("n_slices", C.c_int),
+        ("n_fields", C.c_int),
+        ("n_sub", C.c_int),
+        ("periodic", C.c_int),
+        ("disp_scale", c_double_p),
+    ]
+
+
 def brightness_spec(n_cells, redshift, cosmo=None, use_ts_fluct=False) -> "BrightnessSpec":
     """The two float constants of BrightnessTemperatureBox.c:43-49 for a CosmoParams struct
     (default cosmology if None)."""

@@ -749,6 +749,25 @@ typedef struct c21cm_dvdr_spec {
 int c21cm_lightcone_dvdr_grids(const c21cm_dvdr_spec *spec, float *brightness_temp,
                                const float *los_velocity, const float *tau_21, void *stream);
 
+/* ---- Redshift-space distortions (rsds.py:106-255 apply_rsds / rsds_shift) ----
+ * Every column of n_slices cells (the line of sight is the fastest axis; columns float[n_cols][n_slices])
+ * of each field is moved by los_velocity * disp_scale[j] pixels: the displacement is interpolated
+ * linearly onto n_sub sub-cells per slice, each sub-cell is deposited by linear cloud-in-cell and the
+ * sub-cells are summed back (periodic: modulo the column; else what leaves [0, n_slices) is lost).
+ * Deterministic: 64-bit fixed-point sums.  Pointers may be host or device memory, mixed; out[q] may
+ * alias fields[q].  A non-finite field or velocity value is C21CM_INFINITY_OR_NAN_ERROR. */
+typedef struct c21cm_rsd_spec {
+    long long n_cols;          /* columns (HII_DIM^2 for a box or a rectilinear lightcone) */
+    int n_slices;              /* >= 2 */
+    int n_fields;              /* >= 1; launches take up to 16 at a time */
+    int n_sub;                 /* n_rsd_subcells >= 1 */
+    int periodic;              /* 1: coeval boxes, 0: lightcones */
+    const double *disp_scale;  /* host, n_slices: pixels per unit of los_velocity, 1 / (H(z_j) cell) */
+} c21cm_rsd_spec;
+
+int c21cm_rsd_shift_grids(const c21cm_rsd_spec *spec, const float *const *fields, float *const *out,
+                          const float *los_velocity, void *stream);
+
 /* Library management */
 const char *c21cm_version(void);
 int c21cm_device_synchronize(void);

@@ -10,7 +10,12 @@
 (2) The slab kernel alone at HII_DIM = 512 (5 fields, runs of 8 .. 256 slices, HII_D_PARA = 512)
     and the dv/dr kernel over a 512^2 x 1024 lightcone, timed with events over repeated launches.
 
-    python tools/time_lightcone.py [--sizes 256,512] [--z-end 6] [--step 1.02] [--out FILE]
+(3) With --rsds: the runs of (1) with apply_rsds=True, the redshift-space shift of every lightcone
+    timed as (1) times the slabs and its share of the run; then the RSD kernel alone over 256^2 and
+    512^2 columns of 2000 and 4000 slices with 1 and 3 fields (4 sub-cells, not periodic), its
+    contract (4 B of velocity + 8 B per field and cell) against the time of one call.
+
+    python tools/time_lightcone.py [--sizes 256,512] [--z-end 6] [--step 1.02] [--rsds] [--out FILE]
 Run it under rocprofv3 --kernel-trace --stats for the kernel table.
 """
 import argparse
@@ -37,13 +42,15 @@ ap.add_argument("--ts", default="0,1")
 ap.add_argument("--z-end", type=float, default=6.0)
 ap.add_argument("--step", type=float, default=1.02)
 ap.add_argument("--skip-runs", action="store_true")
+ap.add_argument("--rsds", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 lib = pkg.load(require_gpu=True)
 
 # ---- wrap the two lightcone calls of run_lightcone with wall-clock timers
-acc = {"slab_s": 0.0, "slab_calls": 0, "slab_bytes": 0, "dvdr_s": 0.0, "dvdr_bytes": 0}
-_slices, _dvdr = api.lightcone_slices, api.lightcone_dvdr
+acc = {"slab_s": 0.0, "slab_calls": 0, "slab_bytes": 0, "dvdr_s": 0.0, "dvdr_bytes": 0, "rsd_s": 0.0,
+       "rsd_bytes": 0}
+_slices, _dvdr, _rsd = api.lightcone_slices, api.lightcone_dvdr, api.rsd_shift
 
 
 def timed_slices(lightcones, box_lo, box_hi, i0, plane, *a, **kw):
@@ -66,7 +73,17 @@ def timed_dvdr(bt, vel, hubble, dx, max_dvdr, tau_21=None, **kw):
     acc["dvdr_bytes"] += (16 if tau_21 is not None else 12) * bt.numel()
 
 
-api.lightcone_slices, api.lightcone_dvdr = timed_slices, timed_dvdr
+def timed_rsd(fields, vel, *a, **kw):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = _rsd(fields, vel, *a, **kw)
+    torch.cuda.synchronize()
+    acc["rsd_s"] += time.perf_counter() - t0
+    acc["rsd_bytes"] += (4 + 8 * len(fields)) * vel.numel()
+    return out
+
+
+api.lightcone_slices, api.lightcone_dvdr, api.rsd_shift = timed_slices, timed_dvdr, timed_rsd
 res = {"runs": [], "kernels": {}}
 if not args.skip_runs:
     for n in (int(s) for s in args.sizes.split(",")):
@@ -82,7 +99,7 @@ if not args.skip_runs:
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             t0 = time.perf_counter()
-            out = D.run_lightcone(inputs, lc, nodes, data_path=DATA, device="cuda", lib=lib)
+            out = D.run_lightcone(inputs, lc, nodes, data_path=DATA, device="cuda", lib=lib, apply_rsds=args.rsds)
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
             n_lc = sum(v.numel() * 4 for v in out["lightcones"].values())
@@ -96,12 +113,48 @@ if not args.skip_runs:
                    "dvdr_contract_GB": round(acc["dvdr_bytes"] / 1e9, 3),
                    "dvdr_GBps_wall": round(acc["dvdr_bytes"] / max(acc["dvdr_s"], 1e-12) / 1e9, 1),
                    "lightcone_GB": round(n_lc / 1e9, 3),
+                   **({"rsd_s": round(acc["rsd_s"], 4), "rsd_share_of_run": round(acc["rsd_s"] / wall, 5),
+                       "rsd_contract_GB": round(acc["rsd_bytes"] / 1e9, 3),
+                       "rsd_GBps_wall": round(acc["rsd_bytes"] / max(acc["rsd_s"], 1e-12) / 1e9, 1)}
+                      if args.rsds else {}),
                    "peak_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 3)}
             print(json.dumps(row), flush=True)
             res["runs"].append(row)
             del out
             torch.cuda.empty_cache()
-api.lightcone_slices, api.lightcone_dvdr = _slices, _dvdr
+api.lightcone_slices, api.lightcone_dvdr, api.rsd_shift = _slices, _dvdr, _rsd
+
+if args.rsds:  # ---- the RSD kernel alone
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    g = torch.Generator(device="cuda").manual_seed(2)
+    for n in (256, 512):
+        for n_s in (2000, 4000):
+            vel = torch.randn((n, n, n_s), device="cuda", generator=g) * 1e-17
+            scale = np.full(n_s, 2.0e17)  # ~2 pixels rms, as a lightcone at 1.5 Mpc cells
+            for nf in (1, 3):
+                fields = [torch.rand((n, n, n_s), device="cuda", generator=g) for _ in range(nf)]
+                outs = [torch.empty_like(f) for f in fields]
+                api.rsd_shift(fields, vel, scale, n_sub=4, out=outs)
+                torch.cuda.synchronize()
+                reps = 3
+                ev0.record()
+                for _ in range(reps):
+                    api.rsd_shift(fields, vel, scale, n_sub=4, out=outs)
+                ev1.record()
+                torch.cuda.synchronize()
+                ms = ev0.elapsed_time(ev1) / reps
+                byt = (4 + 8 * nf) * n * n * n_s
+                row = {"columns": n * n, "slices": n_s, "fields": nf, "ms_per_call": round(ms, 3),
+                       "contract_MB": round(byt / 1e6, 1), "TBps_call": round(byt / ms / 1e9, 3)}
+                print("rsd", json.dumps(row), flush=True)
+                res["kernels"][f"rsd_{n}sq_{n_s}_f{nf}"] = row
+                del fields, outs
+            del vel
+            torch.cuda.empty_cache()
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+    sys.exit(0)
 
 # ---- the kernels alone at 512
 n, d_para, nf, reps = 512, 512, len(FIELDS), 10
