@@ -705,6 +705,27 @@ int c21hip_lightcone_dvdr(float *bt, const float *vel, const float *tau, const d
 int c21hip_d2h_2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width,
                   size_t height, void *stream);
 
+/* ---- angular_lightcone_kernels.hip : angular lightcone sampling and the periodic B-spline prefilter
+ * (lightconers.py AngularLightconer) ---- */
+#define C21HIP_ANG_MAX_BOXES (3 * C21HIP_LC_MAX_FIELDS) /* a vector field takes three boxes */
+typedef struct c21hip_ang_slice { /* one slice of a node pair's run, built by the host */
+    double d;                     /* comoving distance [cells] */
+    double w_lo, w_hi;            /* weights of the low- and high-redshift box */
+} c21hip_ang_slice;
+/* slices j in [0, run) of every pixel: dst[q][pix*dst_stride[q] + dst_off[q] + j] sampled at
+ * d_j nhat[:, pix] + origin from the boxes lo / hi (n0 x n1 x n2, periodic); field q takes one box, or
+ * three (bit q of vec: the projection on nhat); nhat: device, [3][n_pix]; *bad |= 1 where a sum is not
+ * finite.  Device pointers only. */
+int c21hip_angular_sample(const float *const *lo, const float *const *hi, float *const *dst,
+                          const long *dst_stride, const long *dst_off, int n_fields, unsigned mean_max,
+                          unsigned vec, int order, size_t n_pix, int run, int n0, int n1, int n2,
+                          const double *nhat, const double *origin, const c21hip_ang_slice *tab,
+                          double w_norm, int *bad, void *stream);
+/* B-spline coefficients (order 3 or 5) of a periodic n0 x n1 x n2 box, src -> dst (may alias);
+ * *bad |= 1 where a src value is not finite.  Device pointers only. */
+int c21hip_spline_prefilter(const float *src, float *dst, int n0, int n1, int n2, int order, int *bad,
+                            void *stream);
+
 /* ---- rsd_kernels.hip : redshift-space distortions along the line of sight (rsds.py:184-255) ---- */
 #define C21HIP_RSD_MAX_FIELDS 16
 #define C21HIP_RSD_MAX_LDS (159 * 1024) /* dynamic LDS of one workgroup: 160 KiB less the static part */

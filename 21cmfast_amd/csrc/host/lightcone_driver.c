@@ -153,11 +153,28 @@ done:
     return status;
 }
 
+static int dvdr_columns(const c21cm_dvdr_spec *s, size_t n_cols, float *brightness_temp,
+                        const float *los_velocity, const float *tau_21, void *stream);
+
 int c21cm_lightcone_dvdr_grids(const c21cm_dvdr_spec *s, float *brightness_temp, const float *los_velocity,
                                const float *tau_21, void *stream) {
-    int status = 0;
     if (!s) return lc_fail("spec is required");
     if (s->hii_dim < 1) return lc_fail("hii_dim must be positive");
+    return dvdr_columns(s, (size_t)s->hii_dim * (size_t)s->hii_dim, brightness_temp, los_velocity, tau_21,
+                        stream);
+}
+
+/* the same correction on n_cols columns (an angular lightcone: one per pixel) */
+int c21cm_lightcone_dvdr_columns_grids(const c21cm_dvdr_spec *s, long long n_cols, float *brightness_temp,
+                                       const float *los_velocity, const float *tau_21, void *stream) {
+    if (!s) return lc_fail("spec is required");
+    if (n_cols < 0) return lc_fail("n_cols must be >= 0");
+    return dvdr_columns(s, (size_t)n_cols, brightness_temp, los_velocity, tau_21, stream);
+}
+
+static int dvdr_columns(const c21cm_dvdr_spec *s, size_t n_cols, float *brightness_temp,
+                        const float *los_velocity, const float *tau_21, void *stream) {
+    int status = 0;
     if (s->n_slices < 3)
         return lc_fail("dv/dr needs at least 3 slices (second-order one-sided differences at both ends)");
     if (!brightness_temp || !los_velocity) return lc_fail("brightness_temp and los_velocity are required");
@@ -168,8 +185,8 @@ int c21cm_lightcone_dvdr_grids(const c21cm_dvdr_spec *s, float *brightness_temp,
     for (int k = 0; k < s->n_slices; ++k)
         if (!(s->hubble[k] > 0.0) || !isfinite(s->hubble[k])) return lc_fail("H(z) must be positive and finite");
 
-    const size_t n_cols = (size_t)s->hii_dim * (size_t)s->hii_dim;
     const size_t elems = n_cols * (size_t)s->n_slices, bytes = elems * sizeof(float);
+    if (elems == 0) return 0;
     double *d_h = (double *)c21hip_ws(WS_LC_HUBBLE, sizeof(double) * (size_t)s->n_slices);
     if (!d_h) return C21CM_MEMORY_ALLOC_ERROR;
     TRY(c21hip_h2d(d_h, s->hubble, sizeof(double) * (size_t)s->n_slices, stream));

@@ -5,7 +5,7 @@ spin-temperature path for the Lagrangian source models
 (reference: src/py21cmfast/drivers/single_field.py:382-470 ``interp_halo_boxes`` and :473-636
 ``compute_xray_source_field``), and the rectilinear lightcone of ``run_lightcone``
 (reference: src/py21cmfast/lightconers.py, drivers/lightcone.py) with its slabs and dv/dr correction on
-the device.  A py21cmfast installation keeps using its own drivers on top of
+the device, and its angular lightcone (AngularLightconer), interpolated on the device.  A py21cmfast installation keeps using its own drivers on top of
 the library; this module is for callers without it (tests, tools, stand-alone runs).
 
 The reference does this bookkeeping in Python with astropy: the shells of the X-ray / Lyman-alpha
@@ -350,7 +350,8 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
     ``device``: a torch device string ("cuda") keeps every array in HBM (zero-copy entry points);
     None uses numpy arrays that the library stages.  ``data_path``: directory of the reference's
     data tables (py21cmfast's ``_data``).  Returns ``{redshift: {field: array}}`` for the requested
-    redshifts (fields in ``keep``; plus the scalars ``mean_f_coll`` and ``Q_HI``), keyed by the
+    redshifts (fields in ``keep``, and ``velocity_x`` / ``velocity_y`` with KEEP_3D_VELOCITIES; plus the
+    scalars ``mean_f_coll`` and ``Q_HI``), keyed by the
     requested redshift as float32 -- a requested redshift between two nodes is computed AT that
     redshift from the last node above it, like upstream -- and, under the key ``"history"``, the
     global signal (z, mean dT_b, mean x_HI, mean T_s) of every snapshot computed.
@@ -365,6 +366,8 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
     snaps = _snapshots(inputs, all_redshifts, is_node, inputs.evolution_required, data_path=data_path,
                        device=device, lib=lib, progress=progress, halo_catalogs=halo_catalogs,
                        inspect=inspect, history=history)
+    if inputs.matter_options.KEEP_3D_VELOCITIES:  # the two extra components come back with velocity_z
+        keep = tuple(keep) + tuple(k for k in ("velocity_x", "velocity_y") if k not in keep)
     ics = None
     for z, boxes, ion, ts, ics in snaps:
         if z in wanted:
@@ -456,8 +459,9 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
     prev_z, prev_xHI = 0.0, None
     prev_means = (0.0, 0.0)
     z_halos, hboxes = [], []
+    pf_fields = ("density", "velocity_z") + (("velocity_x", "velocity_y") if mo.KEEP_3D_VELOCITIES else ())
     for z in all_redshifts:
-        pf_arr = {"density": new(), "velocity_z": new()}
+        pf_arr = {k: new() for k in pf_fields}
         pf = S.PerturbedFieldStruct(**{k: fp(v) for k, v in pf_arr.items()})
         check(lib.ComputePerturbedField(z, C.byref(icss), C.byref(pf)), "ComputePerturbedField")
         hb_arr, hb = {}, S.HaloBoxStruct()
@@ -503,7 +507,7 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
         if prev_pf_arr is None and mini:
             # the first snapshot's "previous" field is a dummy that ComputeIonizedBox overwrites
             # with -1.5 (IonisationBox.c:394-398): it must not alias the current density
-            prev_pf_arr = {"density": new(), "velocity_z": new()}
+            prev_pf_arr = {k: new() for k in pf_fields}
         if mini:  # the trapezoidal means live in the structs (set_mean_fcoll, :476-501)
             prev_ion.mean_f_coll, prev_ion.mean_f_coll_MINI = prev_means
         prev_pf = S.PerturbedFieldStruct(**{k: fp(v) for k, v in (prev_pf_arr or pf_arr).items()})
@@ -533,19 +537,17 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
 
 
 # =============================================================================================
-# Rectilinear lightcones (reference: src/py21cmfast/lightconers.py:36-319,483-529 and
-# drivers/lightcone.py:172-181,249-277,544-575).  The slabs and the dv/dr correction are HIP
-# kernels (csrc/hip/lightcone_kernels.hip); the geometry below is the host's.
+# Lightcones (reference: src/py21cmfast/lightconers.py:36-319,483-529,541-701 and
+# drivers/lightcone.py:172-181,249-277,544-575).  The slabs, the angular sampling, the spline prefilter
+# and the dv/dr correction are HIP kernels (csrc/hip/lightcone_kernels.hip,
+# angular_lightcone_kernels.hip); the geometry below is the host's.
 # =============================================================================================
-class RectilinearLightconer:
-    """Slices at comoving distances ``lc_distances`` [Mpc] along the last axis of the node boxes
-    (RectilinearLightconer, lightconers.py:483-529).  ``index_offset`` (default: the number of
-    slices) places the back of the lightcone on the back of the node box; ``interp_kinds`` maps a
-    quantity to "mean" (default) or "mean_max" (``z_reion``).  ``cosmo``: a FlatCosmology, by
-    default that of the default CosmoParams."""
+class _Lightconer:
+    """What both lightconers share (Lightconer, lightconers.py:36-160): the slice distances
+    ``lc_distances`` [Mpc], their redshifts, the quantities and their interpolation kinds, and which
+    slices lie between two nodes with their redshift-interpolation weights."""
 
-    def __init__(self, lc_distances, quantities=("brightness_temp",), cosmo=None, index_offset=None,
-                 interp_kinds=None):
+    def _init_common(self, lc_distances, quantities, cosmo, interp_kinds):
         self.lc_distances = np.asarray(lc_distances, float)
         if self.lc_distances.ndim != 1 or len(self.lc_distances) == 0:
             raise ValueError("lc_distances must be a non-empty 1-D array")
@@ -556,7 +558,6 @@ class RectilinearLightconer:
             cosmo = FlatCosmology(cp.hlittle, cp.OMm)
         self.cosmo = cosmo
         self.quantities = tuple(quantities)
-        self.index_offset = len(self.lc_distances) if index_offset is None else int(index_offset)
         self.interp_kinds = {"z_reion": "mean_max"} if interp_kinds is None else dict(interp_kinds)
         for k, v in self.interp_kinds.items():
             if v not in ("mean", "mean_max"):
@@ -574,7 +575,7 @@ class RectilinearLightconer:
         d0 = cosmo.comoving_distance(float(min_redshift))
         d1 = cosmo.comoving_distance(float(max_redshift))
         res = float(resolution)
-        return cls(np.arange(d0, d1 + res, res), quantities=quantities, cosmo=cosmo, **kw)
+        return cls(lc_distances=np.arange(d0, d1 + res, res), quantities=quantities, cosmo=cosmo, **kw)
 
     @property
     def lc_redshifts(self) -> np.ndarray:
@@ -588,13 +589,9 @@ class RectilinearLightconer:
             self._lc_redshifts = np.interp(d, self.cosmo.comoving_distance(zgrid), zgrid)
         return self._lc_redshifts
 
-    def get_shape(self, simulation_options) -> tuple:
-        return (int(simulation_options.HII_DIM), int(simulation_options.HII_DIM), len(self.lc_distances))
-
-    def extended(self, n_low: int, n_high: int) -> "RectilinearLightconer":
-        """This lightconer with ``n_low`` / ``n_high`` more slices at the low- / high-redshift end,
-        spaced as its own end slices; ``index_offset`` is kept, as the reference's attrs.evolve keeps
-        it (lightconers.py:395-400), so the node-box planes of the slices follow the new back."""
+    def _extended_distances(self, n_low: int, n_high: int):
+        """lc_distances with ``n_low`` / ``n_high`` more slices at the low- / high-redshift end, spaced
+        as its own end slices; None when both are 0."""
         n_low, n_high = int(n_low), int(n_high)
         if n_low < 0 or n_high < 0:
             raise ValueError("the buffer slice counts must be >= 0")
@@ -602,10 +599,53 @@ class RectilinearLightconer:
         if (n_low or n_high) and len(d) < 2:
             raise ValueError("a lightcone of one slice has no spacing to extend it by")
         if not (n_low or n_high):
-            return self
+            return None
         lo = d[0] - (d[1] - d[0]) * np.arange(n_low, 0, -1)
         hi = d[-1] + (d[-1] - d[-2]) * np.arange(1, n_high + 1)
-        return RectilinearLightconer(np.concatenate([lo, d, hi]), quantities=self.quantities, cosmo=self.cosmo,
+        return np.concatenate([lo, d, hi])
+
+    def pair_slices(self, z_lo, z_hi, cell_size):
+        """The slices between the nodes at ``z_lo`` < ``z_hi`` and their redshift-interpolation weights
+        (make_lightcone_slices :189-207, redshift_interpolation :307-309): returns (idx, lcd, w_lo, w_hi,
+        w_norm) -- the slice indices [i0, i1), their distances, |dc_hi - d|, |dc_lo - d| and |dc_lo - dc_hi|
+        in pixels of ``cell_size`` [Mpc] -- or None when no slice lies between the two."""
+        pix = self.lc_distances / float(cell_size)
+        dc_lo = self.cosmo.comoving_distance(float(z_lo)) / float(cell_size)
+        dc_hi = self.cosmo.comoving_distance(float(z_hi)) / float(cell_size)
+        dcmin, dcmax = min(dc_lo, dc_hi), max(dc_lo, dc_hi)
+        # tolerance at the low-redshift end: the last slice may sit exactly on the lowest node
+        idx = np.nonzero((pix >= dcmin * (1 - 1e-6)) & (pix < dcmax))[0]
+        if len(idx) == 0:
+            return None
+        if np.any(np.diff(idx) != 1):
+            raise ValueError("lc_distances must be increasing")
+        lcd = pix[idx]
+        return idx, lcd, np.abs(dc_hi - lcd), np.abs(dc_lo - lcd), abs(dc_lo - dc_hi)
+
+
+class RectilinearLightconer(_Lightconer):
+    """Slices at comoving distances ``lc_distances`` [Mpc] along the last axis of the node boxes
+    (RectilinearLightconer, lightconers.py:483-529).  ``index_offset`` (default: the number of
+    slices) places the back of the lightcone on the back of the node box; ``interp_kinds`` maps a
+    quantity to "mean" (default) or "mean_max" (``z_reion``).  ``cosmo``: a FlatCosmology, by
+    default that of the default CosmoParams."""
+
+    def __init__(self, lc_distances, quantities=("brightness_temp",), cosmo=None, index_offset=None,
+                 interp_kinds=None):
+        self._init_common(lc_distances, quantities, cosmo, interp_kinds)
+        self.index_offset = len(self.lc_distances) if index_offset is None else int(index_offset)
+
+    def get_shape(self, simulation_options) -> tuple:
+        return (int(simulation_options.HII_DIM), int(simulation_options.HII_DIM), len(self.lc_distances))
+
+    def extended(self, n_low: int, n_high: int) -> "RectilinearLightconer":
+        """This lightconer with ``n_low`` / ``n_high`` more slices at the low- / high-redshift end,
+        spaced as its own end slices; ``index_offset`` is kept, as the reference's attrs.evolve keeps
+        it (lightconers.py:395-400), so the node-box planes of the slices follow the new back."""
+        d = self._extended_distances(n_low, n_high)
+        if d is None:
+            return self
+        return RectilinearLightconer(d, quantities=self.quantities, cosmo=self.cosmo,
                                      index_offset=self.index_offset, interp_kinds=self.interp_kinds)
 
     def lightcone_dimensions(self, simulation_options) -> tuple:
@@ -620,30 +660,164 @@ class RectilinearLightconer:
         returns (i0, plane, w_lo, w_hi, w_norm), or None when no slice lies between the two.
         Distances are in pixels of ``cell_size`` [Mpc]; ``plane`` indexes the node boxes' last axis
         (``d_para`` planes, wrapped)."""
-        pix = self.lc_distances / float(cell_size)
-        dc_lo = self.cosmo.comoving_distance(float(z_lo)) / float(cell_size)
-        dc_hi = self.cosmo.comoving_distance(float(z_hi)) / float(cell_size)
-        dcmin, dcmax = min(dc_lo, dc_hi), max(dc_lo, dc_hi)
-        # tolerance at the low-redshift end: the last slice may sit exactly on the lowest node
-        idx = np.nonzero((pix >= dcmin * (1 - 1e-6)) & (pix < dcmax))[0]
-        if len(idx) == 0:
+        pair = self.pair_slices(z_lo, z_hi, cell_size)
+        if pair is None:
             return None
-        if np.any(np.diff(idx) != 1):
-            raise ValueError("lc_distances must be increasing")
-        lcd = pix[idx]
+        idx, lcd, w_lo, w_hi, w_norm = pair
+        pix = self.lc_distances / float(cell_size)
         lcidx = np.array([int(v) for v in (pix.max() - lcd + 1)], np.int64)
         plane = np.mod(-lcidx + self.index_offset, int(d_para)).astype(np.int32)
-        w_lo = np.abs(dc_hi - lcd)
-        w_hi = np.abs(dc_lo - lcd)
-        return int(idx[0]), plane, w_lo, w_hi, abs(dc_lo - dc_hi)
+        return int(idx[0]), plane, w_lo, w_hi, w_norm
+
+
+# the rotation of AngularLightconer.like_rectilinear: scipy's Rotation.from_euler("Y", -pi/2), which maps
+# the direction (b, l) = (0, 0) to +z
+LIKE_RECTILINEAR_ROTATION = np.array([[0.0, 0.0, -1.0], [0.0, 1.0, 0.0], [1.0, 0.0, 0.0]])
+
+
+def _rotation_matrix(rotation):
+    """A 3 x 3 rotation matrix from None, a matrix or anything with ``as_matrix()`` (scipy's Rotation)."""
+    if rotation is None:
+        return None
+    R = np.array(rotation.as_matrix() if hasattr(rotation, "as_matrix") else rotation, dtype=np.float64)
+    if R.shape != (3, 3) or not np.all(np.isfinite(R)) or not np.allclose(R @ R.T, np.eye(3), atol=1e-9) \
+            or not np.isclose(np.linalg.det(R), 1.0, atol=1e-9):
+        raise ValueError("rotation must be a 3x3 rotation matrix (or have as_matrix())")
+    return R
+
+
+class AngularLightconer(_Lightconer):
+    """Slices at comoving distances ``lc_distances`` [Mpc] sampled in the directions (``latitude``,
+    ``longitude``) [rad] (AngularLightconer, lightconers.py:541-701).  The direction
+    u = (cos b cos l, cos b sin l, sin b) is rotated by ``rotation`` (a 3 x 3 matrix, anything with
+    ``as_matrix()`` such as scipy's Rotation, or None); pixel p of the slice at d sits at
+    x = d n_p / cell + ``origin`` [cells] of the periodic node boxes and takes their B-spline
+    interpolation of ``interpolation_order`` (0, 1, 3 or 5) there.  ``los_velocity`` is the
+    projection of the 3-D velocity on n_p (KEEP_3D_VELOCITIES).  The lightcones have shape
+    (n_pix, n_slices)."""
+
+    def __init__(self, latitude, longitude, lc_distances, quantities=("brightness_temp",), cosmo=None,
+                 interpolation_order=1, origin=(0.0, 0.0, 0.0), rotation=None, interp_kinds=None):
+        self._init_common(lc_distances, quantities, cosmo, interp_kinds)
+        self.latitude = np.asarray(latitude, float)
+        self.longitude = np.asarray(longitude, float)
+        # the reference's validators (lightconers.py:566-573), in its order
+        if self.longitude.ndim != 1:
+            raise ValueError("longitude must be 1-dimensional")
+        if np.any(self.longitude < 0) or np.any(self.longitude > 2 * np.pi):
+            raise ValueError("longitude must be in the range [0, 2pi]")
+        if self.longitude.shape != self.latitude.shape:
+            raise ValueError("longitude and latitude must have the same shape")
+        if not np.all(np.isfinite(self.latitude)):
+            raise ValueError("latitude must be finite")
+        order = int(interpolation_order)
+        if order not in (0, 1, 3, 5):
+            raise ValueError(f"'interpolation_order' must be in [0, 1, 3, 5] (got {interpolation_order!r})")
+        self.interpolation_order = order
+        self.origin = np.asarray(origin, float)
+        if self.origin.shape != (3,) or not np.all(np.isfinite(self.origin)):
+            raise ValueError("origin must be three finite coordinates [pixels]")
+        self.rotation = _rotation_matrix(rotation)
+        self._nhat = None
+
+    @classmethod
+    def like_rectilinear(cls, simulation_options, match_at_z, max_redshift, cosmo=None, **kw):
+        """An angular lightconer with the pixel size of a rectilinear one (lightconers.py:579-635): an
+        HII_DIM x HII_DIM grid of angles spanning BOX_LEN at ``match_at_z`` (latitude decreasing along the
+        rows), the rotation that maps (0, 0) to +z and the origin that puts the slice at ``match_at_z`` on
+        plane 0 of the node boxes; slices one cell apart from ``match_at_z`` to ``max_redshift``."""
+        so = simulation_options
+        if cosmo is None:
+            cp = S.default_cosmo_params()
+            cosmo = FlatCosmology(cp.hlittle, cp.OMm)
+        cell = float(so.BOX_LEN) / float(so.HII_DIM)
+        d_match = cosmo.comoving_distance(float(match_at_z))
+        box_size_radians = float(so.BOX_LEN) / d_match
+        lon = np.linspace(0, box_size_radians, int(so.HII_DIM))
+        lat = np.linspace(0, box_size_radians, int(so.HII_DIM))[::-1]  # x increasing from 0
+        LON, LAT = np.meshgrid(lon, lat)
+        origin = np.array([0.0, 0.0, -d_match / cell])
+        return cls.between_redshifts(min_redshift=match_at_z, max_redshift=max_redshift, resolution=cell,
+                                     cosmo=cosmo, latitude=LAT.flatten(), longitude=LON.flatten(), origin=origin,
+                                     rotation=LIKE_RECTILINEAR_ROTATION, **kw)
+
+    @property
+    def n_pix(self) -> int:
+        return len(self.longitude)
+
+    @property
+    def nhat(self) -> np.ndarray:
+        """The rotated unit directions, float64 (3, n_pix)."""
+        if self._nhat is None:
+            b, lon = self.latitude, self.longitude
+            u = np.stack([np.cos(b) * np.cos(lon), np.cos(b) * np.sin(lon), np.sin(b)])
+            self._nhat = np.ascontiguousarray(u if self.rotation is None else self.rotation @ u)
+        return self._nhat
+
+    def get_shape(self, simulation_options=None) -> tuple:
+        return (self.n_pix, len(self.lc_distances))
+
+    def extended(self, n_low: int, n_high: int) -> "AngularLightconer":
+        """This lightconer with ``n_low`` / ``n_high`` more slices at the low- / high-redshift end, spaced
+        as its own end slices (the RSD buffer); the directions, origin and rotation are kept."""
+        d = self._extended_distances(n_low, n_high)
+        if d is None:
+            return self
+        return AngularLightconer(self.latitude, self.longitude, d, quantities=self.quantities, cosmo=self.cosmo,
+                                 interpolation_order=self.interpolation_order, origin=self.origin,
+                                 rotation=self.rotation, interp_kinds=self.interp_kinds)
+
+    def angular_tables(self, z_lo, z_hi, cell_size):
+        """The slices between the nodes at ``z_lo`` < ``z_hi``: (i0, distance, w_lo, w_hi, w_norm) in
+        pixels of ``cell_size`` [Mpc], or None (the selection and weights of the rectilinear lightconer)."""
+        pair = self.pair_slices(z_lo, z_hi, cell_size)
+        if pair is None:
+            return None
+        idx, lcd, w_lo, w_hi, w_norm = pair
+        return int(idx[0]), lcd, w_lo, w_hi, w_norm
+
+    def validate_options(self, inputs, include_dvdr_in_tau21: bool, apply_rsds: bool):
+        """The angular part of validate_options (lightconers.py:678-701): the dv/dr correction and the
+        RSDs need the projected velocity, so the 3-D velocities; so does a ``los_velocity`` lightcone."""
+        if (include_dvdr_in_tau21 or apply_rsds or "los_velocity" in self.quantities) \
+                and not inputs.matter_options.KEEP_3D_VELOCITIES:
+            raise ValueError("To account for RSDs or velocity corrections in an angular lightcone, you need to set "
+                             "matter_options.KEEP_3D_VELOCITIES=True")
+        if self.interpolation_order >= 3:
+            mm = sorted(q for q in self.quantities if self.interp_kinds.get(q, "mean") == "mean_max")
+            if mm:
+                raise ValueError(f"{mm} interpolate with 'mean_max', which needs interpolation_order 0 or 1: "
+                                 "spline coefficients of a mean_max interpolation are not built")
+
+    def __eq__(self, other):
+        if not isinstance(other, AngularLightconer):
+            return NotImplemented
+
+        def close(a, b):
+            return a.shape == b.shape and np.allclose(a, b)
+
+        if (self.rotation is None) != (other.rotation is None):
+            return False
+        return (close(self.latitude, other.latitude) and close(self.longitude, other.longitude)
+                and close(self.origin, other.origin) and close(self.lc_distances, other.lc_distances)
+                and (self.rotation is None or np.allclose(self.rotation, other.rotation))
+                and self.interpolation_order == other.interpolation_order
+                and self.quantities == other.quantities and self.interp_kinds == other.interp_kinds
+                and (self.cosmo.h, self.cosmo.Om0) == (other.cosmo.h, other.cosmo.Om0))
+
+    __hash__ = None
 
 
 def lightcone_fields(inputs: Inputs) -> set:
     """Names of the (HII_DIM, HII_DIM, HII_D_PARA) fields a run with these inputs produces per node,
-    plus ``los_velocity`` (the line-of-sight velocity, i.e. ``velocity_z``)."""
+    plus ``los_velocity`` (the line-of-sight velocity: ``velocity_z`` of a rectilinear lightcone, the
+    projection of the 3-D velocity of an angular one).  KEEP_3D_VELOCITIES adds ``velocity_x`` /
+    ``velocity_y``."""
     mo, ao = inputs.matter_options, inputs.astro_options
     lagrangian, ts_on, mini = mo.SOURCE_MODEL >= 2, bool(ao.USE_TS_FLUCT), bool(ao.USE_MINI_HALOS)
     out = {"density", "velocity_z", "los_velocity", "brightness_temp"} | set(ION_FIELDS)
+    if mo.KEEP_3D_VELOCITIES:
+        out |= {"velocity_x", "velocity_y"}
     if mo.MINIMIZE_MEMORY:
         out -= {"kinetic_temperature", "mean_free_path"}
     if ao.RECOMB_MODEL == 0:
@@ -658,7 +832,7 @@ def lightcone_fields(inputs: Inputs) -> set:
     return out
 
 
-def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshifts, *, data_path=None,
+def run_lightcone(inputs: Inputs, lightconer, node_redshifts, *, data_path=None,
                   device=None, lib=None, include_dvdr_in_tau21=True, apply_rsds=False, n_rsd_subcells=4,
                   rsd_buffer_slices=(0, 0), halo_catalogs=None, progress=None):
     """Evolve the node boxes as ``run_coeval`` does and assemble a rectilinear lightcone between
@@ -677,11 +851,21 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
     requested distances afterwards; mass moved past the extended ends is lost.  The reference sizes
     that buffer from CLASS's v_b rms, which is not available here: the caller chooses it.
 
+    ``lightconer``: a RectilinearLightconer or an AngularLightconer.  An angular lightcone samples the
+    node boxes at its directions with the interpolation order of its lightconer (orders 3 and 5 on the
+    B-spline coefficients of every node box, prefiltered once per node); its ``los_velocity`` is the
+    3-D velocity projected on the direction, so dv/dr and RSDs need KEEP_3D_VELOCITIES (the reference's
+    validate_options, lightconers.py:678-701).  dv/dr and RSDs then act on its (n_pix, n_slices) columns.
+
     ``device="cuda"`` keeps node boxes and lightcones in HBM; None returns numpy arrays built by the
-    same kernels.  Returns a dict: ``lightcones`` {quantity: (HII_DIM, HII_DIM, n_slices)},
-    ``lightcone_distances`` [Mpc], ``lightcone_redshifts``, ``node_redshifts`` (descending),
-    ``global_quantities`` {quantity: per-node box means (fp64)} and ``history`` as run_coeval's."""
+    same kernels.  Returns a dict: ``lightcones`` {quantity: (HII_DIM, HII_DIM, n_slices) or, angular,
+    (n_pix, n_slices)}, ``lightcone_distances`` [Mpc], ``lightcone_redshifts``, ``node_redshifts``
+    (descending), ``global_quantities`` {quantity: per-node box means (fp64)} and ``history`` as
+    run_coeval's; an angular run adds ``latitude`` and ``longitude``."""
     so, ao, cp = inputs.simulation_options, inputs.astro_options, inputs.cosmo_params
+    angular = isinstance(lightconer, AngularLightconer)
+    if not (angular or isinstance(lightconer, RectilinearLightconer)):
+        raise TypeError("lightconer must be a RectilinearLightconer or an AngularLightconer")
     nodes64 = sorted((float(z) for z in node_redshifts), reverse=True)
     if len(nodes64) < 2:
         raise ValueError("a lightcone needs at least two node redshifts")
@@ -712,6 +896,8 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
     unknown = [q for q in lightconer.quantities if q not in produced]
     if unknown:
         raise ValueError(f"{unknown} are not computed for these inputs; possible: {sorted(produced)}")
+    if angular:
+        lightconer.validate_options(inputs, include_dvdr_in_tau21, apply_rsds)
     quantities = list(dict.fromkeys(lightconer.quantities))
     if include_dvdr_in_tau21:
         if "brightness_temp" not in quantities:
@@ -728,10 +914,13 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
     lib = lib or load(require_gpu=True)
     from . import grid_api as api
 
-    source = {q: ("velocity_z" if q == "los_velocity" else q) for q in quantities}
+    los = ("velocity_x", "velocity_y", "velocity_z") if angular else "velocity_z"
+    source = {q: (los if q == "los_velocity" else q) for q in quantities}
     n, d_para = int(so.HII_DIM), int(so.NON_CUBIC_FACTOR * so.HII_DIM)
     shape, cell = lightconer.get_shape(so), float(so.BOX_LEN) / float(so.HII_DIM)
-    mean_max = tuple(q for q in quantities if lightconer.interp_kinds.get(source[q], "mean") == "mean_max")
+    mean_max = tuple(q for q in quantities
+                     if q != "los_velocity" and lightconer.interp_kinds.get(source[q], "mean") == "mean_max")
+    order = lightconer.interpolation_order if angular else None
     if device is not None:
         import torch
 
@@ -751,6 +940,23 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
         def full(a):
             return a if a.shape == (n, n, d_para) else np.ascontiguousarray(np.broadcast_to(a, (n, n, d_para)))
 
+    if angular:  # the directions stay where the lightcones are built
+        nhat = lightconer.nhat
+        if device is not None:
+            nhat = torch.from_numpy(nhat).to(device)
+        boxes_needed = list(dict.fromkeys(b for q in quantities for b in
+                                          (source[q] if isinstance(source[q], tuple) else (source[q],))))
+
+    def node_boxes(boxes):
+        """this node's boxes of every lightcone: B-spline coefficients for orders 3 and 5"""
+        if not angular:
+            return {q: full(boxes[source[q]]) for q in quantities}
+        src = {b: full(boxes[b]) for b in boxes_needed}
+        if order >= 3:
+            src = api.spline_prefilter(src, order)
+        return {q: (tuple(src[b] for b in source[q]) if isinstance(source[q], tuple) else src[source[q]])
+                for q in quantities}
+
     nodes32 = [float(np.float32(z)) for z in nodes64]
     z64 = dict(zip(nodes32, nodes64))
     glob = {q: np.zeros(len(nodes32)) for q in lightconer.quantities if q != "los_velocity"}
@@ -761,8 +967,14 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
     for iz, (z, boxes, _ion, _ts, _ics) in enumerate(snaps):
         for q in glob:
             glob[q][iz] = mean(boxes[q])
-        cur = {q: full(boxes[source[q]]) for q in quantities}
-        if prev is not None:
+        cur = node_boxes(boxes)
+        if prev is not None and angular:
+            tab = lightconer.angular_tables(z64[z], z64[prev_z], cell)
+            if tab is not None:
+                i0, dist, w_lo, w_hi, w_norm = tab
+                api.lightcone_angular(lcs, cur, prev, i0, dist, w_lo, w_hi, w_norm, nhat, lightconer.origin,
+                                      order=order, mean_max=mean_max)
+        elif prev is not None:
             tab = lightconer.slab_tables(z64[z], z64[prev_z], cell, d_para)
             if tab is not None:
                 i0, plane, w_lo, w_hi, w_norm = tab
@@ -786,5 +998,8 @@ def run_lightcone(inputs: Inputs, lightconer: RectilinearLightconer, node_redshi
         lcs = {k: (v[..., keep].contiguous() if device is not None else np.ascontiguousarray(v[..., keep]))
                for k, v in lcs.items()}
         lcd, lcz = lcd[keep], requested.lc_redshifts
-    return {"lightcones": lcs, "lightcone_distances": lcd.copy(), "lightcone_redshifts": lcz,
-            "node_redshifts": tuple(nodes64), "global_quantities": glob, "history": history}
+    out = {"lightcones": lcs, "lightcone_distances": lcd.copy(), "lightcone_redshifts": lcz,
+           "node_redshifts": tuple(nodes64), "global_quantities": glob, "history": history}
+    if angular:
+        out["latitude"], out["longitude"] = requested.latitude.copy(), requested.longitude.copy()
+    return out

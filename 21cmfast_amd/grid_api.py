@@ -831,23 +831,35 @@ def lightcone_slices(lightcones: dict, box_lo: dict, box_hi: dict, i0: int, plan
 def lightcone_dvdr(brightness_temp, los_velocity, hubble, dx: float, max_dvdr: float, tau_21=None,
                    stream=None):
     """Correct a brightness-temperature lightcone in place for the line-of-sight velocity gradient
-    (reference: rsds.py:16-103 with periodic = False).  ``hubble``: H(z) [1/s] of every slice;
+    (reference: rsds.py:16-103 with periodic = False).  The line of sight is the last axis: a rectilinear
+    lightcone (HII_DIM, HII_DIM, n_slices) or an angular one (n_pix, n_slices).  ``hubble``: H(z) [1/s] of every slice;
     ``tau_21`` given: the USE_TS_FLUCT form, else the Taylor form clipped at +-max_dvdr H."""
-    n, _, n_slices = (int(x) for x in brightness_temp.shape)
+    shape = tuple(int(x) for x in brightness_temp.shape)
+    if len(shape) < 1:
+        raise ValueError("brightness_temp must have a line-of-sight axis")
+    n_slices = shape[-1]
+    # (HII_DIM, HII_DIM, n_slices): the rectilinear entry; any other (..., n_slices): the column entry
+    square = len(shape) == 3 and shape[0] == shape[1]
     for a in (brightness_temp, los_velocity, tau_21):
         if a is not None:
             _f32_dense(a, "brightness_temp / los_velocity / tau_21")
-        if a is not None and tuple(a.shape) != (n, n, n_slices):
+        if a is not None and tuple(a.shape) != shape:
             raise ValueError("los_velocity / tau_21 must have the shape of brightness_temp")
     hubble = np.ascontiguousarray(hubble, np.float64)
     if hubble.shape != (n_slices,):
         raise ValueError(f"hubble must hold one H(z) per slice ({n_slices})")
-    spec = S.DvdrSpec(hii_dim=n, n_slices=n_slices, dx=float(dx), max_dvdr=float(max_dvdr),
+    spec = S.DvdrSpec(hii_dim=shape[0] if square else 0, n_slices=n_slices, dx=float(dx), max_dvdr=float(max_dvdr),
                       use_ts_fluct=int(tau_21 is not None), hubble=hubble.ctypes.data_as(S.c_double_p))
     lib = load()
-    lib.c21cm_lightcone_dvdr_grids.restype = C.c_int
-    check(lib.c21cm_lightcone_dvdr_grids(C.byref(spec), _vptr(brightness_temp), _vptr(los_velocity),
-                                         _vptr(tau_21), _stream(stream)), "c21cm_lightcone_dvdr_grids")
+    ptrs = (_vptr(brightness_temp), _vptr(los_velocity), _vptr(tau_21), _stream(stream))
+    if square:
+        lib.c21cm_lightcone_dvdr_grids.restype = C.c_int
+        check(lib.c21cm_lightcone_dvdr_grids(C.byref(spec), *ptrs), "c21cm_lightcone_dvdr_grids")
+    else:
+        lib.c21cm_lightcone_dvdr_columns_grids.restype = C.c_int
+        n_cols = int(np.prod(shape[:-1], dtype=np.int64))
+        check(lib.c21cm_lightcone_dvdr_columns_grids(C.byref(spec), C.c_longlong(n_cols), *ptrs),
+              "c21cm_lightcone_dvdr_columns_grids")
 
 
 def rsd_shift(fields, los_velocity, disp_scale, n_sub: int = 4, periodic: bool = False, out=None,
@@ -887,4 +899,113 @@ def rsd_shift(fields, los_velocity, disp_scale, n_sub: int = 4, periodic: bool =
     lib.c21cm_rsd_shift_grids.restype = C.c_int
     check(lib.c21cm_rsd_shift_grids(C.byref(spec), ins, outs, _vptr(los_velocity), _stream(stream)),
           "c21cm_rsd_shift_grids")
+    return out
+
+
+def _f64_dense(a, what):
+    ok = (a.is_contiguous() and str(a.dtype) == "torch.float64") if _is_torch(a) else (
+        a.dtype == np.float64 and a.flags["C_CONTIGUOUS"])
+    if not ok:
+        raise ValueError(f"{what} must be a C-contiguous float64 array")
+
+
+def lightcone_angular(lightcones: dict, box_lo: dict, box_hi: dict, i0: int, distance, w_lo, w_hi,
+                      w_norm: float, nhat, origin=(0.0, 0.0, 0.0), order: int = 1, mean_max=("z_reion",),
+                      stream=None):
+    """Fill slices [i0, i0 + len(distance)) of every angular lightcone in ``lightcones`` (name -> array of
+    shape (n_pix, n_slices)) from the node boxes ``box_lo[name]`` / ``box_hi[name]`` (shape (HII_DIM,
+    HII_DIM, HII_D_PARA), periodic) that bracket them (reference: lightconers.py:162-287 with the
+    AngularLightconer).  Pixel p of slice j sits at ``distance[j] * nhat[:, p] + origin``
+    (cells); its value is the B-spline interpolation of ``order`` (0, 1, 3, 5) there, every tap
+    redshift-interpolated first, (w_lo box_lo + w_hi box_hi) / w_norm in fp64 (``mean_max`` fields: the
+    larger value where the two differ in sign).  For orders 3 and 5 the boxes must be B-spline
+    coefficients (``spline_prefilter``).  A vector field (``los_velocity``) gives a triple of boxes
+    (x, y, z components) and stores their projection on ``nhat``.  ``nhat``: float64 (3, n_pix), best a
+    torch CUDA tensor made once per run.  Arrays may be numpy or torch CUDA tensors, mixed freely; a numpy
+    lightcone receives only the slices of this call.  The tables come from
+    ``drivers.AngularLightconer.angular_tables``."""
+    distance = np.ascontiguousarray(distance, np.float64)
+    w_lo = np.ascontiguousarray(w_lo, np.float64)
+    w_hi = np.ascontiguousarray(w_hi, np.float64)
+    run = len(distance)
+    if len(w_lo) != run or len(w_hi) != run:
+        raise ValueError("distance, w_lo and w_hi must have the same length")
+    if int(order) not in (0, 1, 3, 5):
+        raise ValueError("order must be 0, 1, 3 or 5")
+    names = list(lightcones)
+    if not names:
+        raise ValueError("no lightcone to fill")
+    n_pix, n_slices = (int(x) for x in lightcones[names[0]].shape)
+    _f64_dense(nhat, "nhat")
+    if tuple(nhat.shape) != (3, n_pix):
+        raise ValueError(f"nhat must have shape (3, {n_pix})")
+    origin = np.asarray(origin, np.float64)
+    if origin.shape != (3,):
+        raise ValueError("origin must hold three coordinates")
+
+    def boxes(d, k):
+        v = d[k]
+        return list(v) if isinstance(v, (tuple, list)) else [v]
+
+    box_shape = None
+    for k in names:
+        if tuple(lightcones[k].shape) != (n_pix, n_slices):
+            raise ValueError(f"lightcone {k!r} has shape {tuple(lightcones[k].shape)}")
+        _f32_dense(lightcones[k], f"lightcone {k!r}")
+        lo, hi = boxes(box_lo, k), boxes(box_hi, k)
+        if len(lo) not in (1, 3) or len(hi) != len(lo):
+            raise ValueError(f"{k!r}: one node box, or three components of a vector field, on both sides")
+        for b in lo + hi:
+            _f32_dense(b, f"node box of {k!r}")
+            box_shape = box_shape or tuple(int(x) for x in b.shape)
+            if len(box_shape) != 3 or box_shape[0] != box_shape[1] or tuple(b.shape) != box_shape:
+                raise ValueError(f"node box of {k!r} has shape {tuple(b.shape)}: (HII_DIM, HII_DIM, HII_D_PARA)"
+                                 " and the same for every field")
+    nhat_p = C.cast(_vptr(nhat), S.c_double_p)
+    lib = load()
+    lib.c21cm_lightcone_angular_grids.restype = C.c_int
+    for c0 in range(0, len(names), LC_MAX_FIELDS):
+        chunk = names[c0:c0 + LC_MAX_FIELDS]
+        lo = [b for k in chunk for b in boxes(box_lo, k)]
+        hi = [b for k in chunk for b in boxes(box_hi, k)]
+        ptrs = [(C.c_void_p * len(v))(*[_vptr(a).value for a in v]) for v in (lo, hi)]
+        outs = (C.c_void_p * len(chunk))(*[_vptr(lightcones[k]).value for k in chunk])
+        spec = S.AngularSpec(
+            hii_dim=box_shape[0], hii_d_para=box_shape[2], n_pix=n_pix, n_slices=n_slices, i0=int(i0),
+            i1=int(i0) + run, n_fields=len(chunk),
+            mean_max=sum(1 << q for q, k in enumerate(chunk) if k in mean_max),
+            vector=sum(1 << q for q, k in enumerate(chunk) if len(boxes(box_lo, k)) == 3), order=int(order),
+            nhat=nhat_p, origin=(C.c_double * 3)(*origin), distance=distance.ctypes.data_as(S.c_double_p),
+            w_lo=w_lo.ctypes.data_as(S.c_double_p), w_hi=w_hi.ctypes.data_as(S.c_double_p), w_norm=float(w_norm))
+        check(lib.c21cm_lightcone_angular_grids(C.byref(spec), *ptrs, outs, _stream(stream)),
+              "c21cm_lightcone_angular_grids")
+
+
+def spline_prefilter(boxes, order: int, out=None, stream=None):
+    """B-spline coefficients of ``order`` (3 or 5) of periodic 3-D boxes: what
+    ``scipy.ndimage.spline_filter(box, order, mode="grid-wrap")`` computes, stored as float32.  ``boxes``: a
+    dict (name -> array) or a sequence of float32 arrays of one shape; ``out`` (same kind; default: new
+    arrays where each box lives) may be ``boxes`` itself.  Arrays may be numpy or torch CUDA tensors,
+    mixed freely; returns ``out``."""
+    named = isinstance(boxes, dict)
+    names = list(boxes) if named else list(range(len(boxes)))
+    if not names:
+        raise ValueError("no box to prefilter")
+    shape = tuple(int(x) for x in boxes[names[0]].shape)
+    if len(shape) != 3:
+        raise ValueError("the boxes must be 3-D")
+    if out is None:
+        made = {k: _new_like(boxes[k], 0.0) for k in names}
+        out = made if named else [made[k] for k in names]
+    for k in names:
+        for a, what in ((boxes[k], "box"), (out[k], "output")):
+            _f32_dense(a, f"{what} {k!r}")
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{what} {k!r} has shape {tuple(a.shape)}, not {shape}")
+    ins = (C.c_void_p * len(names))(*[_vptr(boxes[k]).value for k in names])
+    outs = (C.c_void_p * len(names))(*[_vptr(out[k]).value for k in names])
+    lib = load()
+    lib.c21cm_spline_prefilter_grids.restype = C.c_int
+    check(lib.c21cm_spline_prefilter_grids(*shape, int(order), len(names), ins, outs, _stream(stream)),
+          "c21cm_spline_prefilter_grids")
     return out

@@ -379,6 +379,29 @@ class RsdSpec(_Base):
     ]
 
 
+class AngularSpec(_Base):
+    """``c21cm_angular_spec`` (include/c21cm_grid.h): the angular slices of one node pair."""
+
+    _fields_ = [
+        ("hii_dim", C.c_int),
+        ("hii_d_para", C.c_int),
+        ("n_pix", C.c_longlong),
+        ("n_slices", C.c_int),
+        ("i0", C.c_int),
+        ("i1", C.c_int),
+        ("n_fields", C.c_int),
+        ("mean_max", C.c_uint),
+        ("vector", C.c_uint),
+        ("order", C.c_int),
+        ("nhat", c_double_p),
+        ("origin", C.c_double * 3),
+        ("distance", c_double_p),
+        ("w_lo", c_double_p),
+        ("w_hi", c_double_p),
+        ("w_norm", C.c_double),
+    ]
+
+
 def brightness_spec(n_cells, redshift, cosmo=None, use_ts_fluct=False) -> "BrightnessSpec":
     """The two float constants of BrightnessTemperatureBox.c:43-49 for a CosmoParams struct
     (default cosmology if None)."""

@@ -768,6 +768,53 @@ typedef struct c21cm_rsd_spec {
 int c21cm_rsd_shift_grids(const c21cm_rsd_spec *spec, const float *const *fields, float *const *out,
                           const float *los_velocity, void *stream);
 
+/* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
+ * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
+ * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
+ * each box (hii_dim x hii_dim x hii_d_para) is periodic along every axis.  The value is the B-spline
+ * interpolation of the given order at x (scipy.ndimage.map_coordinates, mode "grid-wrap") in which
+ * every tap is first redshift-interpolated, (w_lo[j] box_lo + w_hi[j] box_hi) / w_norm in fp64 (bit f
+ * of mean_max: where box_lo * box_hi < 0 the larger of the two); the sum is fp64, stored as fp32.
+ * Orders 3 and 5 read B-spline coefficients (c21cm_spline_prefilter_grids of each node box); the
+ * prefilter is linear, so this is exact for "mean" fields; mean_max fields need order 0 or 1.
+ * Bit f of vector: field f takes three consecutive boxes (x, y, z components) and stores their
+ * projection sum_k v_k nhat_k (los_velocity).  box_lo / box_hi list n_fields + 2 popcount(vector)
+ * boxes in field order, lightcone lists n_fields outputs float[n_pix][n_slices] (slices fastest).
+ * Boxes, lightcones and nhat may be host or device memory, mixed; a host nhat is copied every call,
+ * so a run keeps it on the device.  A non-finite sum (a non-finite tap) is C21CM_INFINITY_OR_NAN_ERROR. */
+typedef struct c21cm_angular_spec {
+    int hii_dim;              /* node boxes: hii_dim x hii_dim x hii_d_para */
+    int hii_d_para;
+    long long n_pix;          /* pixels (columns of the lightcone) */
+    int n_slices;             /* length of the lightcone */
+    int i0, i1;               /* slices filled by this call, 0 <= i0 < i1 <= n_slices */
+    int n_fields;             /* outputs, 1 .. C21CM_LC_MAX_FIELDS */
+    unsigned mean_max;        /* bit f: field f interpolates with mean_max */
+    unsigned vector;          /* bit f: field f is the projection of a vector field (three boxes) */
+    int order;                /* 0, 1, 3 or 5 */
+    const double *nhat;       /* [3][n_pix] rotated unit directions */
+    double origin[3];         /* cells */
+    const double *distance;   /* host, i1 - i0: comoving distance of the slice [cells] */
+    const double *w_lo;       /* host, i1 - i0: |dc_hi - d| (cells) */
+    const double *w_hi;       /* host, i1 - i0: |dc_lo - d| */
+    double w_norm;            /* |dc_lo - dc_hi| > 0 */
+} c21cm_angular_spec;
+
+int c21cm_lightcone_angular_grids(const c21cm_angular_spec *spec, const float *const *box_lo,
+                                  const float *const *box_hi, float *const *lightcone, void *stream);
+
+/* B-spline coefficients of order 3 or 5 of n_fields periodic boxes (n0 x n1 x n2, the last axis
+ * fastest): what scipy.ndimage.spline_filter(box, order, mode = "grid-wrap") computes, stored as
+ * fp32.  coefs[f] may alias boxes[f]; pointers may be host or device memory.  A non-finite box value
+ * is C21CM_INFINITY_OR_NAN_ERROR. */
+int c21cm_spline_prefilter_grids(int n0, int n1, int n2, int order, int n_fields, const float *const *boxes,
+                                 float *const *coefs, void *stream);
+
+/* c21cm_lightcone_dvdr_grids on n_cols columns of spec->n_slices slices (any lightcone whose line of sight
+ * is its fastest axis: an angular one has n_pix columns); spec->hii_dim is not read. */
+int c21cm_lightcone_dvdr_columns_grids(const c21cm_dvdr_spec *spec, long long n_cols, float *brightness_temp,
+                                       const float *los_velocity, const float *tau_21, void *stream);
+
 /* Library management */
 const char *c21cm_version(void);
 int c21cm_device_synchronize(void);

@@ -15,7 +15,16 @@
     512^2 columns of 2000 and 4000 slices with 1 and 3 fields (4 sub-cells, not periodic), its
     contract (4 B of velocity + 8 B per field and cell) against the time of one call.
 
-    python tools/time_lightcone.py [--sizes 256,512] [--z-end 6] [--step 1.02] [--rsds] [--out FILE]
+(4) With --angular ORDERS (e.g. 1,3): for each HII_DIM the run of (1) without USE_TS_FLUCT, with
+    KEEP_3D_VELOCITIES and the fields density, neutral_fraction, brightness_temp (+ los_velocity for
+    dv/dr), once rectilinear and once per order with a like_rectilinear AngularLightconer (n_pix =
+    HII_DIM^2: the same output cells).  The assembly calls (slabs; angular sampling and the spline
+    prefilter) are timed as (1) times the slabs, with the bytes of the taps the sampling reads (8 B per
+    tap and component: both node boxes) plus 4 B per stored cell, the prefilter's 16 B per cell, pole and
+    axis (two passes that read and write the line), and the HBM the kept coefficients take.
+
+    python tools/time_lightcone.py [--sizes 256,512] [--z-end 6] [--step 1.02] [--rsds] [--angular 1,3]
+                                   [--out FILE]
 Run it under rocprofv3 --kernel-trace --stats for the kernel table.
 """
 import argparse
@@ -43,9 +52,94 @@ ap.add_argument("--z-end", type=float, default=6.0)
 ap.add_argument("--step", type=float, default=1.02)
 ap.add_argument("--skip-runs", action="store_true")
 ap.add_argument("--rsds", action="store_true")
+ap.add_argument("--angular", default=None)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 lib = pkg.load(require_gpu=True)
+
+if args.angular:  # ---- (4) rectilinear against angular assembly
+    ANG_FIELDS = ("density", "neutral_fraction", "brightness_temp")
+    tm = {"assembly_s": 0.0, "calls": 0, "tap_bytes": 0, "prefilter_s": 0.0, "prefilter_bytes": 0,
+          "coef_boxes": 0}
+    _ang, _pre, _sl = api.lightcone_angular, api.spline_prefilter, api.lightcone_slices
+
+    def t_ang(lightcones, box_lo, box_hi, i0, distance, *a, order=1, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _ang(lightcones, box_lo, box_hi, i0, distance, *a, order=order, **kw)
+        torch.cuda.synchronize()
+        tm["assembly_s"] += time.perf_counter() - t0
+        tm["calls"] += 1
+        taps = (order + 1) ** 3
+        comps = sum(len(v) if isinstance(v, tuple) else 1 for v in box_lo.values())
+        n_pix = next(iter(lightcones.values())).shape[0]
+        tm["tap_bytes"] += n_pix * len(distance) * (8 * taps * comps + 4 * len(lightcones))
+
+    def t_pre(boxes, order, *a, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = _pre(boxes, order, *a, **kw)
+        torch.cuda.synchronize()
+        tm["prefilter_s"] += time.perf_counter() - t0
+        cells = next(iter(boxes.values())).numel()
+        tm["prefilter_bytes"] += 16 * 3 * (1 if order == 3 else 2) * cells * len(boxes)
+        tm["coef_boxes"] = len(boxes)
+        return out
+
+    def t_sl(lightcones, box_lo, box_hi, i0, plane, *a, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _sl(lightcones, box_lo, box_hi, i0, plane, *a, **kw)
+        torch.cuda.synchronize()
+        tm["assembly_s"] += time.perf_counter() - t0
+        tm["calls"] += 1
+        first = next(iter(lightcones.values()))
+        tm["tap_bytes"] += 12 * first.shape[0] * first.shape[1] * len(plane) * len(lightcones)
+
+    api.lightcone_angular, api.spline_prefilter, api.lightcone_slices = t_ang, t_pre, t_sl
+    res = {"runs": []}
+    for n in (int(s) for s in args.sizes.split(",")):
+        for kind in ["rectilinear"] + [f"angular_o{o}" for o in args.angular.split(",")]:
+            for k in tm:
+                tm[k] = 0
+            inputs = D.Inputs(random_seed=12345, HII_DIM=n, DIM=2 * n, BOX_LEN=1.5 * n, SOURCE_MODEL=1,
+                              USE_TS_FLUCT=False, USE_LYA_HEATING=False, HII_FILTER=0, USE_EXP_FILTER=False,
+                              CELL_RECOMB=False, R_BUBBLE_MAX=30.0, ZPRIME_STEP_FACTOR=args.step,
+                              Z_HEAT_MAX=35.0, N_THREADS=16, KEEP_3D_VELOCITIES=True)
+            nodes = D.get_logspaced_redshifts(args.z_end, args.step, 35.0)
+            z0, z1 = nodes[-1] + 0.2, nodes[0] - 0.2
+            if kind == "rectilinear":
+                lc = D.RectilinearLightconer.between_redshifts(z0, z1, 1.5, quantities=ANG_FIELDS)
+            else:
+                lc = D.AngularLightconer.like_rectilinear(inputs.simulation_options, z0, z1, quantities=ANG_FIELDS,
+                                                          interpolation_order=int(kind[-1]))
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            out = D.run_lightcone(inputs, lc, nodes, data_path=DATA, device="cuda", lib=lib)
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            box_gb = n * n * n * 4 / 1e9
+            row = {"hii_dim": n, "kind": kind, "n_nodes": len(nodes), "n_slices": len(lc.lc_distances),
+                   "lightcone_fields": sorted(out["lightcones"]), "run_s": round(wall, 3),
+                   "assembly_s": round(tm["assembly_s"], 4), "assembly_calls": tm["calls"],
+                   "prefilter_s": round(tm["prefilter_s"], 4),
+                   "share_of_run": round((tm["assembly_s"] + tm["prefilter_s"]) / wall, 5),
+                   "assembly_GB": round(tm["tap_bytes"] / 1e9, 2),
+                   "assembly_GBps_wall": round(tm["tap_bytes"] / max(tm["assembly_s"], 1e-12) / 1e9, 1),
+                   "prefilter_GB": round(tm["prefilter_bytes"] / 1e9, 2),
+                   "prefilter_GBps_wall": round(tm["prefilter_bytes"] / max(tm["prefilter_s"], 1e-12) / 1e9, 1),
+                   # the coefficients of the current and the previous node of every box sampled
+                   "coefficients_GB": round(2 * tm["coef_boxes"] * box_gb, 3),
+                   "peak_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 3)}
+            print(json.dumps(row), flush=True)
+            res["runs"].append(row)
+            del out
+            torch.cuda.empty_cache()
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+    sys.exit(0)
 
 # ---- wrap the two lightcone calls of run_lightcone with wall-clock timers
 acc = {"slab_s": 0.0, "slab_calls": 0, "slab_bytes": 0, "dvdr_s": 0.0, "dvdr_bytes": 0, "rsd_s": 0.0,
