@@ -68,6 +68,8 @@ const char *c21hip_get_error(void);
 /* ---- fft.hip : in-place padded real 3-D transforms (reference: dft.c:18-72) ---- */
 int c21hip_fft_r2c(float *padded, int nx, int ny, int nz, void *stream);
 int c21hip_fft_c2r(float *padded, int nx, int ny, int nz, void *stream);
+/* n_batch padded boxes back to back (rocFFT, one batched plan) */
+int c21hip_fft_r2c_batched(float *padded, int nx, int ny, int nz, int n_batch, void *stream);
 void c21hip_fft_release(void);
 /* 1 when the hand-written power-of-two transform is used, 0 for rocFFT */
 int c21hip_fft_is_native(int nx, int ny, int nz);
@@ -737,6 +739,30 @@ size_t c21hip_rsd_lds_bytes(int n, int nf, int *cpb);
 int c21hip_rsd_shift(const float *const *in, float *const *out, int nf, const float *vel,
                      const double *disp_scale, size_t n_cols, int n, int m, int periodic, int *bad,
                      void *stream);
+
+/* ---- power_kernels.hip : power spectra of boxes and lightcone chunks, binned on the device ---- */
+#define C21HIP_POWER_MAX_LDS (144 * 1024) /* dynamic LDS of one bin workgroup */
+typedef struct c21hip_power_tabs { /* device pointers the driver fills (power_driver.c) */
+    const double *kx, *ky, *kz; /* wavenumbers per axis: nx, ny, nz/2 + 1 (numpy's fftfreq(n, L/n) 2 pi) */
+    const double *edges;        /* n_local + 1: |k|^2 thresholds of the |k| edges, or k_par edges (cylindrical) */
+    const int *rows;            /* row ids i ny + j, grouped (cylindrical: by k_perp bin) */
+    const int *wg_rows;         /* n_wg + 1: workgroup w bins rows[wg_rows[w] .. wg_rows[w + 1]) */
+    const int *group_wg;        /* n_groups + 1: the workgroups of group g (its bins g n_local ..) */
+    int n_wg, n_groups, n_local;
+    int ignore_zero_mode, ignore_kpar_zero;
+} c21hip_power_tabs;
+size_t c21hip_power_lds_bytes(int n_local, int cylindrical);
+/* in[offsets[b] + (i ny + j) row_pitch + l] -> padded[b][i][j][l] for l < nz; *bad |= 1 on a non-finite value */
+int c21hip_power_pack(const float *in, float *padded, int nx, int ny, int nz, long long row_pitch,
+                      const long long *offsets, int n_batch, int *bad, void *stream);
+/* one pass over the half spectra complex[n_batch][nx][ny][nz/2+1] (spec2: cross power, or NULL) into
+ * partials[n_batch][n_wg][n_local][3 or 4] */
+int c21hip_power_bin(const float *spec1, const float *spec2, int nx, int ny, int nz, int n_batch,
+                     int cylindrical, const c21hip_power_tabs *t, double *partials, int *bad, void *stream);
+/* partials -> totals[n_batch][n_groups n_local][3 or 4] -> means (device outputs) */
+int c21hip_power_finish(const double *partials, double *totals, int n_batch, int cylindrical,
+                        const c21hip_power_tabs *t, double scale, double *power, double *kmean,
+                        long long *counts, void *stream);
 
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */

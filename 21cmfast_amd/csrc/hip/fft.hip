@@ -30,12 +30,12 @@ struct Plan {
     void *work = nullptr;
     size_t work_bytes = 0;
 };
-using Key = std::tuple<int, int, int, int>;
+using Key = std::tuple<int, int, int, int, int>;  // nx, ny, nz, inverse, batch
 std::map<Key, Plan> g_plans;
 std::mutex g_mutex;
 bool g_setup = false;
 
-int make_plan(Plan &p, int nx, int ny, int nz, int inverse) {
+int make_plan(Plan &p, int nx, int ny, int nz, int inverse, int batch) {
     if (!g_setup) {
         if (rocfft_setup() != rocfft_status_success) {
             c21hip_set_error("rocfft_setup failed");
@@ -48,23 +48,26 @@ int make_plan(Plan &p, int nx, int ny, int nz, int inverse) {
     size_t lengths[3] = {(size_t)nz, (size_t)ny, (size_t)nx};
     size_t rstride[3] = {1, 2 * nzc, 2 * nzc * (size_t)ny};
     size_t cstride[3] = {1, nzc, nzc * (size_t)ny};
+    // batches of padded boxes back to back (single transforms keep the plans they always had)
+    const size_t rdist = batch > 1 ? 2 * nzc * (size_t)ny * (size_t)nx : 0;
+    const size_t cdist = batch > 1 ? nzc * (size_t)ny * (size_t)nx : 0;
     rocfft_plan_description desc = nullptr;
     rocfft_status st = rocfft_plan_description_create(&desc);
     if (st == rocfft_status_success) {
         if (!inverse)
             st = rocfft_plan_description_set_data_layout(
                 desc, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                nullptr, 3, rstride, 0, 3, cstride, 0);
+                nullptr, 3, rstride, rdist, 3, cstride, cdist);
         else
             st = rocfft_plan_description_set_data_layout(
                 desc, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, nullptr,
-                nullptr, 3, cstride, 0, 3, rstride, 0);
+                nullptr, 3, cstride, cdist, 3, rstride, rdist);
     }
     if (st == rocfft_status_success)
         st = rocfft_plan_create(&p.plan, rocfft_placement_inplace,
                                 inverse ? rocfft_transform_type_real_inverse
                                         : rocfft_transform_type_real_forward,
-                                rocfft_precision_single, 3, lengths, 1, desc);
+                                rocfft_precision_single, 3, lengths, (size_t)batch, desc);
     if (desc) rocfft_plan_description_destroy(desc);
     if (st != rocfft_status_success) {
         c21hip_set_error("rocFFT plan creation failed (%dx%dx%d, inverse=%d, status %d)", nx, ny,
@@ -85,15 +88,15 @@ int make_plan(Plan &p, int nx, int ny, int nz, int inverse) {
     return 0;
 }
 
-int run_rocfft(float *padded, int nx, int ny, int nz, int inverse, void *stream) {
+int run_rocfft(float *padded, int nx, int ny, int nz, int inverse, void *stream, int batch = 1) {
     Plan *p = nullptr;
     {
         std::lock_guard<std::mutex> lock(g_mutex);
-        Key key(nx, ny, nz, inverse);
+        Key key(nx, ny, nz, inverse, batch);
         auto it = g_plans.find(key);
         if (it == g_plans.end()) {
             Plan fresh;
-            int st = make_plan(fresh, nx, ny, nz, inverse);
+            int st = make_plan(fresh, nx, ny, nz, inverse, batch);
             if (st) return st;
             it = g_plans.emplace(key, fresh).first;
         }
@@ -126,6 +129,14 @@ extern "C" int c21hip_fft_is_native(int nx, int ny, int nz) {
 extern "C" int c21hip_fft_r2c(float *padded, int nx, int ny, int nz, void *stream) {
     // forward transforms run 2-3 times per Compute* call (pre-loop only): rocFFT for now
     return run_rocfft(padded, nx, ny, nz, 0, stream);
+}
+
+extern "C" int c21hip_fft_r2c_batched(float *padded, int nx, int ny, int nz, int n_batch, void *stream) {
+    if (n_batch < 1) {
+        c21hip_set_error("batched r2c: n_batch must be >= 1");
+        return C21CM_VALUE_ERROR;
+    }
+    return run_rocfft(padded, nx, ny, nz, 0, stream, n_batch);
 }
 
 extern "C" int c21hip_fft_c2r(float *padded, int nx, int ny, int nz, void *stream) {

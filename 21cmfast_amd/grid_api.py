@@ -1009,3 +1009,56 @@ def spline_prefilter(boxes, order: int, out=None, stream=None):
     check(lib.c21cm_spline_prefilter_grids(*shape, int(order), len(names), ins, outs, _stream(stream)),
           "c21cm_spline_prefilter_grids")
     return out
+
+
+def power_spectrum(field, field2, shape, lengths, edges, edges_par=None, *, offsets=(0,), row_pitch=None,
+                   ignore_zero_mode=False, ignore_kperp_zero=False, ignore_kpar_zero=False, stream=None):
+    """Binned power spectra of ``len(offsets)`` boxes of ``shape`` = (nx, ny, nz) cells and ``lengths``
+    (Lx, Ly, Lz) read from the float32 array ``field`` (box b at flat element ``offsets[b] + (i ny + j)
+    row_pitch + l``; ``row_pitch`` defaults to nz), cross spectra with ``field2`` (same layout) when given.
+    ``edges``: the |k| edges, or the k_perp edges with ``edges_par`` the k_par edges (cylindrical).
+    Returns ``(power, kmean, counts)``: float64, float64, int64, shaped (n_batch, n_bins) or (n_batch,
+    n_perp, n_par) with kmean (n_batch, n_perp + n_par); numpy for numpy input, torch on the field's device
+    for a torch CUDA field."""
+    nx, ny, nz = (int(x) for x in shape)
+    row_pitch = nz if row_pitch is None else int(row_pitch)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_batch = len(offsets)
+    size = int(np.prod(field.shape, dtype=np.int64))
+    for a, what in ((field, "field"), (field2, "field2")):
+        if a is None:
+            continue
+        _f32_dense(a, what)
+        if int(np.prod(a.shape, dtype=np.int64)) != size:
+            raise ValueError(f"{what} has {int(np.prod(a.shape))} elements, not {size}")
+    if n_batch < 1 or offsets.min() < 0 or offsets.max() + (nx * ny - 1) * row_pitch + nz > size:
+        raise ValueError("the boxes do not lie inside the field")
+    edges = np.ascontiguousarray(edges, np.float64)
+    cyl = edges_par is not None
+    edges_par = np.ascontiguousarray(edges_par if cyl else [0.0, 1.0], np.float64)
+    bins = S.PowerBins(cylindrical=int(cyl), n_bins=len(edges) - 1, n_bins_par=len(edges_par) - 1,
+                       edges=edges.ctypes.data_as(S.c_double_p), edges_par=edges_par.ctypes.data_as(S.c_double_p),
+                       ignore_zero_mode=int(bool(ignore_zero_mode)), ignore_kperp_zero=int(bool(ignore_kperp_zero)),
+                       ignore_kpar_zero=int(bool(ignore_kpar_zero)))
+    nb, npar = len(edges) - 1, len(edges_par) - 1
+    pshape = (n_batch, nb, npar) if cyl else (n_batch, nb)
+    kshape = (n_batch, nb + npar) if cyl else (n_batch, nb)
+    if _is_torch(field):
+        import torch
+
+        power = torch.empty(pshape, dtype=torch.float64, device=field.device)
+        kmean = torch.empty(kshape, dtype=torch.float64, device=field.device)
+        counts = torch.empty(pshape, dtype=torch.int64, device=field.device)
+    else:
+        power, kmean, counts = np.empty(pshape), np.empty(kshape), np.empty(pshape, np.int64)
+    lib = load()
+    lib.c21cm_power_spectrum_grids.restype = C.c_int
+    lib.c21cm_power_spectrum_grids.argtypes = [
+        C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_double,
+        C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    Lx, Ly, Lz = (float(x) for x in lengths)
+    check(lib.c21cm_power_spectrum_grids(_vptr(field), _vptr(field2), nx, ny, nz, n_batch, row_pitch,
+                                         offsets.ctypes.data_as(C.c_void_p), Lx, Ly, Lz, C.byref(bins),
+                                         _vptr(power), _vptr(kmean), _vptr(counts), _stream(stream)),
+          "c21cm_power_spectrum_grids")
+    return power, kmean, counts

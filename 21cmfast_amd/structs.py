@@ -402,6 +402,21 @@ class AngularSpec(_Base):
     ]
 
 
+class PowerBins(_Base):
+    """``c21cm_power_bins`` (include/c21cm_grid.h): the bins of a power spectrum."""
+
+    _fields_ = [
+        ("cylindrical", C.c_int),
+        ("n_bins", C.c_int),
+        ("n_bins_par", C.c_int),
+        ("edges", c_double_p),
+        ("edges_par", c_double_p),
+        ("ignore_zero_mode", C.c_int),
+        ("ignore_kperp_zero", C.c_int),
+        ("ignore_kpar_zero", C.c_int),
+    ]
+
+
 def brightness_spec(n_cells, redshift, cosmo=None, use_ts_fluct=False) -> "BrightnessSpec":
     """The two float constants of BrightnessTemperatureBox.c:43-49 for a CosmoParams struct
     (default cosmology if None)."""

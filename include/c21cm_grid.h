@@ -768,6 +768,33 @@ typedef struct c21cm_rsd_spec {
 int c21cm_rsd_shift_grids(const c21cm_rsd_spec *spec, const float *const *fields, float *const *out,
                           const float *los_velocity, void *stream);
 
+/* ---- Power spectra of boxes and lightcone chunks ----
+ * n_batch boxes of nx x ny x nz cells, box b at field[batch_offsets[b] + (i ny + j) row_pitch + l]
+ * (row_pitch = nz for a dense box; chunks of a lightcone of n_slices: row_pitch = n_slices, offset = the
+ * chunk's first slice), each of lengths Lx, Ly, Lz.  F = (V/N) DFT(f) (fp32 transform), P = |F|^2 / V, or
+ * Re(F F2*) / V when field2 is given (same layout).  Every mode of the full grid with its wavenumber
+ * k = numpy's fftfreq(n, L/n) 2 pi per axis is binned with np.digitize on the given edges: |k| =
+ * sqrt((kx^2 + ky^2) + kz^2) (fp64), or k_perp = sqrt(kx^2 + ky^2) and k_par = |kz| (cylindrical); each bin
+ * is the plain mean.  Outputs (host or device): power[n_batch][n_bins (* n_bins_par)], kmean[n_batch][...]
+ * (mean |k| per bin; cylindrical: mean k_perp per k_perp bin, then mean k_par per k_par bin), counts (modes
+ * per bin); empty bins are NaN.  Deterministic: two calls give the same bits.  Pointers may be host or device
+ * memory.  A non-finite field value (or transform output) is C21CM_INFINITY_OR_NAN_ERROR; nothing is written. */
+typedef struct c21cm_power_bins {
+    int cylindrical;           /* 0: |k| bins; 1: (k_perp, k_par) bins */
+    int n_bins;                /* |k| (or k_perp) bins >= 1 */
+    int n_bins_par;            /* k_par bins >= 1 (cylindrical) */
+    const double *edges;       /* host, n_bins + 1, increasing */
+    const double *edges_par;   /* host, n_bins_par + 1, increasing (cylindrical) */
+    int ignore_zero_mode;      /* drop k = 0 */
+    int ignore_kperp_zero;     /* drop kx = ky = 0 */
+    int ignore_kpar_zero;      /* drop kz = 0 */
+} c21cm_power_bins;
+
+int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, int ny, int nz, int n_batch,
+                               long long row_pitch, const long long *batch_offsets, double Lx, double Ly,
+                               double Lz, const c21cm_power_bins *bins, double *power, double *kmean,
+                               long long *counts, void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);

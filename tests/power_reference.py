@@ -1,0 +1,161 @@
+"""Host restatement (numpy, fp64, the full Fourier grid) of ``21cmfast_amd.powerspec``: the spec of every
+option beyond powerbox's defaults.
+
+With its defaults ``get_power`` is ``oracle/powerbox_power.get_power`` (tests/test_power_host.py holds the
+two to 1e-12); only that path is pinned to powerbox, through the reference fixtures.  The rest is written
+down here:
+
+* grid: F = (V/N) fftn(f), k_i = ``fftfreq(n_i, d=L_i/n_i) * 2 pi``, |k| = sqrt((kx^2 + ky^2) + kz^2);
+  P = |F|^2 / V, or Re(F F2*) / V with ``deltax2`` (cross power);
+* edges (``_getbins``): an array of edges is used as given; an int n gives ``np.linspace(min, max, n + 1)``
+  or, with ``log_bins``, ``np.geomspace(smallest non-zero, max, n + 1)`` of the binned coordinate over the
+  FULL grid.  ``max`` is the smallest per-axis maximum (``bins_upto_boxlen=True``) or the grid's maximum
+  (``bins_upto_boxlen=False``).  The ignore flags never move the edges;
+* ``np.digitize``: half-open bins [e_i, e_i+1), modes below the first or at/above the last edge dropped;
+* ``ignore_zero_mode`` drops k = 0, ``ignore_kperp_zero`` the modes with kx = ky = 0, ``ignore_kpar_zero``
+  those with kz = 0 (the line of sight is the last axis);
+* each bin is the plain mean of P over its modes, ``k`` the mean of the binned coordinate, ``counts`` the
+  number of modes; empty bins are NaN; ``bin_ave=False`` returns the edges instead of ``k``;
+* cylindrical: k_perp = sqrt(kx^2 + ky^2) binned on its own edges (max: the smaller of max|kx|, max|ky|;
+  default count ``int(sqrt(nx ny) / 2.2)``), k_par = |kz| (max: max|kz|; default count ``int(nz / 2.2)``);
+  ``kperp`` / ``kpar`` are the mean k_perp / k_par over the modes of a row / column of bins;
+* lightcones: chunk c is slices [s_c, s_c + n) of the last axis, a box of (nx dx, ny dx, n dx); the default
+  chunks are cubic (n = nx) and back to back from slice 0; a chunk's redshift is the mean of the redshifts of
+  its slices (n - 1) // 2 and n // 2; ``dimensionless`` multiplies by k^3 / (2 pi^2) with k the bin's mean
+  |k| (cylindrical: sqrt(kperp^2 + kpar^2) of the bin's means).
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+
+def _lengths(boxlength, dim):
+    return [float(boxlength)] * dim if np.isscalar(boxlength) else [float(x) for x in boxlength]
+
+
+def _grids(shape, boxlength):
+    L = _lengths(boxlength, len(shape))
+    freq = [np.fft.fftfreq(n, d=l / n) * 2.0 * np.pi for n, l in zip(shape, L)]
+    return L, np.meshgrid(*freq, indexing="ij")
+
+
+def _spectrum(field, boxlength, deltax2):
+    field = np.asarray(field, np.float64)
+    L = _lengths(boxlength, field.ndim)
+    V = float(np.prod(L))
+    ft = np.fft.fftn(field) * (V / float(np.prod(field.shape)))
+    if deltax2 is None:
+        return (ft.real**2 + ft.imag**2) / V
+    ft2 = np.fft.fftn(np.asarray(deltax2, np.float64)) * (V / float(np.prod(field.shape)))
+    return (ft.real * ft2.real + ft.imag * ft2.imag) / V
+
+
+def _getbins(bins, coord, log, upto_boxlen):
+    if np.ndim(bins) > 0:
+        return np.asarray(bins, np.float64)
+    mx = coord.max()
+    if upto_boxlen:
+        mx = min(float(np.min(np.max(coord, axis=i))) for i in range(coord.ndim))
+    if log:
+        return np.geomspace(coord[coord > 0].min(), mx, int(bins) + 1)
+    return np.linspace(coord.min(), mx, int(bins) + 1)
+
+
+def _bin(x, weights_list, keep, edges):
+    indx = np.digitize(x[keep], edges)
+    counts = np.bincount(indx, minlength=len(edges) + 1)[1:-1]
+    out = []
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for w in weights_list:
+            out.append(np.bincount(indx, weights=w[keep], minlength=len(edges) + 1)[1:-1] / counts)
+    return out, counts
+
+
+def get_power(field, boxlength, *, deltax2=None, bins=None, log_bins=False, ignore_zero_mode=False,
+              bins_upto_boxlen=True, ignore_kperp_zero=False, ignore_kpar_zero=False, bin_ave=True,
+              return_counts=False):
+    field = np.asarray(field)
+    N = field.shape
+    _, (kx, ky, kz) = _grids(N, boxlength)
+    kmag = np.sqrt(sum(g * g for g in (kx, ky, kz)))
+    P = _spectrum(field, boxlength, deltax2)
+    if bins is None:
+        bins = int(np.prod(N) ** (1.0 / field.ndim) / 2.2)
+    edges = _getbins(bins, kmag, log_bins, bins_upto_boxlen)
+    keep = np.ones(N, bool)
+    if ignore_zero_mode:
+        keep &= kmag != 0
+    if ignore_kperp_zero:
+        keep &= (kx != 0) | (ky != 0)
+    if ignore_kpar_zero:
+        keep &= kz != 0
+    (p_av, k_av), counts = _bin(kmag, [P, kmag], keep, edges)
+    out = (p_av, k_av if bin_ave else edges)
+    return out + (counts,) if return_counts else out
+
+
+def get_cylindrical_power(field, boxlength, *, deltax2=None, kperp_bins=None, kpar_bins=None, log_bins=False,
+                          ignore_zero_mode=False, return_counts=False):
+    field = np.asarray(field)
+    N = field.shape
+    _, (kx, ky, kz) = _grids(N, boxlength)
+    kperp = np.sqrt(kx * kx + ky * ky)
+    kpar = np.abs(kz)
+    P = _spectrum(field, boxlength, deltax2)
+    if kperp_bins is None:
+        kperp_bins = int(np.prod(N[:2]) ** (1.0 / 2) / 2.2)
+    if kpar_bins is None:
+        kpar_bins = int(np.prod(N[2:]) ** (1.0 / 1) / 2.2)
+    ep = _getbins(kperp_bins, kperp[:, :, 0], log_bins, True)
+    ez = _getbins(kpar_bins, kpar[0, 0, :], log_bins, False)
+    keep = np.ones(N, bool)
+    if ignore_zero_mode:
+        keep &= (kperp != 0) | (kpar != 0)
+    ip = np.digitize(kperp, ep) - 1
+    iz = np.digitize(kpar, ez) - 1
+    keep &= (ip >= 0) & (ip < len(ep) - 1) & (iz >= 0) & (iz < len(ez) - 1)
+    flat = (ip * (len(ez) - 1) + iz)[keep]
+    nb = (len(ep) - 1) * (len(ez) - 1)
+    counts = np.bincount(flat, minlength=nb).reshape(len(ep) - 1, len(ez) - 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        power = np.bincount(flat, weights=P[keep], minlength=nb).reshape(counts.shape) / counts
+        sp = np.bincount(flat, weights=kperp[keep], minlength=nb).reshape(counts.shape)
+        sz = np.bincount(flat, weights=kpar[keep], minlength=nb).reshape(counts.shape)
+        kp = sp.sum(axis=1) / counts.sum(axis=1)
+        kz_av = sz.sum(axis=0) / counts.sum(axis=0)
+    out = (power, kp, kz_av)
+    return out + (counts,) if return_counts else out
+
+
+def lightcone_power_spectra(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None,
+                            dimensionless=False, cylindrical=False, **binning):
+    """Returns a dict: power (n_chunks, ...), k or kperp / kpar, counts, chunk_starts, redshifts."""
+    lc = np.asarray(lightcone)
+    nx, ny, ns = lc.shape
+    n = nx if chunk_length is None else int(chunk_length)
+    starts = np.arange(0, ns - n + 1, n) if chunk_starts is None else np.asarray(chunk_starts, np.int64)
+    L = (nx * cell_size, ny * cell_size, n * cell_size)
+    d2 = binning.pop("deltax2", None)
+    res = {"chunk_starts": starts, "power": []}
+    for s in starts:
+        kw = dict(binning, return_counts=True)
+        if d2 is not None:
+            kw["deltax2"] = np.asarray(d2)[:, :, s:s + n]
+        if cylindrical:
+            p, kp, kz, c = get_cylindrical_power(lc[:, :, s:s + n], L, **kw)
+            if dimensionless:
+                p = p * (kp[:, None] ** 2 + kz[None, :] ** 2) ** 1.5 / (2 * np.pi**2)
+            res.update(kperp=kp, kpar=kz, counts=c)
+        else:
+            p, k, c = get_power(lc[:, :, s:s + n], L, **kw)
+            if dimensionless:
+                kk = k if binning.get("bin_ave", True) else get_power(lc[:, :, s:s + n], L, **dict(kw, bin_ave=True))[1]
+                p = p * kk**3 / (2 * np.pi**2)
+            res.update(k=k, counts=c)
+        res["power"].append(p)
+    res["power"] = np.array(res["power"])
+    if redshifts is not None:
+        z = np.asarray(redshifts, np.float64)
+        res["redshifts"] = 0.5 * (z[starts + (n - 1) // 2] + z[starts + n // 2])
+    return res
