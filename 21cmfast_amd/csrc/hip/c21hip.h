@@ -752,13 +752,16 @@ typedef struct c21hip_power_tabs { /* device pointers the driver fills (power_dr
     int ignore_zero_mode, ignore_kpar_zero;
 } c21hip_power_tabs;
 size_t c21hip_power_lds_bytes(int n_local, int cylindrical);
-/* in[offsets[b] + (i ny + j) row_pitch + l] -> padded[b][i][j][l] for l < nz; *bad |= 1 on a non-finite value */
+/* in[offsets[b] + (i ny + j) row_pitch + l] - mean[b] -> padded[b][i][j][l] for l < nz; *bad |= 1 on a non-finite
+ * value.  mean[n_batch] (written here: each box's mean rounded to fp32) goes on to c21hip_power_bin; rowsum:
+ * n_batch nx ny doubles of scratch */
 int c21hip_power_pack(const float *in, float *padded, int nx, int ny, int nz, long long row_pitch,
-                      const long long *offsets, int n_batch, int *bad, void *stream);
+                      const long long *offsets, int n_batch, double *rowsum, double *mean, int *bad, void *stream);
 /* one pass over the half spectra complex[n_batch][nx][ny][nz/2+1] (spec2: cross power, or NULL) into
- * partials[n_batch][n_wg][n_local][3 or 4] */
+ * partials[n_batch][n_wg][n_local][3 or 4]; mean1 / mean2: the means the pack took out of each box */
 int c21hip_power_bin(const float *spec1, const float *spec2, int nx, int ny, int nz, int n_batch,
-                     int cylindrical, const c21hip_power_tabs *t, double *partials, int *bad, void *stream);
+                     int cylindrical, const c21hip_power_tabs *t, const double *mean1, const double *mean2,
+                     double *partials, int *bad, void *stream);
 /* partials -> totals[n_batch][n_groups n_local][3 or 4] -> means (device outputs) */
 int c21hip_power_finish(const double *partials, double *totals, int n_batch, int cylindrical,
                         const c21hip_power_tabs *t, double scale, double *power, double *kmean,

@@ -3,7 +3,11 @@
 //
 // Three steps around the forward transform (fft.hip, rocFFT):
 //   pack    one wave per (batch, x, y) row: the field (or one chunk of a lightcone) into the padded r2c layout
-//           float[nx][ny][2(nz/2+1)], every value checked for finiteness;
+//           float[nx][ny][2(nz/2+1)], every value checked for finiteness, less the box's mean.  An fp32 transform
+//           spreads the round-off of its largest mode, the mean's, over the lines through k = 0: with a mean as
+//           large as the fluctuations that is a few 1e-5 of the power of the modes beside the axes at 10^7 cells.
+//           The mean (fp64 row sums, a fixed tree; rounded to fp32 so that the subtraction is a plain fp32
+//           one) goes back onto the k = 0 mode where it is read, N mean, in fp64;
 //   bin     one pass over the half spectrum complex[nx][ny][nz/2+1].  A mode with 0 < kz < nz/2 stands for
 //           itself and its conjugate (weight 2), the planes kz = 0 and kz = nz/2 (even nz) for themselves, so
 //           the counts are those of the full grid.  |k| = sqrt((kx^2 + ky^2) + kz^2) in fp64 from the per-axis
@@ -43,24 +47,63 @@ int launch_status(const char *what) {
     return 0;
 }
 
-// one wave per row (b, i, j): in[offsets[b] + (i ny + j) row_pitch + l] -> padded[b][i][j][l], l < nz
+// one wave per row (b, i, j): in[offsets[b] + (i ny + j) row_pitch + l] - mean[b] -> padded[b][i][j][l], l < nz
 __global__ __launch_bounds__(kBlock) void power_pack_kernel(const float *__restrict__ in, float *__restrict__ padded,
                                                             long long rows_per_batch, long long n_rows, int nz,
                                                             long long row_pitch,
-                                                            const long long *__restrict__ offsets, int *bad) {
+                                                            const long long *__restrict__ offsets,
+                                                            const double *__restrict__ mean, int *bad) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (row >= n_rows) return;
     const long long b = row / rows_per_batch, r = row - b * rows_per_batch;
     const float *src = in + offsets[b] + r * row_pitch;
+    const float m = (float)mean[b];
     float *dst = padded + row * (2 * ((long long)nz / 2 + 1));
     int nonfinite = 0;
     for (int l = lane; l < nz; l += 64) {
         const float v = src[l];
         nonfinite |= !isfinite(v);
-        dst[l] = v;
+        dst[l] = v - m;
     }
     if (nonfinite) atomicOr(bad, 1);
+}
+
+// rowsum[row] = the fp64 sum of row (b, i, j), lanes strided then a fixed shuffle tree: one wave per row
+__global__ __launch_bounds__(kBlock) void power_rowsum_kernel(const float *__restrict__ in, double *__restrict__ rowsum,
+                                                              long long rows_per_batch, long long n_rows, int nz,
+                                                              long long row_pitch,
+                                                              const long long *__restrict__ offsets) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (row >= n_rows) return;  // the whole wave
+    const long long b = row / rows_per_batch, r = row - b * rows_per_batch;
+    const float *src = in + offsets[b] + r * row_pitch;
+    double s = 0.0;
+    for (int l = lane; l < nz; l += 64) s += (double)src[l];
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+    if (lane == 0) rowsum[row] = s;
+}
+
+// mean[b] = the mean of box b rounded to fp32 (held as a double): one workgroup per box, thread t sums rows t,
+// t + 256, .. in order, then a fixed tree
+__global__ __launch_bounds__(kBlock) void power_boxmean_kernel(const double *__restrict__ rowsum,
+                                                               double *__restrict__ mean, long long rows_per_batch,
+                                                               double inv_cells) {
+    __shared__ double red[kBlock];
+    const double *src = rowsum + (long long)blockIdx.x * rows_per_batch;
+    double s = 0.0;
+    for (long long r = threadIdx.x; r < rows_per_batch; r += kBlock) s += src[r];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float m = (float)(red[0] * inv_cells);
+        mean[blockIdx.x] = isfinite(m) ? (double)m : 0.0;  // a non-finite box is reported by the pack
+    }
 }
 
 // NV accumulators per bin: sum w P, sum w k (|k| or k_perp), [sum w k_par], sum w
@@ -68,6 +111,8 @@ template <bool CYL, bool CROSS>
 __global__ __launch_bounds__(kBlock) void power_bin_kernel(const float2 *__restrict__ s1,
                                                            const float2 *__restrict__ s2, long long batch_c,
                                                            int ny, int nz, c21hip_power_tabs t,
+                                                           const double *__restrict__ mean1,
+                                                           const double *__restrict__ mean2, double n_cells,
                                                            double *__restrict__ partials, int *bad) {
     constexpr int NV = CYL ? 4 : 3;
     extern __shared__ double lds[];
@@ -99,13 +144,16 @@ __global__ __launch_bounds__(kBlock) void power_bin_kernel(const float2 *__restr
             const int row = t.rows[r0 + rl];
             const int i = row / ny, j = row - i * ny;
             const float2 a = f1[(long long)row * nh + l];
+            const bool zero_mode = row == 0 && l == 0;  // the mean the pack took out comes back here
+            const double ax = zero_mode ? (double)a.x + mean1[b] * n_cells : (double)a.x;
             double q;
             if (CROSS) {
                 const float2 c = f2[(long long)row * nh + l];
                 nonfinite |= !(isfinite(c.x) && isfinite(c.y));
-                q = (double)a.x * (double)c.x + (double)a.y * (double)c.y;
+                const double cx = zero_mode ? (double)c.x + mean2[b] * n_cells : (double)c.x;
+                q = ax * cx + (double)a.y * (double)c.y;
             } else {
-                q = (double)a.x * (double)a.x + (double)a.y * (double)a.y;
+                q = ax * ax + (double)a.y * (double)a.y;
             }
             nonfinite |= !(isfinite(a.x) && isfinite(a.y));
             const double kx = t.kx[i], ky = t.ky[j], kz = t.kz[l];
@@ -259,21 +307,26 @@ extern "C" size_t c21hip_power_lds_bytes(int n_local, int cylindrical) {
 }
 
 extern "C" int c21hip_power_pack(const float *in, float *padded, int nx, int ny, int nz, long long row_pitch,
-                                 const long long *offsets, int n_batch, int *bad, void *stream) {
+                                 const long long *offsets, int n_batch, double *rowsum, double *mean, int *bad,
+                                 void *stream) {
     if (nx < 1 || ny < 1 || nz < 1 || n_batch < 1 || row_pitch < nz) {
         c21hip_set_error("power pack: bad launch shape");
         return C21CM_VALUE_ERROR;
     }
     const long long per = (long long)nx * ny, rows = per * n_batch;
     const long long blocks = (rows + kWaves - 1) / kWaves;
+    hipLaunchKernelGGL(power_rowsum_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, in, rowsum,
+                       per, rows, nz, row_pitch, offsets);
+    hipLaunchKernelGGL(power_boxmean_kernel, dim3((unsigned)n_batch), dim3(kBlock), 0, (hipStream_t)stream, rowsum,
+                       mean, per, 1.0 / ((double)per * (double)nz));
     hipLaunchKernelGGL(power_pack_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, in, padded,
-                       per, rows, nz, row_pitch, offsets, bad);
+                       per, rows, nz, row_pitch, offsets, mean, bad);
     return launch_status("power pack");
 }
 
 extern "C" int c21hip_power_bin(const float *spec1, const float *spec2, int nx, int ny, int nz, int n_batch,
-                                int cylindrical, const c21hip_power_tabs *t, double *partials, int *bad,
-                                void *stream) {
+                                int cylindrical, const c21hip_power_tabs *t, const double *mean1,
+                                const double *mean2, double *partials, int *bad, void *stream) {
     const size_t lds = c21hip_power_lds_bytes(t->n_local, cylindrical);
     if (nx < 2 || ny < 2 || nz < 2 || n_batch < 1 || t->n_local < 1 || lds > C21HIP_POWER_MAX_LDS ||
         n_batch > 65535) {
@@ -297,12 +350,13 @@ extern "C" int c21hip_power_bin(const float *spec1, const float *spec2, int nx, 
     const float2 *a = (const float2 *)spec1, *c = (const float2 *)spec2;
     const dim3 grid((unsigned)t->n_wg, (unsigned)n_batch);
     const hipStream_t s = (hipStream_t)stream;
+    const double n_cells = (double)nx * (double)ny * (double)nz;
     if (cylindrical) {
-        if (c) hipLaunchKernelGGL((power_bin_kernel<true, true>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, partials, bad);
-        else hipLaunchKernelGGL((power_bin_kernel<true, false>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, partials, bad);
+        if (c) hipLaunchKernelGGL((power_bin_kernel<true, true>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
+        else hipLaunchKernelGGL((power_bin_kernel<true, false>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
     } else {
-        if (c) hipLaunchKernelGGL((power_bin_kernel<false, true>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, partials, bad);
-        else hipLaunchKernelGGL((power_bin_kernel<false, false>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, partials, bad);
+        if (c) hipLaunchKernelGGL((power_bin_kernel<false, true>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
+        else hipLaunchKernelGGL((power_bin_kernel<false, false>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
     }
     return launch_status("power bin");
 }

@@ -197,10 +197,12 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
     const size_t n_dest = (size_t)n_groups * n_local, n_k = cyl ? (size_t)n_groups + n_local : (size_t)n_local;
     const size_t part_dbl = (size_t)n_batch * n_wg * n_local * NV, tot_dbl = (size_t)n_batch * n_dest * NV;
     const size_t out_dbl = (size_t)n_batch * (2 * n_dest + n_k); /* power, counts (int64), kmean */
+    /* the box means the pack takes out (per field), and the row sums they come from */
+    const size_t mean_dbl = (size_t)n_fields * (size_t)n_batch, rowsum_dbl = (size_t)n_rows * (size_t)n_batch;
 
     unsigned char *d_tab = (unsigned char *)c21hip_ws(WS_PW_TAB, tab_bytes);
     float *d_pad = (float *)c21hip_ws(WS_PW_PAD, sizeof(float) * pad_floats * n_fields);
-    double *d_sums = (double *)c21hip_ws(WS_PW_SUMS, sizeof(double) * (part_dbl + tot_dbl + out_dbl));
+    double *d_sums = (double *)c21hip_ws(WS_PW_SUMS, sizeof(double) * (part_dbl + tot_dbl + out_dbl + mean_dbl + rowsum_dbl));
     int *d_bad = (int *)c21hip_ws(WS_PW_FLAG, sizeof(int));
     if (!d_tab || !d_pad || !d_sums || !d_bad) {
         status = C21CM_MEMORY_ALLOC_ERROR;
@@ -224,6 +226,7 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
     t.ignore_zero_mode = bins->ignore_zero_mode != 0;
     t.ignore_kpar_zero = bins->ignore_kpar_zero != 0;
 
+    double *d_mean = d_sums + part_dbl + tot_dbl + out_dbl, *d_rowsum = d_mean + mean_dbl;
     const float *src[2] = {field, field2};
     int n_host = 0;
     for (int q = 0; q < n_fields; ++q) n_host += !c21hip_is_device_ptr(src[q]);
@@ -243,14 +246,15 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
             in = d;
         }
         float *pad = d_pad + (size_t)q * pad_floats;
-        TRY(c21hip_power_pack(in, pad, nx, ny, nz, row_pitch, d_off, n_batch, d_bad, stream));
+        TRY(c21hip_power_pack(in, pad, nx, ny, nz, row_pitch, d_off, n_batch, d_rowsum, d_mean + (size_t)q * n_batch,
+                              d_bad, stream));
         TRY(c21hip_fft_r2c_batched(pad, nx, ny, nz, n_batch, stream));
     }
     double *d_part = d_sums, *d_tot = d_part + part_dbl, *d_power = d_tot + tot_dbl;
     long long *d_counts = (long long *)(d_power + (size_t)n_batch * n_dest);
     double *d_kmean = (double *)(d_counts + (size_t)n_batch * n_dest);
-    TRY(c21hip_power_bin(d_pad, field2 ? d_pad + pad_floats : NULL, nx, ny, nz, n_batch, cyl, &t, d_part, d_bad,
-                         stream));
+    TRY(c21hip_power_bin(d_pad, field2 ? d_pad + pad_floats : NULL, nx, ny, nz, n_batch, cyl, &t, d_mean,
+                         field2 ? d_mean + n_batch : NULL, d_part, d_bad, stream));
     /* F = (V/N) DFT: P = |F|^2 / V = (V/N)^2 |DFT|^2 / V */
     const double vol = Lx * Ly * Lz, c = vol / ((double)nx * (double)ny * (double)nz);
     TRY(c21hip_power_finish(d_part, d_tot, n_batch, cyl, &t, c * c / vol, d_power, d_kmean, d_counts, stream));

@@ -27,6 +27,8 @@ down here:
 
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 
@@ -34,10 +36,23 @@ def _lengths(boxlength, dim):
     return [float(boxlength)] * dim if np.isscalar(boxlength) else [float(x) for x in boxlength]
 
 
-def _grids(shape, boxlength):
-    L = _lengths(boxlength, len(shape))
+@functools.lru_cache(maxsize=1)
+def _cached_grids(shape, L):
     freq = [np.fft.fftfreq(n, d=l / n) * 2.0 * np.pi for n, l in zip(shape, L)]
-    return L, np.meshgrid(*freq, indexing="ij")
+    return np.meshgrid(*freq, indexing="ij")
+
+
+def _grids(shape, boxlength):
+    """(lengths, [kx, ky, kz] on the full grid); the grids of the last (shape, lengths) are kept, so
+    binning one box in several ways builds them once (read-only: nothing here writes into them)."""
+    L = _lengths(boxlength, len(shape))
+    return L, _cached_grids(tuple(int(n) for n in shape), tuple(L))
+
+
+def spectrum(field, boxlength, deltax2=None):
+    """P on the full Fourier grid, fp64: what ``get_power`` / ``get_cylindrical_power`` bin.  Pass it back
+    as their ``spectrum`` to bin one box in several ways without transforming it again."""
+    return _spectrum(field, boxlength, deltax2)
 
 
 def _spectrum(field, boxlength, deltax2):
@@ -62,24 +77,37 @@ def _getbins(bins, coord, log, upto_boxlen):
     return np.linspace(coord.min(), mx, int(bins) + 1)
 
 
+def _bin_sums(index, n_out, weights_list):
+    """``np.bincount(index, weights=w, minlength=n_out)`` for every w, and the counts, with each bin summed
+    pairwise (``np.sum`` of its members) instead of one after the other: a bin of millions of modes keeps a
+    rounding error of a few ulp, where the running sum of bincount loses about 1e-12 of it."""
+    counts = np.bincount(index, minlength=n_out)
+    order = np.argsort(index.astype(np.int16) if n_out < 2**15 else index, kind="stable")
+    ends = np.cumsum(counts)
+    sums = []
+    for w in weights_list:
+        ws = w[order]
+        sums.append(np.array([ws[a:b].sum() for a, b in zip(ends - counts, ends)]))
+    return sums, counts
+
+
 def _bin(x, weights_list, keep, edges):
     indx = np.digitize(x[keep], edges)
-    counts = np.bincount(indx, minlength=len(edges) + 1)[1:-1]
-    out = []
+    sums, counts = _bin_sums(indx, len(edges) + 1, [w[keep] for w in weights_list])
+    counts = counts[1:-1]
     with np.errstate(invalid="ignore", divide="ignore"):
-        for w in weights_list:
-            out.append(np.bincount(indx, weights=w[keep], minlength=len(edges) + 1)[1:-1] / counts)
+        out = [s[1:-1] / counts for s in sums]
     return out, counts
 
 
 def get_power(field, boxlength, *, deltax2=None, bins=None, log_bins=False, ignore_zero_mode=False,
               bins_upto_boxlen=True, ignore_kperp_zero=False, ignore_kpar_zero=False, bin_ave=True,
-              return_counts=False):
+              return_counts=False, spectrum=None):
     field = np.asarray(field)
     N = field.shape
     _, (kx, ky, kz) = _grids(N, boxlength)
     kmag = np.sqrt(sum(g * g for g in (kx, ky, kz)))
-    P = _spectrum(field, boxlength, deltax2)
+    P = _spectrum(field, boxlength, deltax2) if spectrum is None else spectrum
     if bins is None:
         bins = int(np.prod(N) ** (1.0 / field.ndim) / 2.2)
     edges = _getbins(bins, kmag, log_bins, bins_upto_boxlen)
@@ -96,13 +124,13 @@ def get_power(field, boxlength, *, deltax2=None, bins=None, log_bins=False, igno
 
 
 def get_cylindrical_power(field, boxlength, *, deltax2=None, kperp_bins=None, kpar_bins=None, log_bins=False,
-                          ignore_zero_mode=False, return_counts=False):
+                          ignore_zero_mode=False, return_counts=False, spectrum=None):
     field = np.asarray(field)
     N = field.shape
     _, (kx, ky, kz) = _grids(N, boxlength)
     kperp = np.sqrt(kx * kx + ky * ky)
     kpar = np.abs(kz)
-    P = _spectrum(field, boxlength, deltax2)
+    P = _spectrum(field, boxlength, deltax2) if spectrum is None else spectrum
     if kperp_bins is None:
         kperp_bins = int(np.prod(N[:2]) ** (1.0 / 2) / 2.2)
     if kpar_bins is None:
@@ -117,11 +145,11 @@ def get_cylindrical_power(field, boxlength, *, deltax2=None, kperp_bins=None, kp
     keep &= (ip >= 0) & (ip < len(ep) - 1) & (iz >= 0) & (iz < len(ez) - 1)
     flat = (ip * (len(ez) - 1) + iz)[keep]
     nb = (len(ep) - 1) * (len(ez) - 1)
-    counts = np.bincount(flat, minlength=nb).reshape(len(ep) - 1, len(ez) - 1)
+    (power, sp, sz), counts = _bin_sums(flat, nb, [P[keep], kperp[keep], kpar[keep]])
+    counts = counts.reshape(len(ep) - 1, len(ez) - 1)
+    sp, sz = sp.reshape(counts.shape), sz.reshape(counts.shape)
     with np.errstate(invalid="ignore", divide="ignore"):
-        power = np.bincount(flat, weights=P[keep], minlength=nb).reshape(counts.shape) / counts
-        sp = np.bincount(flat, weights=kperp[keep], minlength=nb).reshape(counts.shape)
-        sz = np.bincount(flat, weights=kpar[keep], minlength=nb).reshape(counts.shape)
+        power = power.reshape(counts.shape) / counts
         kp = sp.sum(axis=1) / counts.sum(axis=1)
         kz_av = sz.sum(axis=0) / counts.sum(axis=0)
     out = (power, kp, kz_av)

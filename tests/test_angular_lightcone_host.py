@@ -137,6 +137,18 @@ def test_prefilter_restatement_is_scipy_grid_wrap(order, shape):
     np.testing.assert_allclose(AR.periodic_prefilter(box, order), want, atol=1e-14 * np.abs(want).max())
 
 
+@pytest.mark.parametrize("order", [3, 5])
+@pytest.mark.parametrize("shape", [(32, 32, 32), (50, 50, 50), (64, 64, 64), (40, 64, 96), (128, 128, 128)],
+                         ids=lambda s: "x".join(map(str, s)))
+def test_prefilter_restatement_is_scipy_grid_wrap_at_production_sizes(order, shape):
+    """Lines of 32 cells and more, where the device truncates its start sums (the horizon is 32 cells for the
+    cubic pole, 50 and 14 for the quintic ones) and the restatement, which sums the whole period, does not:
+    the GPU tests compare against either, so the two are held together here."""
+    box = np.random.default_rng(sum(shape) + order).standard_normal(shape, dtype=np.float32)
+    want = ndimage.spline_filter(box.astype(np.float64), order=order, mode="grid-wrap")
+    np.testing.assert_allclose(AR.periodic_prefilter(box, order), want, rtol=0, atol=1e-12 * np.abs(want).max())
+
+
 def small_inputs(**kw):
     return D.Inputs(HII_DIM=16, DIM=32, BOX_LEN=32.0, SOURCE_MODEL=1, **kw)
 

@@ -71,6 +71,25 @@ def test_reference_options_are_self_consistent():
     assert P.shape == cc.shape == (len(kp), len(kz))
 
 
+def test_a_given_spectrum_is_binned_as_the_field_is():
+    """``spectrum=`` (one transform, several binnings: the large-shape GPU tests) changes no number, and the
+    wavenumber grids kept from the last call follow a change of shape or lengths."""
+    rng = np.random.default_rng(8)
+    f, g = rng.standard_normal((12, 14, 17)), rng.standard_normal((12, 14, 17))
+    for L in ((60.0, 50.0, 70.0), 55.0):
+        for d2 in (None, g):
+            P = PR.spectrum(f, L, d2)
+            for opts in (dict(), dict(log_bins=True, ignore_kperp_zero=True), dict(bins=5, bin_ave=False)):
+                a = PR.get_power(f, L, deltax2=d2, return_counts=True, **opts)
+                b = PR.get_power(f, L, spectrum=P, return_counts=True, **opts)
+                assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
+            a = PR.get_cylindrical_power(f, L, deltax2=d2, return_counts=True)
+            b = PR.get_cylindrical_power(f, L, spectrum=P, return_counts=True)
+            assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
+    small = PR.get_power(f[:8, :8, :8], 55.0)
+    assert len(small[0]) != len(PR.get_power(f, 55.0)[0])
+
+
 def test_argument_errors():
     f = np.zeros((8, 8, 8), np.float32)
     with pytest.raises(ValueError, match="3-D"):
