@@ -333,7 +333,6 @@ typedef struct {
     double *scalars;
     double *partials; /* >= max(C21HIP_PARTIALS, nx*ny/8) doubles */
     float *table_dev;
-    unsigned char *mask; /* internal first-crossing mask of the fused single-GPU path */
     int fused;           /* fused pass Z + barrier available for radius index > 0 */
     /* deferred f_coll sums of the fused radii: partials of radius R at def_partials + R *
      * def_stride, radii def_first, def_first - def_step, ... (def_count of them) */
@@ -402,12 +401,12 @@ static int r0_direct(void);
  * spectrum, 8 ... which is N_rec, 16 fourth spectrum (x_e + N_rec), 32 two radii per sweep */
 static int g_loop_flags;
 int c21cm_ionize_last_loop_flags(void) { return g_loop_flags; }
-static int g_single_pass; /* set by c21cm_ionize_grids around its ctx_setup: not a shard phase */
-static int g_rc_phase;    /* set by the (first crossing, Gamma_12) shard phases around their ctx_setup */
 
+/* fused_rc_ok: the caller can finish what the fused recombination loop leaves (first crossings with
+ * Gamma_12): the single pass and the rc shard phases; the other shard phases keep such runs off it */
 static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedField *pf,
                      const IonizedBox *prev, const TsBox *ts, const HaloBox *halos,
-                     IonizedBox *box, int need_outputs, void *stream) {
+                     IonizedBox *box, int need_outputs, int fused_rc_ok, void *stream) {
     int status = 0;
     memset(c, 0, sizeof(*c));
     c->s = s;
@@ -485,11 +484,11 @@ static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedFiel
      * b alone).  C21CM_RECOMB_FUSED=0: the unfused per-radius sequence. */
     c->fused_rc = 0;
     /* (round 4, late: CELL_RECOMB = false without an x_e grid as well -- N_rec filtered at the radius is
-     * the barrier kernel's third line where the x_e grid would be; single pass only.
+     * the barrier kernel's third line where the x_e grid would be; single pass and rc shard phases.
      * C21CM_RECOMB_FUSED_NREC=0 keeps such runs on the unfused sequence) */
     const char *e_nr = getenv("C21CM_RECOMB_FUSED_NREC");
     const int nrec_ok = s->cell_recomb ||
-                        (c->inhomo && (g_single_pass || g_rc_phase) && !(e_nr && e_nr[0] == '0') &&
+                        (c->inhomo && fused_rc_ok && !(e_nr && e_nr[0] == '0') &&
                          (s->use_ts_fluct ? c21hip_z_ionise_recomb_xe_nrec_supported(c->nx, c->ny, c->nz)
                                           : c21hip_z_ionise_recomb_xe_supported(c->nx, c->ny, c->nz)));
     c->x3_on = c->x3_nrec = 0;
@@ -499,7 +498,7 @@ static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedFiel
     c->cur_x4 = NULL;
     if (c->native && c->lagrangian && c->recomb && nrec_ok &&
         !s->use_mini_halos && !s->ionise_entire_sphere && s->r_lowest == 0 &&
-        (g_single_pass || g_rc_phase)) {
+        fused_rc_ok) {
         /* (round 4: with the x_e grid of a spin-temperature run too -- a third line of the barrier
          * kernel; C21CM_RECOMB_FUSED_TS=0 keeps such runs on the unfused sequence) */
         const char *e = getenv("C21CM_RECOMB_FUSED"), *et = getenv("C21CM_RECOMB_FUSED_TS");
@@ -1113,8 +1112,6 @@ done:
     return status;
 }
 
-/* One filter radius: IonisationBox.c:1546-1580.  first_cross != NULL = shard mode.
- * next_R: the radius index this process handles after R_ct (-1: none / unknown). */
 /* the two dense x_e(R) buffers of the Eulerian mask path */
 static int eul_xe_buffers(ion_ctx *c) {
     if (c->eul_xe[0] && c->eul_xe[1]) return 0;
@@ -1312,9 +1309,8 @@ static int eul_band_after(ion_ctx *c, int R_ct, int next_R, int banded, int sig_
                           int n_part, double *sum_dev) {
     int status = 0;
     const c21cm_ionize_spec *s = c->s;
-    const char *e_rel = getenv("C21CM_EUL_BAND_MINREL"), *e_shift = getenv("C21CM_EUL_BAND_SHIFT");
-    double min_rel = e_rel ? atof(e_rel) : 0.005;
-    if (!(min_rel >= 0.)) min_rel = 0.005;
+    const char *e_shift = getenv("C21CM_EUL_BAND_SHIFT");
+    const double min_rel = 0.005; /* the least relative half-width of a band */
     const double shift = e_shift ? atof(e_shift) : 0.; /* test hook: a prediction off by this fraction */
     const int h1 = c->band_h1, h2 = c->band_h2;
     c->band_hist[R_ct][0] = (short)h1, c->band_hist[R_ct][1] = (short)h2, c->band_hist[R_ct][2] = (short)c->band_hn;
@@ -1333,10 +1329,7 @@ static int eul_band_after(ion_ctx *c, int R_ct, int next_R, int banded, int sig_
     const char *e_q = getenv("C21CM_EUL_BAND_QUAD");
     const int quad = h1 >= 0 && h2 >= 0 && next_R >= 1 && fabs(t_next - 1.) < 1e-6 && fabs(t_cur - 1.) < 1e-6 &&
                      !(e_q && e_q[0] == '0');
-    const char *e_sb = getenv("C21CM_EUL_SUMBAND"); /* 0: c21hip_reduce_sum's own launches (A/B) */
-    const int split = partials && e_sb && e_sb[0] == '0';
-    if (split) TRY(c21hip_reduce_sum(partials, n_part, sum_dev, c->stream));
-    TRY(c21hip_eul_band(split ? NULL : partials, n_part, sum_dev, (double)c->ntot, s->mass_dep_zeta,
+    TRY(c21hip_eul_band(partials, n_part, sum_dev, (double)c->ntot, s->mass_dep_zeta,
                         s->f_limit_acg, c->scalars + SC_MEANS, R_ct, h1, h2, t_cur, t_next,
                         predict_next ? next_R : -1, banded, s->fix_mean, s->mean_f_coll, s->ion_eff_factor,
                         min_rel, shift, c->scalars + SC_BAND, c->scalars + SC_BANDX,
@@ -1406,6 +1399,9 @@ static int eul_filter_density_xe(ion_ctx *c, int R_ct, int next_R, float *dst, f
                                    c->ny, c->nz, s->box_len, s->box_len_z, R, R_ct > 0, 0, 0, c->stream);
 }
 
+/* One filter radius: IonisationBox.c:1546-1580.  first_cross != NULL: the barrier goes into that
+ * first-crossing grid (radii > 0 of the mask loops and the shard phases) instead of the outputs.
+ * next_R: the radius index this process handles after R_ct (-1: none / unknown). */
 static int one_radius(ion_ctx *c, int R_ct, unsigned char *first_cross, int next_R) {
     int status = 0;
     const c21cm_ionize_spec *s = c->s;
@@ -2044,6 +2040,11 @@ done:
     return status;
 }
 
+/* the f_coll grid means of the radii, as the scalar block holds them */
+static void report_grid_means(c21cm_ionize_report *report, const double *means, int n_radii) {
+    for (int r = 0; r < n_radii; r++) report->f_coll_grid_mean[r] = means[r];
+}
+
 /* post-loop + result collection: IonisationBox.c:1589-1628 */
 static int postloop(ion_ctx *c, IonizedBox *box, c21cm_ionize_report *report) {
     int status = 0;
@@ -2127,7 +2128,7 @@ static int postloop(ion_ctx *c, IonizedBox *box, c21cm_ionize_report *report) {
                                               : (s->fix_mean ? s->mean_f_coll_mini : means_m[last]);
         box->mean_f_coll_MINI = mean_m_out;
         if (report) {
-            for (int r = 0; r < s->n_radii; r++) report->f_coll_grid_mean[r] = means[r];
+            report_grid_means(report, means, s->n_radii);
             report->global_xH = global_xH;
             report->mean_f_coll_out = mean_out;
             if (c->mini)
@@ -2185,19 +2186,20 @@ static int eul_r0_fused(const ion_ctx *c) {
 }
 
 /* Eulerian source models (and every other loop off the fused path) on the native passes: the density
- * (and x_e) windows of the radii first, first - step, ... evaluated inside pass X (top-hat / sharp-k
- * HII_FILTER), no window tables.  The single pass AND the shard phases call this, so that a rank's
- * radii see the very arithmetic of the single pass: the evaluated windows (quintic Hermite in float)
+ * (and x_e) windows evaluated inside pass X (top-hat / sharp-k HII_FILTER), no window tables.  Always for
+ * the WHOLE ladder, in the single pass and in every shard phase (a rank does not prepare its share alone:
+ * even the node-table length follows from the set of radii), so that a rank's radii see the very
+ * arithmetic of the single pass: the evaluated windows (quintic Hermite in float)
  * and the table fallback (fp64, rounded) differ by an ulp or two of W, which is enough to flip a cell
  * within float noise of a barrier -- the sharded result is only bit-identical by construction if both
  * use the same one (round 4: the shard phases did not, and test_gpu_config5's comparison failed on about
  * one box in three). */
-static int native_wev_prepare(ion_ctx *c, int first, int step, void *stream) {
+static int native_wev_prepare(ion_ctx *c) {
     const c21cm_ionize_spec *spec = c->s;
     if (!c->native || c->fused) return 0;
     float radii[C21CM_MAX_RADII];
     int n = 0, on = 0;
-    for (int R_ct = first; R_ct >= 1 && R_ct >= spec->r_lowest && n < C21CM_MAX_RADII; R_ct -= step)
+    for (int R_ct = spec->n_radii - 1; R_ct >= 1 && R_ct >= spec->r_lowest && n < C21CM_MAX_RADII; R_ct--)
         radii[n++] = (float)spec->R[R_ct];
     if (n == 0) return 0;
     /* one filtered grid: two radii per pass-X sweep where two line tiles fit the LDS (C21CM_EUL_PAIR=0: one) */
@@ -2205,11 +2207,121 @@ static int native_wev_prepare(ion_ctx *c, int first, int step, void *stream) {
     const int pair = c->eul_mask && !(ep && ep[0] == '0') && c21hip_pair_sweep_supported(c->nx);
     const int st = c21hip_wev_prepare(spec->hii_filter, 0.f, spec->hii_filter, 0.f, spec->use_ts_fluct ? 2 : 1,
                                       radii, n, c->nx, c->ny, c->nz, spec->box_len, spec->box_len_z, pair, &on,
-                                      stream);
+                                      c->stream);
     c->wev_pair = !st && on && pair;
     return st;
 }
 
+/* Stream timestamps around the phases of an entry point: the report's timings. */
+typedef struct {
+    void *ev[4];
+    int n, marked;
+} phase_clock;
+
+static int clock_start(phase_clock *k, int n, void *stream) {
+    for (k->n = 0; k->n < n; k->n++) k->ev[k->n] = c21hip_event_create();
+    k->marked = 1;
+    return c21hip_event_record(k->ev[0], stream);
+}
+
+static int clock_mark(phase_clock *k, void *stream) { return c21hip_event_record(k->ev[k->marked++], stream); }
+
+static double clock_ms(const phase_clock *k, int i) { return c21hip_event_elapsed_ms(k->ev[i], k->ev[i + 1]); }
+
+static void clock_free(phase_clock *k) {
+    while (k->n > 0) c21hip_event_destroy(k->ev[--k->n]);
+}
+
+/* The radii first, first - step, ... down to max(1, r_lowest) into the first-crossing grid `mask`: the
+ * whole ladder of the single pass (n_radii - 1, 1), a rank's share of it in the shard phases
+ * (n_radii - 1 - rank, world).  One of three routes: the fused loop (Lagrangian grids), the pipelined
+ * table loop (Eulerian models with a per-radius table) or one_radius per radius; the last two rerun the
+ * radii at and below a missed band on the dense sweeps.  On return every barrier has been applied to
+ * `mask`; the f_coll sums of the fused radii are still deferred (flush_deferred).
+ * after: the radius index this call goes on with once the ladder is done -- 0 where the single pass'
+ * cell-scale radius follows, -1 where nothing does.  It is the next_R hint of the ladder's last radius.
+ * It also tells eul_flush_pending whether the ladder's last f_coll grid is the call's last: only with
+ * after < 0 does no further radius write the f_coll grid, and only then is the second f_coll buffer
+ * copied into box->unnormalised_nion.  A hint never names a radius below the floor: nothing is
+ * prefetched, paired or predicted for a radius that does not run.
+ * The pending barrier and the bands belong to the per-radius route alone: on the fused and table routes
+ * eul_pend stays < 0 and, once the table route's own eul_band_finish has run, band_used is 0, so a
+ * further eul_flush_pending / eul_band_finish before index 0 would launch nothing and is not made. */
+static int radii_ladder(ion_ctx *c, int first, int step, unsigned char *mask, int after) {
+    int status = 0;
+    const c21cm_ionize_spec *s = c->s;
+    const int lowest = s->r_lowest > 1 ? s->r_lowest : 1;
+    if (c->fused) return fused_loop(c, first, step, lowest, mask);
+    if (c->eul_mask && s->fcoll_mode != C21CM_FCOLL_ERFC && s->fcoll_mode != C21CM_FCOLL_NODES) {
+        int radii[C21CM_MAX_RADII], n = 0, redo = 0;
+        for (int R_ct = first; R_ct >= lowest; R_ct -= step) radii[n++] = R_ct;
+        TRY(eul_table_loop(c, radii, n, mask));
+        TRY(eul_band_finish(c, mask, &redo)); /* banded barrier: markers settled, bands checked */
+        if (redo) {
+            int m = 0;
+            for (int i = 0; i < n; i++)
+                if (radii[i] <= redo) radii[m++] = radii[i];
+            TRY(eul_table_loop(c, radii, m, mask));
+        }
+        goto done;
+    }
+    for (int attempt = 0, from = first; attempt < 2; attempt++) {
+        int redo = 0;
+        for (int R_ct = first; R_ct >= lowest; R_ct -= step) {
+            if (R_ct > from) continue; /* second attempt: from the radius whose band missed */
+            TRY(one_radius(c, R_ct, mask, R_ct - step >= lowest ? R_ct - step : after));
+        }
+        TRY(eul_flush_pending(c, after < 0)); /* the last radius' barrier of the closed-form loop */
+        TRY(eul_band_finish(c, mask, &redo));
+        if (!redo) break;
+        from = redo;
+    }
+done:
+    return status;
+}
+
+/* First crossings of the radii > 0 -> x_HI and z_reion, then the cell-scale radius (where the loop goes
+ * down to it): the tail of the single pass and the sharded finish on one rank.  Three ways: the final
+ * sweep of the fused loop (stars_ready: final_prepare already ran), the one sweep of the Eulerian loops
+ * (eul_r0_fused), or the general kernels, which test xH > TINY at the cell scale and therefore need the
+ * mask materialised first. */
+static int finish_first_cross(ion_ctx *c, const unsigned char *mask, int stars_ready) {
+    int status = 0;
+    const c21cm_ionize_spec *s = c->s;
+    if (c->fused && s->r_lowest == 0 && !c->sphere) return final_step(c, mask, stars_ready);
+    if (eul_r0_fused(c)) { /* one sweep: mask + cell-scale radius + post-loop (one_radius) */
+        c->r0_mask = mask;
+        return one_radius(c, 0, NULL, -1);
+    }
+    TRY(c21hip_apply_first_cross(mask, c->prev_zre, s->first_snapshot, s->redshift, c->xH, c->zre, c->ntot,
+                                 c->stream));
+    if (c->sphere) TRY(paint_spheres(c, mask));
+    if (s->r_lowest == 0) TRY(one_radius(c, 0, NULL, -1));
+done:
+    return status;
+}
+
+/* The same for the state the fused recombination loop leaves (first crossings, with Gamma_12 in place
+ * in c->G12): x_HI, z_reion and the mean free path -- the radius of the crossing -- then the cell-scale
+ * radius on the general kernels (fused_rc implies r_lowest == 0). */
+static int finish_first_cross_recomb(ion_ctx *c, const unsigned char *mask) {
+    int status = 0;
+    const c21cm_ionize_spec *s = c->s;
+    float Rf[C21CM_MAX_RADII];
+    for (int r = 0; r < C21CM_MAX_RADII; r++) Rf[r] = r < s->n_radii ? (float)s->R[r] : 0.f;
+    float *R_dev = (float *)c21hip_ws(WS_R_DEV, sizeof(Rf));
+    if (!R_dev) return C21CM_MEMORY_ALLOC_ERROR;
+    TRY(c21hip_h2d(R_dev, Rf, sizeof(Rf), c->stream));
+    TRY(c21hip_sync(c->stream)); /* `Rf` is a stack buffer */
+    TRY(c21hip_apply_first_cross_recomb(mask, R_dev, c->prev_zre, s->first_snapshot, s->redshift, c->xH,
+                                        c->zre, c->mfp, c->ntot, c->stream));
+    TRY(one_radius(c, 0, NULL, -1));
+done:
+    return status;
+}
+
+/* The single pass: the whole ladder and the finish tail in one call -- what a world = 1 run of a radii
+ * phase followed by its finish phase does too. */
 int c21cm_ionize_grids(const c21cm_ionize_spec *spec, const PerturbedField *perturbed_field,
                        const IonizedBox *previous_ionize_box, const TsBox *spin_temp,
                        const HaloBox *halos, IonizedBox *box, c21cm_ionize_report *report,
@@ -2217,125 +2329,48 @@ int c21cm_ionize_grids(const c21cm_ionize_spec *spec, const PerturbedField *pert
     int status = validate_spec(spec, perturbed_field, halos, spin_temp, box);
     if (status) return status;
     ion_ctx c;
-    void *ev[4] = {NULL, NULL, NULL, NULL};
+    phase_clock clk = {{NULL}, 0, 0};
+    unsigned char *mask = NULL;
     g_spectra.valid = 0;
-    g_single_pass = 1;
-    status = ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, stream);
-    g_single_pass = 0;
-    if (status) goto done;
-    for (int i = 0; i < 4; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, 1, stream));
+    TRY(clock_start(&clk, 4, stream));
     TRY(init_output_grids(&c, previous_ionize_box));
     TRY(preloop(&c));
-    TRY(c21hip_event_record(ev[1], stream));
+    TRY(clock_mark(&clk, stream));
     if (c.fused || c.eul_mask || c.sphere) {
-        c.mask = (unsigned char *)c21hip_ws(WS_FIRST_CROSS, c.ntot);
-        if (!c.mask) {
+        mask = (unsigned char *)c21hip_ws(WS_FIRST_CROSS, c.ntot);
+        if (!mask) {
             status = C21CM_MEMORY_ALLOC_ERROR;
             goto done;
         }
-        TRY(c21hip_memset(c.mask, 0, c.ntot, stream));
+        TRY(c21hip_memset(mask, 0, c.ntot, stream));
     }
-    {
-        const int use_mask = c.fused || c.eul_mask || c.sphere;
-        int mask_pending = use_mask;
-        int R_start = spec->n_radii;
-        /* (the fused Lagrangian loop prepares its own set; grids with other windows keep their tables) */
-        TRY(native_wev_prepare(&c, spec->n_radii - 1, 1, stream));
-        if (c.eul_mask && spec->fcoll_mode != C21CM_FCOLL_ERFC && spec->fcoll_mode != C21CM_FCOLL_NODES) {
-            int radii[C21CM_MAX_RADII], n = 0;
-            for (int R_ct = spec->n_radii - 1; R_ct >= 1 && R_ct >= spec->r_lowest; R_ct--)
-                radii[n++] = R_ct;
-            TRY(eul_table_loop(&c, radii, n, c.mask));
-            {
-                int redo = 0; /* banded barrier: markers settled; a missed band reruns its radii on the
-                               * dense sweeps, through the pipelined loop again */
-                TRY(eul_band_finish(&c, c.mask, &redo));
-                if (redo) {
-                    int m = 0;
-                    for (int i = 0; i < n; i++)
-                        if (radii[i] <= redo) radii[m++] = radii[i];
-                    TRY(eul_table_loop(&c, radii, m, c.mask));
-                }
-            }
-            R_start = 1; /* only the cell-scale radius is left */
-        }
-        if (c.fused) { /* radii n-1 .. 1 through the fused steps; index 0 is the final sweep */
-            TRY(fused_loop(&c, spec->n_radii - 1, 1, spec->r_lowest, c.mask));
-            R_start = 1;
-        }
-        for (int R_ct = R_start; R_ct--;) {
-            if (R_ct < spec->r_lowest) break; /* IonisationBox.c:1537-1541 */
-            if (R_ct == 0 && mask_pending) {
-                TRY(eul_flush_pending(&c, 0)); /* the last radius' barrier of the closed-form loop */
-                {
-                    int redo = 0; /* banded barrier: markers settled; a missed band reruns its radii */
-                    TRY(eul_band_finish(&c, c.mask, &redo));
-                    if (redo) {
-                        R_ct = redo + 1;
-                        continue;
-                    }
-                }
-                mask_pending = 0;
-                if (c.fused && !c.sphere && !c.fused_rc) {
-                    TRY(flush_deferred(&c));
-                    TRY(final_step(&c, c.mask, 0));
-                    break;
-                }
-                if (c.fused) TRY(flush_deferred(&c));
-                if (c.fused_rc) { /* first crossings -> x_HI, z_reion, mean free path (Gamma_12 is in place) */
-                    float Rf[C21CM_MAX_RADII];
-                    for (int r = 0; r < C21CM_MAX_RADII; r++) Rf[r] = r < spec->n_radii ? (float)spec->R[r] : 0.f;
-                    float *R_dev = (float *)c21hip_ws(WS_R_DEV, sizeof(Rf));
-                    if (!R_dev) {
-                        status = C21CM_MEMORY_ALLOC_ERROR;
-                        goto done;
-                    }
-                    TRY(c21hip_h2d(R_dev, Rf, sizeof(Rf), stream));
-                    TRY(c21hip_sync(stream)); /* `Rf` is a stack buffer */
-                    TRY(c21hip_apply_first_cross_recomb(c.mask, R_dev, c.prev_zre, spec->first_snapshot,
-                                                        spec->redshift, c.xH, c.zre, c.mfp, c.ntot, stream));
-                    TRY(one_radius(&c, 0, NULL, -1));
-                    continue;
-                }
-                if (eul_r0_fused(&c)) { /* one sweep: mask + cell-scale radius + post-loop (one_radius) */
-                    c.r0_mask = c.mask;
-                } else {
-                    /* the cell-scale radius tests xH > TINY: materialise the mask first */
-                    TRY(c21hip_apply_first_cross(c.mask, c.prev_zre, spec->first_snapshot,
-                                                 spec->redshift, c.xH, c.zre, c.ntot, stream));
-                    if (c.sphere) TRY(paint_spheres(&c, c.mask));
-                }
-            }
-            TRY(one_radius(&c, R_ct, (R_ct > 0 && use_mask) ? c.mask : NULL,
-                           (R_ct - 1 >= spec->r_lowest) ? R_ct - 1 : -1));
-        }
+    /* (the fused Lagrangian loop prepares its own set; grids with other windows keep their tables) */
+    TRY(native_wev_prepare(&c));
+    if (mask) {
+        TRY(radii_ladder(&c, spec->n_radii - 1, 1, mask, spec->r_lowest == 0 ? 0 : -1));
         TRY(flush_deferred(&c));
-        if (mask_pending) {
-            int redo = 0; /* a loop that stopped above index 0 (r_lowest): same check as above */
-            TRY(eul_band_finish(&c, c.mask, &redo));
-            if (redo) {
-                for (int R_ct = redo; R_ct >= spec->r_lowest && R_ct >= 1; R_ct--)
-                    TRY(one_radius(&c, R_ct, c.mask, (R_ct - 1 >= spec->r_lowest) ? R_ct - 1 : -1));
-                TRY(flush_deferred(&c));
-            }
-            TRY(c21hip_apply_first_cross(c.mask, c.prev_zre, spec->first_snapshot, spec->redshift,
-                                         c.xH, c.zre, c.ntot, stream));
-            if (c.sphere) TRY(paint_spheres(&c, c.mask));
-        }
+        TRY(c.fused_rc ? finish_first_cross_recomb(&c, mask) : finish_first_cross(&c, mask, 0));
+    } else {
+        /* no first-crossing grid (grids the native passes do not take, the unfused recombination
+         * sequence, mini-halos): every radius, index 0 included, writes the outputs itself (one_radius
+         * without a mask reads no next_R hint) */
+        for (int R_ct = spec->n_radii - 1; R_ct >= spec->r_lowest; R_ct--) /* IonisationBox.c:1537-1541 */
+            TRY(one_radius(&c, R_ct, NULL, -1));
+        TRY(flush_deferred(&c));
     }
     c21hip_wev_release();
-    TRY(c21hip_event_record(ev[2], stream));
+    TRY(clock_mark(&clk, stream));
     TRY(postloop(&c, box, report));
-    TRY(c21hip_event_record(ev[3], stream));
+    TRY(clock_mark(&clk, stream));
     if (report) {
-        report->ms_preloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-        report->ms_postloop = c21hip_event_elapsed_ms(ev[2], ev[3]);
+        report->ms_preloop = clock_ms(&clk, 0);
+        report->ms_rloop = clock_ms(&clk, 1);
+        report->ms_postloop = clock_ms(&clk, 2);
     }
 done:
     c21hip_wev_release();
-    for (int i = 0; i < 4; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 
@@ -2369,79 +2404,113 @@ int c21cm_ionize_shard_set_means(const double *means, int n_radii) {
     return 0;
 }
 
+/* ... and the finishing rank puts them back (ctx_setup zeroed the scalar block) */
+static int shard_means_restore(ion_ctx *c) {
+    int status = 0;
+    if (g_shard_means.valid && g_shard_means.n == c->s->n_radii)
+        status = c21hip_h2d(c->scalars + SC_MEANS, g_shard_means.means, sizeof(double) * (size_t)c->s->n_radii,
+                            c->stream);
+    g_shard_means.valid = 0;
+    return status;
+}
+
+/* A radii phase has no IonizedBox.  `dummy` is what its ctx_setup gets in place of one: empty, but for
+ * the unnormalised_nion scratch of the Eulerian models (slot-backed).  Validation sees stand-in outputs:
+ * the phase never touches x_HI / z_reion / T_k (recomb: nor the outputs of a recombination model). */
+static int radii_phase_box(const c21cm_ionize_spec *spec, const PerturbedField *pf, const HaloBox *halos,
+                           const TsBox *ts, int recomb, IonizedBox *dummy) {
+    memset(dummy, 0, sizeof(*dummy));
+    if (spec && spec->fcoll_mode != C21CM_FCOLL_STARS_GRID)
+        dummy->unnormalised_nion = (float *)c21hip_ws(
+            WS_NION_DENSE, (size_t)spec->hii_dim * spec->hii_dim * spec->hii_dim_z * sizeof(float));
+    IonizedBox probe = *dummy;
+    float sentinel;
+    probe.neutral_fraction = probe.z_reion = probe.kinetic_temperature = &sentinel;
+    if (recomb) probe.ionisation_rate_G12 = probe.cumulative_recombinations = &sentinel;
+    int status = validate_spec(spec, pf, halos, ts, &probe);
+    if (!status && spec->use_mini_halos) status = no_mini_shards();
+    return status;
+}
+
+/* The pre-loop of a radii phase: its unfiltered spectra stay in the workspace for the finish phase of
+ * this process (spectra_reuse). */
+static int radii_phase_preloop(ion_ctx *c, const PerturbedField *pf, const HaloBox *halos, const TsBox *ts) {
+    g_spectra.valid = 0;
+    const int status = preloop(c);
+    if (!status) spectra_remember(c, pf, halos, ts);
+    return status;
+}
+
+/* ... which reuses them when this process ran the radii phase on the same input arrays just before,
+ * and otherwise redoes the pre-loop transforms.  *stars_ready: final_prepare ran as well. */
+static int spectra_reuse(ion_ctx *c, const PerturbedField *pf, const HaloBox *halos, const TsBox *ts,
+                         int *stars_ready) {
+    int status = 0;
+    if (spectra_match(c, pf, halos, ts)) {
+        if (stars_ready) *stars_ready = g_spectra.stars_r0_ready;
+    } else {
+        status = preloop(c);
+    }
+    g_spectra.valid = 0;
+    return status;
+}
+
+/* End of a radii phase (clock marks: start, pre-loop done, radii done): the rank's f_coll means and the
+ * timings. */
+static int radii_phase_report(ion_ctx *c, int world, const phase_clock *k, c21cm_ionize_report *report) {
+    int status = 0;
+    double means[C21CM_MAX_RADII];
+    if (!report) return 0;
+    TRY(c21hip_d2h(means, c->scalars + SC_MEANS, sizeof(means), c->stream));
+    TRY(c21hip_sync(c->stream));
+    report_grid_means(report, means, c->s->n_radii);
+    /* a single-process run of both phases (world = 1) keeps its own means */
+    if (world == 1) c21cm_ionize_shard_set_means(means, c->s->n_radii);
+    report->ms_preloop = clock_ms(k, 0);
+    report->ms_rloop = clock_ms(k, 1);
+    report->ms_postloop = 0.;
+done:
+    return status;
+}
+
+/* End of a finish phase (clock mark: start): the post-loop and the timings. */
+static int finish_phase_postloop(ion_ctx *c, IonizedBox *box, c21cm_ionize_report *report, phase_clock *k) {
+    int status = 0;
+    TRY(clock_mark(k, c->stream));
+    TRY(postloop(c, box, report));
+    TRY(clock_mark(k, c->stream));
+    if (report) {
+        report->ms_preloop = 0.;
+        report->ms_rloop = clock_ms(k, 0);
+        report->ms_postloop = clock_ms(k, 1);
+    }
+done:
+    return status;
+}
+
 int c21cm_ionize_shard_radii(const c21cm_ionize_spec *spec, int rank, int world,
                              const PerturbedField *perturbed_field,
                              const IonizedBox *previous_ionize_box, const TsBox *spin_temp,
                              const HaloBox *halos, unsigned char *first_cross,
                              c21cm_ionize_report *report, void *stream) {
     IonizedBox dummy;
-    memset(&dummy, 0, sizeof(dummy));
     int status = 0;
     if (!first_cross || !c21hip_is_device_ptr(first_cross) || world < 1 || rank < 0 ||
         rank >= world) {
         c21hip_set_error("ionize shard: first_cross must be a device array, 0 <= rank < world");
         return C21CM_VALUE_ERROR;
     }
-    if (spec && spec->fcoll_mode != C21CM_FCOLL_STARS_GRID) {
-        /* Eulerian models need unnormalised_nion scratch; give the ctx a slot-backed one */
-        dummy.unnormalised_nion = (float *)c21hip_ws(
-            WS_NION_DENSE, (size_t)spec->hii_dim * spec->hii_dim * spec->hii_dim_z * sizeof(float));
-    }
-    /* validate with stand-in outputs: the shard phase never touches xH / z_reion / T_k */
-    {
-        IonizedBox probe = dummy;
-        float sentinel;
-        probe.neutral_fraction = &sentinel;
-        probe.z_reion = &sentinel;
-        probe.kinetic_temperature = &sentinel;
-        status = validate_spec(spec, perturbed_field, halos, spin_temp, &probe);
-        if (!status && spec->use_mini_halos) status = no_mini_shards();
-        if (status) return status;
-    }
+    if ((status = radii_phase_box(spec, perturbed_field, halos, spin_temp, 0, &dummy))) return status;
     ion_ctx c;
-    void *ev[3] = {NULL, NULL, NULL};
-    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, &dummy, 0,
-                  stream));
-    for (int i = 0; i < 3; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
+    phase_clock clk = {{NULL}, 0, 0};
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, &dummy, 0, 0, stream));
+    TRY(clock_start(&clk, 3, stream));
     TRY(c21hip_memset(first_cross, 0, c.ntot, stream));
-    g_spectra.valid = 0;
-    TRY(preloop(&c));
-    spectra_remember(&c, perturbed_field, halos, spin_temp);
-    TRY(c21hip_event_record(ev[1], stream));
-    TRY(native_wev_prepare(&c, spec->n_radii - 1, 1, stream)); /* the single pass' node tables: the whole ladder */
+    TRY(radii_phase_preloop(&c, perturbed_field, halos, spin_temp));
+    TRY(clock_mark(&clk, stream));
+    TRY(native_wev_prepare(&c));
     /* radii n-1 .. 1 dealt round-robin, largest first; index 0 belongs to the finish step */
-    if (c.eul_mask && spec->fcoll_mode != C21CM_FCOLL_ERFC && spec->fcoll_mode != C21CM_FCOLL_NODES) {
-        int radii[C21CM_MAX_RADII], n = 0;
-        for (int R_ct = spec->n_radii - 1 - rank; R_ct >= 1 && R_ct >= spec->r_lowest; R_ct -= world)
-            radii[n++] = R_ct;
-        TRY(eul_table_loop(&c, radii, n, first_cross));
-        {
-            int redo = 0; /* banded barrier: markers settled; a missed band reruns its radii (dense) */
-            TRY(eul_band_finish(&c, first_cross, &redo));
-            if (redo) {
-                int m = 0;
-                for (int i = 0; i < n; i++)
-                    if (radii[i] <= redo) radii[m++] = radii[i];
-                TRY(eul_table_loop(&c, radii, m, first_cross));
-            }
-        }
-    } else if (c.fused) {
-        TRY(fused_loop(&c, spec->n_radii - 1 - rank, world, spec->r_lowest, first_cross));
-    } else {
-        for (int attempt = 0, from = spec->n_radii; attempt < 2; attempt++) {
-            int redo = 0;
-            for (int R_ct = spec->n_radii - 1 - rank; R_ct >= 1; R_ct -= world) {
-                if (R_ct < spec->r_lowest) break;
-                if (R_ct > from) continue; /* second attempt: from the radius whose band missed */
-                TRY(one_radius(&c, R_ct, first_cross, R_ct - world));
-            }
-            TRY(eul_flush_pending(&c, 1));
-            TRY(eul_band_finish(&c, first_cross, &redo)); /* banded barrier: markers settled, bands checked */
-            if (!redo) break;
-            from = redo;
-        }
-    }
+    TRY(radii_ladder(&c, spec->n_radii - 1 - rank, world, first_cross, -1));
     TRY(flush_deferred(&c));
     /* The rank that will run the finish step has one radius fewer than the busiest ranks: it
      * uses that slack to transform the unfiltered emissivity for the cell-scale step, so that
@@ -2450,21 +2519,11 @@ int c21cm_ionize_shard_radii(const c21cm_ionize_spec *spec, int rank, int world,
         TRY(final_prepare(&c));
         g_spectra.stars_r0_ready = 1;
     }
-    TRY(c21hip_event_record(ev[2], stream));
-    if (report) {
-        double means[C21CM_MAX_RADII];
-        TRY(c21hip_d2h(means, c.scalars + SC_MEANS, sizeof(means), stream));
-        TRY(c21hip_sync(stream));
-        for (int r = 0; r < spec->n_radii; r++) report->f_coll_grid_mean[r] = means[r];
-        /* a single-process run of both phases (world = 1) keeps its own means */
-        if (world == 1) c21cm_ionize_shard_set_means(means, spec->n_radii);
-        report->ms_preloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-        report->ms_postloop = 0.;
-    }
+    TRY(clock_mark(&clk, stream));
+    TRY(radii_phase_report(&c, world, &clk, report));
 done:
     c21hip_wev_release();
-    for (int i = 0; i < 3; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 
@@ -2481,50 +2540,24 @@ int c21cm_ionize_shard_finish(const c21cm_ionize_spec *spec, const unsigned char
         return C21CM_VALUE_ERROR;
     }
     ion_ctx c;
-    void *ev[3] = {NULL, NULL, NULL};
-    /* When this process ran c21cm_ionize_shard_radii on the same input arrays just before,
-     * its unfiltered spectra are still in the workspace and are reused; otherwise the
-     * pre-loop transforms are redone. */
-    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1,
-                  stream));
-    for (int i = 0; i < 3; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
-    if (g_shard_means.valid && g_shard_means.n == spec->n_radii) /* ctx_setup zeroed the block */
-        TRY(c21hip_h2d(c.scalars + SC_MEANS, g_shard_means.means,
-                       sizeof(double) * (size_t)spec->n_radii, stream));
-    g_shard_means.valid = 0;
-    TRY(init_output_grids(&c, previous_ionize_box));
+    phase_clock clk = {{NULL}, 0, 0};
     int stars_ready = 0;
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, 0, stream));
+    TRY(clock_start(&clk, 3, stream));
+    TRY(shard_means_restore(&c));
+    TRY(init_output_grids(&c, previous_ionize_box));
+    /* the cell-scale radius needs the unfiltered spectra, unless the final sweep reads the emissivity
+     * input itself */
     if (spec->r_lowest == 0) {
         if (c.fused && r0_direct() && !c.sphere)
-            stars_ready = 0; /* the final sweep reads the emissivity input itself */
-        else if (spectra_match(&c, perturbed_field, halos, spin_temp))
-            stars_ready = g_spectra.stars_r0_ready;
+            g_spectra.valid = 0;
         else
-            TRY(preloop(&c));
-        g_spectra.valid = 0;
+            TRY(spectra_reuse(&c, perturbed_field, halos, spin_temp, &stars_ready));
     }
-    if (c.fused && spec->r_lowest == 0 && !c.sphere) {
-        TRY(final_step(&c, first_cross, stars_ready));
-    } else if (eul_r0_fused(&c)) { /* as the single pass: one sweep for mask + cell-scale radius + post-loop */
-        c.r0_mask = first_cross;
-        TRY(one_radius(&c, 0, NULL, -1));
-    } else {
-        TRY(c21hip_apply_first_cross(first_cross, c.prev_zre, spec->first_snapshot,
-                                     spec->redshift, c.xH, c.zre, c.ntot, stream));
-        if (c.sphere) TRY(paint_spheres(&c, first_cross));
-        if (spec->r_lowest == 0) TRY(one_radius(&c, 0, NULL, -1));
-    }
-    TRY(c21hip_event_record(ev[1], stream));
-    TRY(postloop(&c, box, report));
-    TRY(c21hip_event_record(ev[2], stream));
-    if (report) {
-        report->ms_preloop = 0.;
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_postloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-    }
+    TRY(finish_first_cross(&c, first_cross, stars_ready));
+    TRY(finish_phase_postloop(&c, box, report, &clk));
 done:
-    for (int i = 0; i < 3; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 
@@ -2594,8 +2627,8 @@ int c21cm_ionize_shard_finish_slab(const c21cm_ionize_spec *spec, const unsigned
     st.rank = rank;
     st.world = world;
     ion_ctx c;
-    void *ev[3] = {NULL, NULL, NULL};
-    int entered = 0, wev = 0;
+    phase_clock clk = {{NULL}, 0, 0};
+    int entered = 0;
     int status = validate_spec(spec, perturbed_field, halos, spin_temp, box);
     if (!status && !c21cm_ionize_shard_slab_supported(spec)) {
         c21hip_set_error("ionize shard: this model does not finish by slabs (c21cm_ionize_shard_slab_supported)");
@@ -2609,7 +2642,7 @@ int c21cm_ionize_shard_finish_slab(const c21cm_ionize_spec *spec, const unsigned
     if (status) goto done;
     TRY(c21cm_ionize_shard_slab(spec, rank, world, &st.chunk_begin, &st.chunk_end, &st.cell_begin,
                                 &st.cell_end, &st.n_chunks, &st.chunk_cells));
-    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, stream));
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, 0, stream));
     const int eul = !c.lagrangian;
     if ((!eul && (!c.fused || c.sphere)) || (eul && !eul_r0_fused(&c))) { /* (slab_supported mirrors ctx_setup) */
         c21hip_set_error("ionize shard: the slab finish needs the fused Lagrangian loop or the one-sweep "
@@ -2618,25 +2651,21 @@ int c21cm_ionize_shard_finish_slab(const c21cm_ionize_spec *spec, const unsigned
         goto done;
     }
     st.ntot = c.ntot;
-    for (int i = 0; i < 3; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
+    TRY(clock_start(&clk, 3, stream));
     c.r0_slab = eul;
     TRY(init_output_grids(&c, previous_ionize_box));
+    /* (no shard_means_restore: every rank finishes, and its report carries the f_coll mean of index 0,
+     * which it computes itself; the means of the radii > 0 stay with the radii-phase reports) */
     g_shard_means.valid = 0;
     if (eul) {
-        /* the cell-scale radius' f_coll grid on every rank (its spectra: left by this process' shard phase,
-         * else recomputed), then the rank's slab of the one sweep */
-        if (!spectra_match(&c, perturbed_field, halos, spin_temp)) TRY(preloop(&c));
-        g_spectra.valid = 0;
-        wev = 1; /* (released under done: a failing radius must not leak the node tables -- ADVICE r5) */
-        TRY(native_wev_prepare(&c, spec->n_radii - 1, 1, stream));
+        /* the cell-scale radius' f_coll grid on every rank, then the rank's slab of the one sweep */
+        TRY(spectra_reuse(&c, perturbed_field, halos, spin_temp, NULL));
+        TRY(native_wev_prepare(&c));
         c.r0_mask = first_cross;
-        c.r0_slab = 1;
         c.r0_cb = st.chunk_begin;
         c.r0_ce = st.chunk_end;
         TRY(one_radius(&c, 0, NULL, -1));
         c21hip_wev_release();
-        wev = 0;
     } else {
         g_spectra.valid = 0;
         TRY(final_step_range(&c, first_cross, 0, st.chunk_begin, st.chunk_end));
@@ -2656,26 +2685,19 @@ int c21cm_ionize_shard_finish_slab(const c21cm_ionize_spec *spec, const unsigned
     } else {
         TRY(final_step_sums(&c));
     }
-    TRY(c21hip_event_record(ev[1], stream));
     if (!outputs_gathered) { /* slab-resident outputs: the host copies of staged grids cover the slab */
         c.cb_cell0 = st.cell_begin;
         c.cb_ncell = st.cell_end - st.cell_begin;
         if (!c.cb_ncell) c.cb.n = 0;
     }
-    TRY(postloop(&c, box, report));
-    TRY(c21hip_event_record(ev[2], stream));
-    if (report) {
-        report->ms_preloop = 0.;
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_postloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-    }
+    TRY(finish_phase_postloop(&c, box, report, &clk));
 done:
-    if (wev) c21hip_wev_release();
+    c21hip_wev_release(); /* (a failing radius must not leak the node tables) */
     if (!entered && exchange) {
         const int st2 = exchange(exchange_user, &st, status ? status : C21CM_VALUE_ERROR, stream);
         if (!status) status = st2;
     }
-    for (int i = 0; i < 3; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 
@@ -2692,7 +2714,6 @@ int c21cm_ionize_shard_radii_keys(const c21cm_ionize_spec *spec, int rank, int w
                                   const HaloBox *halos, unsigned long long *cross_keys,
                                   c21cm_ionize_report *report, void *stream) {
     IonizedBox dummy;
-    memset(&dummy, 0, sizeof(dummy));
     int status = 0;
     if (!cross_keys || !c21hip_is_device_ptr(cross_keys) || world < 1 || rank < 0 || rank >= world) {
         c21hip_set_error("ionize shard: cross_keys must be a device array, 0 <= rank < world");
@@ -2702,56 +2723,37 @@ int c21cm_ionize_shard_radii_keys(const c21cm_ionize_spec *spec, int rank, int w
         c21hip_set_error("ionize shard: the key phases are for recombination models");
         return C21CM_VALUE_ERROR;
     }
-    const size_t ntot = (size_t)spec->hii_dim * spec->hii_dim * spec->hii_dim_z;
-    if (spec->fcoll_mode != C21CM_FCOLL_STARS_GRID)
-        dummy.unnormalised_nion = (float *)c21hip_ws(WS_NION_DENSE, ntot * sizeof(float));
-    {
-        IonizedBox probe = dummy;
-        float sentinel;
-        probe.neutral_fraction = probe.z_reion = probe.kinetic_temperature = &sentinel;
-        probe.ionisation_rate_G12 = probe.cumulative_recombinations = &sentinel;
-        status = validate_spec(spec, perturbed_field, halos, spin_temp, &probe);
-        if (!status && spec->use_mini_halos) status = no_mini_shards();
-        if (status) return status;
-    }
+    if ((status = radii_phase_box(spec, perturbed_field, halos, spin_temp, 1, &dummy))) return status;
     ion_ctx c;
-    void *ev[3] = {NULL, NULL, NULL};
-    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, &dummy, 0,
-                  stream));
+    phase_clock clk = {{NULL}, 0, 0};
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, &dummy, 0, 0, stream));
+    const size_t ntot = c.ntot;
     c.xH = (float *)c21hip_ws(WS_SH_XH, ntot * sizeof(float));
     c.zre = (float *)c21hip_ws(WS_SH_ZRE, ntot * sizeof(float));
     c.G12 = (float *)c21hip_ws(WS_SH_G12, ntot * sizeof(float));
     c.mfp = (float *)c21hip_ws(WS_SH_MFP, ntot * sizeof(float));
-    if (!c.xH || !c.zre || !c.G12 || !c.mfp) return C21CM_MEMORY_ALLOC_ERROR;
-    for (int i = 0; i < 3; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
+    if (!c.xH || !c.zre || !c.G12 || !c.mfp) {
+        status = C21CM_MEMORY_ALLOC_ERROR;
+        goto done;
+    }
+    TRY(clock_start(&clk, 3, stream));
     TRY(c21hip_fill(c.xH, ntot, 1.0f, stream)); /* a fresh IonizedBox (outputs.py:1524-1527) */
     TRY(c21hip_memset(c.G12, 0, ntot * sizeof(float), stream));
     TRY(c21hip_memset(c.mfp, 0, ntot * sizeof(float), stream));
-    g_spectra.valid = 0;
-    TRY(preloop(&c));
-    spectra_remember(&c, perturbed_field, halos, spin_temp);
-    TRY(c21hip_event_record(ev[1], stream));
-    TRY(native_wev_prepare(&c, spec->n_radii - 1, 1, stream)); /* the single pass' node tables: the whole ladder */
-    for (int R_ct = spec->n_radii - 1 - rank; R_ct >= 1; R_ct -= world) {
-        if (R_ct < spec->r_lowest) break;
-        TRY(one_radius(&c, R_ct, NULL, R_ct - world));
-    }
+    TRY(radii_phase_preloop(&c, perturbed_field, halos, spin_temp));
+    TRY(clock_mark(&clk, stream));
+    TRY(native_wev_prepare(&c));
+    /* Not radii_ladder: the unfused recombination sequence keeps no first-crossing grid.  Each of the
+     * rank's radii writes the rank-local x_HI / Gamma_12 / mean free path itself (one_radius without a
+     * mask, which takes no next_R hint), and no banded or deferred barrier is in play. */
+    for (int R_ct = spec->n_radii - 1 - rank; R_ct >= 1 && R_ct >= spec->r_lowest; R_ct -= world)
+        TRY(one_radius(&c, R_ct, NULL, -1));
     TRY(c21hip_pack_cross_keys(c.mfp, c.G12, cross_keys, ntot, stream));
-    TRY(c21hip_event_record(ev[2], stream));
-    if (report) {
-        double means[C21CM_MAX_RADII];
-        TRY(c21hip_d2h(means, c.scalars + SC_MEANS, sizeof(means), stream));
-        TRY(c21hip_sync(stream));
-        for (int r = 0; r < spec->n_radii; r++) report->f_coll_grid_mean[r] = means[r];
-        if (world == 1) c21cm_ionize_shard_set_means(means, spec->n_radii);
-        report->ms_preloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-        report->ms_postloop = 0.;
-    }
+    TRY(clock_mark(&clk, stream));
+    TRY(radii_phase_report(&c, world, &clk, report));
 done:
     c21hip_wev_release();
-    for (int i = 0; i < 3; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 
@@ -2770,33 +2772,20 @@ int c21cm_ionize_shard_finish_keys(const c21cm_ionize_spec *spec,
         return C21CM_VALUE_ERROR;
     }
     ion_ctx c;
-    void *ev[3] = {NULL, NULL, NULL};
-    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1,
-                  stream));
-    for (int i = 0; i < 3; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
-    if (g_shard_means.valid && g_shard_means.n == spec->n_radii)
-        TRY(c21hip_h2d(c.scalars + SC_MEANS, g_shard_means.means,
-                       sizeof(double) * (size_t)spec->n_radii, stream));
-    g_shard_means.valid = 0;
+    phase_clock clk = {{NULL}, 0, 0};
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, 0, stream));
+    TRY(clock_start(&clk, 3, stream));
+    TRY(shard_means_restore(&c));
     TRY(init_output_grids(&c, previous_ionize_box));
     TRY(c21hip_apply_cross_keys(cross_keys, c.prev_zre, spec->first_snapshot, spec->redshift, c.xH,
                                 c.zre, c.G12, c.mfp, c.ntot, stream));
     if (spec->r_lowest == 0) {
-        if (!spectra_match(&c, perturbed_field, halos, spin_temp)) TRY(preloop(&c));
-        g_spectra.valid = 0;
+        TRY(spectra_reuse(&c, perturbed_field, halos, spin_temp, NULL));
         TRY(one_radius(&c, 0, NULL, -1));
     }
-    TRY(c21hip_event_record(ev[1], stream));
-    TRY(postloop(&c, box, report));
-    TRY(c21hip_event_record(ev[2], stream));
-    if (report) {
-        report->ms_preloop = 0.;
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_postloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-    }
+    TRY(finish_phase_postloop(&c, box, report, &clk));
 done:
-    for (int i = 0; i < 3; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 
@@ -2840,7 +2829,6 @@ int c21cm_ionize_shard_radii_rc(const c21cm_ionize_spec *spec, int rank, int wor
                                 const HaloBox *halos, unsigned char *first_cross, float *cross_g12,
                                 c21cm_ionize_report *report, void *stream) {
     IonizedBox dummy;
-    memset(&dummy, 0, sizeof(dummy));
     int status = 0;
     if (!first_cross || !cross_g12 || !c21hip_is_device_ptr(first_cross) ||
         !c21hip_is_device_ptr(cross_g12) || world < 1 || rank < 0 || rank >= world) {
@@ -2852,50 +2840,28 @@ int c21cm_ionize_shard_radii_rc(const c21cm_ionize_spec *spec, int rank, int wor
                          "(c21cm_ionize_shard_rc_supported); use the 64-bit key phases");
         return C21CM_VALUE_ERROR;
     }
-    {
-        IonizedBox probe = dummy;
-        float sentinel;
-        probe.neutral_fraction = probe.z_reion = probe.kinetic_temperature = &sentinel;
-        probe.ionisation_rate_G12 = probe.cumulative_recombinations = &sentinel;
-        status = validate_spec(spec, perturbed_field, halos, spin_temp, &probe);
-        if (status) return status;
-    }
+    if ((status = radii_phase_box(spec, perturbed_field, halos, spin_temp, 1, &dummy))) return status;
     ion_ctx c;
-    void *ev[3] = {NULL, NULL, NULL};
-    g_rc_phase = 1;
-    status = ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, &dummy, 0,
-                       stream);
-    g_rc_phase = 0;
-    if (status) return status;
+    phase_clock clk = {{NULL}, 0, 0};
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, &dummy, 0, 1, stream));
     if (!c.fused_rc) {
         c21hip_set_error("ionize shard: the fused recombination loop is not available for this box");
-        return C21CM_VALUE_ERROR;
+        status = C21CM_VALUE_ERROR;
+        goto done;
     }
     c.G12 = cross_g12;
-    for (int i = 0; i < 3; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
+    TRY(clock_start(&clk, 3, stream));
     TRY(c21hip_memset(first_cross, 0, c.ntot, stream));
     TRY(c21hip_memset(cross_g12, 0, c.ntot * sizeof(float), stream));
-    g_spectra.valid = 0;
-    TRY(preloop(&c));
-    spectra_remember(&c, perturbed_field, halos, spin_temp);
-    TRY(c21hip_event_record(ev[1], stream));
-    TRY(fused_loop(&c, spec->n_radii - 1 - rank, world, 1, first_cross));
+    TRY(radii_phase_preloop(&c, perturbed_field, halos, spin_temp));
+    TRY(clock_mark(&clk, stream));
+    TRY(radii_ladder(&c, spec->n_radii - 1 - rank, world, first_cross, -1)); /* (fused_rc: the fused loop) */
     TRY(flush_deferred(&c));
-    TRY(c21hip_event_record(ev[2], stream));
-    if (report) {
-        double means[C21CM_MAX_RADII];
-        TRY(c21hip_d2h(means, c.scalars + SC_MEANS, sizeof(means), stream));
-        TRY(c21hip_sync(stream));
-        for (int r = 0; r < spec->n_radii; r++) report->f_coll_grid_mean[r] = means[r];
-        if (world == 1) c21cm_ionize_shard_set_means(means, spec->n_radii);
-        report->ms_preloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-        report->ms_postloop = 0.;
-    }
+    TRY(clock_mark(&clk, stream));
+    TRY(radii_phase_report(&c, world, &clk, report));
 done:
     c21hip_wev_release();
-    for (int i = 0; i < 3; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 
@@ -2913,45 +2879,17 @@ int c21cm_ionize_shard_finish_rc(const c21cm_ionize_spec *spec, const unsigned c
         return C21CM_VALUE_ERROR;
     }
     ion_ctx c;
-    void *ev[3] = {NULL, NULL, NULL};
-    g_rc_phase = 1;
-    status = ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, stream);
-    g_rc_phase = 0;
-    if (status) return status;
-    for (int i = 0; i < 3; i++) ev[i] = c21hip_event_create();
-    TRY(c21hip_event_record(ev[0], stream));
-    if (g_shard_means.valid && g_shard_means.n == spec->n_radii)
-        TRY(c21hip_h2d(c.scalars + SC_MEANS, g_shard_means.means,
-                       sizeof(double) * (size_t)spec->n_radii, stream));
-    g_shard_means.valid = 0;
+    phase_clock clk = {{NULL}, 0, 0};
+    TRY(ctx_setup(&c, spec, perturbed_field, previous_ionize_box, spin_temp, halos, box, 1, 1, stream));
+    TRY(clock_start(&clk, 3, stream));
+    TRY(shard_means_restore(&c));
     TRY(init_output_grids(&c, previous_ionize_box));
     TRY(c21hip_d2d(c.G12, cross_g12, c.ntot * sizeof(float), stream));
-    {
-        float Rf[C21CM_MAX_RADII];
-        for (int r = 0; r < C21CM_MAX_RADII; r++) Rf[r] = r < spec->n_radii ? (float)spec->R[r] : 0.f;
-        float *R_dev = (float *)c21hip_ws(WS_R_DEV, sizeof(Rf));
-        if (!R_dev) {
-            status = C21CM_MEMORY_ALLOC_ERROR;
-            goto done;
-        }
-        TRY(c21hip_h2d(R_dev, Rf, sizeof(Rf), stream));
-        TRY(c21hip_sync(stream)); /* `Rf` is a stack buffer */
-        TRY(c21hip_apply_first_cross_recomb(first_cross, R_dev, c.prev_zre, spec->first_snapshot,
-                                            spec->redshift, c.xH, c.zre, c.mfp, c.ntot, stream));
-    }
-    if (!spectra_match(&c, perturbed_field, halos, spin_temp)) TRY(preloop(&c));
-    g_spectra.valid = 0;
-    TRY(one_radius(&c, 0, NULL, -1));
-    TRY(c21hip_event_record(ev[1], stream));
-    TRY(postloop(&c, box, report));
-    TRY(c21hip_event_record(ev[2], stream));
-    if (report) {
-        report->ms_preloop = 0.;
-        report->ms_rloop = c21hip_event_elapsed_ms(ev[0], ev[1]);
-        report->ms_postloop = c21hip_event_elapsed_ms(ev[1], ev[2]);
-    }
+    TRY(spectra_reuse(&c, perturbed_field, halos, spin_temp, NULL)); /* for the cell-scale radius */
+    TRY(finish_first_cross_recomb(&c, first_cross));
+    TRY(finish_phase_postloop(&c, box, report, &clk));
 done:
-    for (int i = 0; i < 3; i++) c21hip_event_destroy(ev[i]);
+    clock_free(&clk);
     return status;
 }
 

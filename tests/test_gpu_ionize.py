@@ -353,6 +353,36 @@ def test_shard_phases_equal_single_pass(api):
     assert rep.global_xH == rep3.global_xH
 
 
+@pytest.mark.parametrize("r_lowest", [2, 3])
+def test_closed_form_shard_phases_with_a_radius_floor_equal_single_pass(api, r_lowest):
+    """Closed-form Eulerian shards whose loop stops above the cell scale (r_lowest >= 2), world = 3: some
+    rank's stride then ends on a radius whose successor lies between 1 and the floor.  No sweep is paired
+    with, and no band is predicted for, a radius that does not run; the max-reduced first crossings and
+    the finish must still be the single pass bit for bit (64-point lines: banded barrier and two radii
+    per pass-X sweep are both in play)."""
+    import torch
+
+    n, world = 64, 3
+    spec = W.ionize_spec(n, mode=W.FCOLL_ERFC, r_bubble_max=10.0, r_lowest=r_lowest)
+    # the case in question: a rank whose last radius R has 1 <= R - world < r_lowest
+    lasts = [[R for R in range(spec.n_radii - 1 - rank, 0, -world) if R >= r_lowest][-1] for rank in range(world)]
+    assert any(1 <= R - world < r_lowest for R in lasts), lasts
+    density = torch.from_numpy(W.density_field_numpy(n, seed=6)).cuda()
+    buf, box, rep = api.ionize_grids(spec, density)
+    assert 0.005 < float((buf.neutral_fraction == 0).float().mean()) < 0.98
+    masks = []
+    for rank in range(world):
+        fc = torch.zeros((n, n, n), dtype=torch.uint8, device="cuda")
+        api.ionize_shard_radii(spec, rank, world, fc, density)
+        masks.append(fc.clone())
+    reduced = torch.stack(masks).max(dim=0).values.contiguous()
+    buf2, box2, rep2 = api.ionize_shard_finish(spec, reduced, density)
+    torch.cuda.synchronize()
+    for name in ("neutral_fraction", "z_reion", "kinetic_temperature"):
+        assert torch.equal(getattr(buf, name), getattr(buf2, name)), name
+    assert rep.global_xH == rep2.global_xH
+
+
 def _emulated_slab_finish(api, spec, world, density, n_ion, **kw):
     """The sharded pass with the finish phase by cell slabs, the ranks of `world` run one after the
     other on the one GPU: every rank's shard phase, exchange 1 (packed first crossings by slab, through
