@@ -391,6 +391,19 @@ int c21hip_halo_deposit(const struct c21cm_halo_consts *consts, unsigned long lo
                         const float *mturn_a, const float *mturn_m, double *out_nion, double *out_sfr,
                         double *out_sfr_mini, double *out_xray, double *out_wsfr, int *scratch,
                         void *stream);
+/* ComputePerturbedHaloCatalog + convert_halo_props (PerturbedHaloCatalog.c:25-149, HaloBox.c:781-880)
+ * for a catalogue in device arrays: one thread per halo, rows in input order.  vdf / vdf2: D - D_i and
+ * its 2LPT analogue; lo_dim: the turnover grids' dimensions; box_to_lores = HII_DIM / DIM.
+ * out = {coords [3 n], masses, M*, SFR, n_ion, L_X, f_esc-weighted SFR, M*_mini, SFR_mini}: the first
+ * five are required, the rest are written where given (L_X with use_xray, the mini pair with
+ * use_mini_halos only); halos of zero mass get coordinates and keep their property rows */
+int c21hip_halo_catalog(const struct c21cm_halo_consts *consts, unsigned long long n_halos,
+                        const float *masses, const float *coords, const float *star_rng,
+                        const float *sfr_rng, const float *xray_rng, const float *const vel[3],
+                        const float *const vel2[3], const int vel_dim[3], const int lo_dim[3],
+                        double box_len, double box_len_z, double vdf, double vdf2, int lpt2,
+                        double box_to_lores, const float *mturn_a, const float *mturn_m,
+                        float *const out[9], void *stream);
 int c21hip_narrow(const double *in, float *out, float *out_scaled, double scale, size_t n,
                   void *stream);
 /* {min, max} of n floats into out2 (device); partials: 2 * 2048 doubles */

@@ -1958,3 +1958,159 @@ extern "C" int c21hip_halo_props(const c21cm_halo_consts *consts, unsigned long 
     LAUNCH_CHECK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// ComputePerturbedHaloCatalog (PerturbedHaloCatalog.c:25-149) with convert_halo_props
+// (HaloBox.c:781-880): the catalogue itself, moved and converted.  One thread per halo in input
+// order, row i of every output array belongs to halo i.  Coordinates: fp64 as upstream, the nearest
+// cell of the velocity grid (pos_to_index, wrap_coord), 1LPT / 2LPT displacement, wrap_position,
+// stored as float -- for every halo.  Properties: halos of non-zero mass only; the turnover masses are
+// CIC-read at the STORED float coordinate times HII_DIM / DIM (HaloBox.c:825-827: upstream scales Mpc
+// as if they were high-resolution cell units; restated as it is, DESIGN Appendix A.3), then the same
+// halo_relations as the deposit and test_halo_props.  A block of kBlock halos moves its coordinate
+// triples through LDS so that the catalogue is read and written in whole lines; the gathers (3 or 6
+// velocities, 16 turnover values) are the random part.
+namespace {
+struct HaloCatalogParams {
+    HaloDepositParams h;  // out_dim: the low-resolution turnover grid; box_size: the wrap lengths
+    double box_to_lores;  // HII_DIM / DIM
+};
+struct HaloCatalogOutputs {
+    float *coords, *masses, *stars, *sfr, *nion, *xray, *wsfr, *stars_mini, *sfr_mini;  // NULL = not written
+};
+
+// wrap_position (indexing.c:14-35).  Upstream subtracts (adds) the box length until the position is
+// inside; so does this, for up to kWrapSteps lengths.  Beyond that (upstream would take as many
+// iterations as box lengths, and never ends on an Inf) the remainder is taken in one step; a NaN stays.
+constexpr int kWrapSteps = 8;
+__device__ __forceinline__ double wrap_position_1d(double pos, double size) {
+    for (int k = 0; k < kWrapSteps && pos >= size; k++) pos -= size;
+    if (pos >= size) pos -= size * floor(pos / size);
+    for (int k = 0; k < kWrapSteps && pos < 0; k++) pos += size;
+    if (pos < 0) pos -= size * floor(pos / size);
+    return pos;  // may equal `size` after an addition that rounds up, as upstream's does
+}
+
+// (int) of a double: defined below 2^31 only; anything else (NaN, Inf, absurd positions) takes cell 0
+__device__ __forceinline__ int checked_int(double x) { return fabs(x) < kPosLimit ? (int)x : 0; }
+
+__global__ void __launch_bounds__(kBlock)
+halo_catalog_kernel(HaloCatalogParams q, HaloArrays A, HaloCatalogOutputs O) {
+    __shared__ float xyz[3 * kBlock];
+    const HaloDepositParams &h = q.h;
+    const c21cm_halo_consts &c = h.c;
+    const unsigned long long base = (unsigned long long)blockIdx.x * kBlock;
+    const unsigned long long left = h.n_halos - base;  // > 0: the grid has ceil(n_halos / kBlock) blocks
+    const int nb = left < (unsigned long long)kBlock ? (int)left : kBlock;
+    for (int i = threadIdx.x; i < 3 * nb; i += kBlock) xyz[i] = A.coords[3 * base + i];
+    __syncthreads();
+    const unsigned long long t = base + threadIdx.x;
+    const bool active = (int)threadIdx.x < nb;
+    float fpos[3] = {0.f, 0.f, 0.f};
+    if (active) {
+        double pos[3];
+        int ip[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            pos[a] = (double)xyz[3 * threadIdx.x + a];
+            ip[a] = wrap_idx(checked_int(pos[a] * h.cell_size_inv_v + 0.5), h.vel_dim[a]);
+        }
+        const size_t vi =
+            (size_t)ip[2] + (size_t)h.vel_dim[2] * ((size_t)ip[1] + (size_t)h.vel_dim[1] * ip[0]);
+        const float v[3] = {A.vx[vi], A.vy[vi], A.vz[vi]};
+        float v2[3] = {0.f, 0.f, 0.f};
+        if (h.lpt2) v2[0] = A.v2x[vi], v2[1] = A.v2y[vi], v2[2] = A.v2z[vi];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            pos[a] += (double)v[a] * h.vdf;
+            if (h.lpt2) pos[a] -= (double)v2[a] * h.vdf2;
+            pos[a] = wrap_position_1d(pos[a], h.box_size[a]);
+            fpos[a] = (float)pos[a];
+            xyz[3 * threadIdx.x + a] = fpos[a];
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * nb; i += kBlock) O.coords[3 * base + i] = xyz[i];
+    if (!active) return;
+    const double hmass = (double)A.masses[t];
+    if (hmass == 0.) return;  // halos cut from the catalogue keep their property rows (HaloBox.c:820-822)
+    double M_turn_a = c.mturn_a_nofb, M_turn_m = c.mturn_m_nofb;
+    if (c.use_mini_halos) {  // cic_read_float at the scaled position (:825-833)
+        int i0[3], i1[3];
+        double d[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const double hp = (double)fpos[a] * q.box_to_lores;
+            const double fl = fabs(hp) < kPosLimit ? floor(hp) : 0.;
+            d[a] = hp - fl;
+            i0[a] = wrap_idx((int)fl, h.out_dim[a]);
+            i1[a] = wrap_idx((int)fl + 1, h.out_dim[a]);
+        }
+        const size_t sy = (size_t)h.out_dim[2], sx = (size_t)h.out_dim[1] * h.out_dim[2];
+        size_t idx[8];
+        double w[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            idx[k] = (size_t)((k & 1) ? i1[0] : i0[0]) * sx + (size_t)((k & 2) ? i1[1] : i0[1]) * sy +
+                     (size_t)((k & 4) ? i1[2] : i0[2]);
+            w[k] = ((k & 1) ? d[0] : 1. - d[0]) * ((k & 2) ? d[1] : 1. - d[1]) *
+                   ((k & 4) ? d[2] : 1. - d[2]);
+        }
+        M_turn_a = pow(10., cic_read(A.mturn_a, idx, w));
+        M_turn_m = pow(10., cic_read(A.mturn_m, idx, w));
+    }
+    const HaloProps p = halo_relations(h, hmass, (double)A.star_rng[t], (double)A.sfr_rng[t],
+                                       A.xray_rng ? (double)A.xray_rng[t] : 0., M_turn_a, M_turn_m);
+    O.masses[t] = (float)hmass;
+    O.stars[t] = (float)p.stars;
+    O.sfr[t] = (float)p.sfr;
+    O.nion[t] = (float)p.n_ion;
+    if (O.stars_mini) O.stars_mini[t] = (float)p.stars_mini;
+    if (O.sfr_mini) O.sfr_mini[t] = (float)p.sfr_mini;
+    if (O.wsfr) O.wsfr[t] = (float)p.wsfr;
+    if (O.xray) O.xray[t] = (float)p.xray;
+}
+}  // namespace
+
+// out = {coords [3 n], masses, stellar masses, SFR, n_ion, L_X, f_esc-weighted SFR, M*_mini, SFR_mini}: the
+// first five are required, the others are written where they are given (the mini pair only with
+// consts->use_mini_halos, L_X only with consts->use_xray); lo_dim: the turnover grids' dimensions
+extern "C" int c21hip_halo_catalog(const c21cm_halo_consts *consts, unsigned long long n_halos,
+                                   const float *masses, const float *coords, const float *star_rng,
+                                   const float *sfr_rng, const float *xray_rng,
+                                   const float *const vel[3], const float *const vel2[3],
+                                   const int vel_dim[3], const int lo_dim[3], double box_len,
+                                   double box_len_z, double vdf, double vdf2, int lpt2,
+                                   double box_to_lores, const float *mturn_a, const float *mturn_m,
+                                   float *const out[9], void *stream) {
+    if (!n_halos) return 0;
+    const size_t blocks = (size_t)((n_halos + kBlock - 1) / kBlock);
+    if (blocks > 0x7fffffffull) {
+        c21hip_set_error("perturbed halo catalogue: %llu halos are more than one launch takes", n_halos);
+        return C21CM_VALUE_ERROR;
+    }
+    HaloCatalogParams q;
+    fill_relation_constants(q.h, consts);
+    q.h.n_halos = n_halos;
+    const double box[3] = {box_len, box_len, box_len_z};
+    for (int a = 0; a < 3; a++) {
+        q.h.vel_dim[a] = vel_dim[a];
+        q.h.out_dim[a] = lo_dim[a];
+        q.h.box_size[a] = box[a];
+    }
+    q.h.cell_size_inv_v = vel_dim[0] / box_len;
+    q.h.vdf = vdf, q.h.vdf2 = vdf2;
+    q.h.cell_vol_inv = 1.;
+    q.h.lpt2 = lpt2;
+    q.box_to_lores = box_to_lores;
+    const bool mini = consts->use_mini_halos;
+    const HaloArrays A = {masses, coords, star_rng, sfr_rng, consts->use_xray ? xray_rng : nullptr,
+                          vel[0], vel[1], vel[2], lpt2 ? vel2[0] : nullptr, lpt2 ? vel2[1] : nullptr,
+                          lpt2 ? vel2[2] : nullptr, mini ? mturn_a : nullptr, mini ? mturn_m : nullptr};
+    const HaloCatalogOutputs O = {out[0], out[1], out[2], out[3], out[4], consts->use_xray ? out[5] : nullptr,
+                                  out[6], mini ? out[7] : nullptr, mini ? out[8] : nullptr};
+    hipLaunchKernelGGL(halo_catalog_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       q, A, O);
+    LAUNCH_CHECK();
+    return 0;
+}

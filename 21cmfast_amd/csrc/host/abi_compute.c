@@ -1467,3 +1467,105 @@ int ComputeHaloBox(double redshift, InitialConditions *ini_boxes, HaloCatalog *h
     if (!ao->USE_TS_FLUCT) g.halo_xray = NULL;
     return c21cm_halobox_grids(&s, ini_boxes, &g, NULL);
 }
+
+/* reference: src/py21cmfast/src/PerturbedHaloCatalog.c:25-149 with convert_halo_props
+ * (HaloBox.c:781-880).  The growth factors are floats upstream (:45-46,79-89), so the two displacement
+ * factors are differences of floats; the halos take the unadjusted scaling constants, the turnover
+ * grids are those of get_log10_turnovers (ComputeHaloBox's). */
+int ComputePerturbedHaloCatalog(float redshift, InitialConditions *boxes, TsBox *prev_ts,
+                                IonizedBox *prev_ion, HaloCatalog *halos,
+                                PerturbedHaloCatalog *halos_perturbed) {
+    int st = require_globals("ComputePerturbedHaloCatalog", 1);
+    if (st) return st;
+    if (!boxes || !halos || !halos_perturbed) {
+        c21hip_set_error("ComputePerturbedHaloCatalog: NULL InitialConditions / HaloCatalog / "
+                         "PerturbedHaloCatalog");
+        return C21CM_VALUE_ERROR;
+    }
+    const SimulationOptions *so = simulation_options_global;
+    const MatterOptions *mo = matter_options_global;
+    const AstroOptions *ao = astro_options_global;
+    /* what the catalogue branch of ComputeHaloBox refuses, as far as it concerns the halos */
+    const char *unsupported = NULL;
+    if (mo->SOURCE_MODEL != C21CM_SOURCE_DEXM_ESF && mo->SOURCE_MODEL != C21CM_SOURCE_CHMF_SAMPLER)
+        unsupported = "a SOURCE_MODEL without halo catalogues (not DEXM-ESF / CHMF-SAMPLER)";
+    if (ao->USE_MINI_HALOS && mo->PERTURB_ON_HIGH_RES)
+        unsupported = "USE_MINI_HALOS with PERTURB_ON_HIGH_RES (refused by ComputeHaloBox, whose grids "
+                      "this catalogue goes with)";
+    if (ao->PHOTON_CONS_TYPE != C21CM_PHOTONCONS_NONE) unsupported = "PHOTON_CONS_TYPE != none";
+    if (unsupported) {
+        c21hip_set_error("ComputePerturbedHaloCatalog: %s is not implemented in this backend yet", unsupported);
+        return C21CM_VALUE_ERROR;
+    }
+    if (halos_perturbed->buffer_size < halos->n_halos) {
+        c21hip_set_error("ComputePerturbedHaloCatalog: buffer_size %llu < n_halos %llu",
+                         halos_perturbed->buffer_size, halos->n_halos);
+        return C21CM_VALUE_ERROR;
+    }
+    if (!halos->n_halos) {
+        halos_perturbed->n_halos = 0;
+        return 0;
+    }
+    const int mini = ao->USE_MINI_HALOS, below = (double)redshift < so->Z_HEAT_MAX; /* HaloBox.c:488-492 */
+    const int flucts = mo->V_CB_MODEL == C21CM_VCB_FLUCTS;
+    PerturbedHaloCatalog o = *halos_perturbed;
+    if (!mini) o.stellar_mini = o.sfr_mini = NULL; /* HaloBox.c:852-861 */
+    if (ao->RECOMB_MODEL == C21CM_RECOMB_NONE) o.fesc_sfr = NULL;
+    if (!ao->USE_TS_FLUCT) o.xray_emissivity = NULL;
+    if ((mini && (!o.stellar_mini || !o.sfr_mini)) ||
+        (ao->RECOMB_MODEL != C21CM_RECOMB_NONE && !o.fesc_sfr) || (ao->USE_TS_FLUCT && !o.xray_emissivity)) {
+        c21hip_set_error("ComputePerturbedHaloCatalog: the output lacks an array that the options ask for "
+                         "(stellar_mini / sfr_mini: USE_MINI_HALOS; fesc_sfr: RECOMB_MODEL; "
+                         "xray_emissivity: USE_TS_FLUCT)");
+        return C21CM_VALUE_ERROR;
+    }
+    if (mini && ((below && (!prev_ts || !prev_ts->J_21_LW || !prev_ion || !prev_ion->ionisation_rate_G12 ||
+                            !prev_ion->z_reion)) ||
+                 (flucts && !boxes->lowres_vcb))) {
+        c21hip_set_error("ComputePerturbedHaloCatalog: USE_MINI_HALOS needs, below Z_HEAT_MAX, the previous "
+                         "TsBox.J_21_LW and IonizedBox Gamma_12 / z_reion (with V_CB_MODEL = FLUCTS also "
+                         "lowres_vcb)");
+        return C21CM_VALUE_ERROR;
+    }
+    if ((st = ensure_ps())) return st;
+
+    c21cm_perturb_halos_spec s;
+    memset(&s, 0, sizeof(s));
+    geometry(&s.dim, &s.dim_z, &s.hii_dim, &s.hii_dim_z, &s.box_len, &s.box_len_z);
+    s.perturb_on_high_res = mo->PERTURB_ON_HIGH_RES;
+    s.lpt2 = (mo->PERTURB_ALGORITHM == C21CM_PERTURB_2LPT);
+    const float growth = (float)dicke(redshift), init_growth = (float)dicke(so->INITIAL_REDSHIFT);
+    const float d2 = (float)(-(3.0 / 7.0) * growth * growth), init_d2 = (float)(-(3.0 / 7.0) * init_growth * init_growth);
+    if (!isfinite(growth) || !isfinite(init_growth)) return C21CM_VALUE_ERROR;
+    s.velocity_displacement_factor = growth - init_growth;
+    s.velocity_displacement_factor_2lpt = d2 - init_d2;
+
+    c21_scaling_consts sc;
+    if ((st = c21_set_scaling_constants(redshift, &sc))) return st;
+    c21cm_halo_consts hc;
+    fill_halo_consts(redshift, &sc, &hc);
+    float *mta = NULL, *mtm = NULL;
+    if (mini) {
+        const size_t n_lo = (size_t)s.hii_dim * s.hii_dim * s.hii_dim_z;
+        mta = (float *)c21hip_ws(229, n_lo * sizeof(float));
+        mtm = (float *)c21hip_ws(230, n_lo * sizeof(float));
+        if (!mta || !mtm) return C21CM_MEMORY_ALLOC_ERROR;
+        c21cm_mturn_spec ms;
+        memset(&ms, 0, sizeof(ms));
+        ms.hii_dim = s.hii_dim, ms.hii_dim_z = s.hii_dim_z;
+        ms.redshift = redshift;
+        ms.mturn_a_nofb = sc.mturn_a_nofb;
+        ms.vcb_const = sc.vcb_const;
+        ms.A_LW = astro_params_global->A_LW, ms.BETA_LW = astro_params_global->BETA_LW;
+        ms.A_VCB = astro_params_global->A_VCB, ms.BETA_VCB = astro_params_global->BETA_VCB;
+        ms.sigma_vcb = cosmo_tables_global->V_CB_AVG * sqrt(3 * M_PI / 8);
+        if ((st = c21cm_halobox_turnovers(&ms, astro_params_global->M_TURN, below, so->N_THREADS,
+                                          below ? prev_ion->ionisation_rate_G12 : NULL,
+                                          below ? prev_ion->z_reion : NULL, below ? prev_ts->J_21_LW : NULL,
+                                          flucts ? boxes->lowres_vcb : NULL, mta, mtm, NULL, NULL)))
+            return st;
+    }
+    st = c21cm_perturb_halos_grids(&s, &hc, boxes, mta, mtm, halos, &o, NULL);
+    if (!st) halos_perturbed->n_halos = o.n_halos;
+    return st;
+}

@@ -336,9 +336,77 @@ def _initialise(lib, inputs: Inputs, data_path):
         lib.init_MHR()
 
 
+class PerturbedHalos:
+    """What ``perturb_halo_catalog`` returns: ``n_halos`` and one array per field of the reference's
+    PerturbedHaloCatalog (``halo_coords`` [n_halos, 3] in Mpc, the others [n_halos]); a field that the
+    options switch off is None.  ``struct`` is the C struct the arrays belong to."""
+
+    def __init__(self, struct):
+        self.struct, self.n_halos = struct, int(struct.n_halos)
+        for name in S.PERTURBED_HALO_FIELDS:
+            a = struct.arrays.get(name)
+            setattr(self, name, None if a is None else a[:self.n_halos])
+
+    def fields(self):
+        return {k: getattr(self, k) for k in S.PERTURBED_HALO_FIELDS if getattr(self, k) is not None}
+
+
+def _box_struct(cls, box):
+    """A TsBox / IonizedBox struct from None, a struct or a dict of arrays by field name."""
+    from . import grid_api as api
+
+    if box is None or isinstance(box, cls):
+        return box
+    names = {f[0] for f in cls._fields_}
+    st = cls(**{k: api._fptr(v) for k, v in box.items() if k in names and hasattr(v, "shape")})
+    st._keep = box
+    return st
+
+
+def _perturb_halos(lib, inputs, redshift, icss, catalog, prev_ts, prev_ion, device):
+    """ComputePerturbedHaloCatalog with the globals already broadcast."""
+    lib.ComputePerturbedHaloCatalog.restype = C.c_int
+    lib.ComputePerturbedHaloCatalog.argtypes = [C.c_float] + [C.c_void_p] * 5
+    out = S.perturbed_halo_catalog(int(catalog.n_halos), inputs, device=device)
+    check(lib.ComputePerturbedHaloCatalog(float(redshift), C.byref(icss),
+                                          C.byref(prev_ts) if prev_ts is not None else None,
+                                          C.byref(prev_ion) if prev_ion is not None else None,
+                                          C.byref(catalog), C.byref(out)), "ComputePerturbedHaloCatalog")
+    return PerturbedHalos(out)
+
+
+def perturb_halo_catalog(inputs: Inputs, redshift, ics, catalog, prev_ts=None, prev_ion=None, *,
+                         data_path=None, device=None, lib=None):
+    """The halos of ``catalog`` (``structs.halo_catalog``; numpy or device arrays) at their Eulerian
+    positions at ``redshift`` with their stellar masses, star-formation rates, ionising and X-ray
+    emissivities (reference: ``perturb_halo_catalog``, drivers/single_field.py; C:
+    PerturbedHaloCatalog.c:25-149, HaloBox.c:781-880), for SOURCE_MODEL = DEXM-ESF / CHMF-SAMPLER.
+    Row i belongs to halo i; halos of zero mass get coordinates and zeros elsewhere.
+
+    ``ics``: the initial conditions, as ``run_coeval`` returns them under ``"initial_conditions"`` (a
+    dict of arrays) or an InitialConditionsStruct.  ``prev_ts`` / ``prev_ion``: the previous snapshot's
+    TsBox / IonizedBox (structs, or dicts of arrays by field name), read with USE_MINI_HALOS below
+    Z_HEAT_MAX only.  ``device``: where the output arrays live (None: numpy).  Returns a
+    ``PerturbedHalos``."""
+    from . import grid_api as api
+
+    lib = lib or load(require_gpu=True)
+    i = inputs
+    lib.Broadcast_struct_global_all(*(C.byref(x) for x in (
+        i.simulation_options, i.matter_options, i.cosmo_params, i.astro_params, i.astro_options,
+        i.cosmo_tables)))
+    if data_path is not None:
+        i._data_path = str(data_path).encode()  # kept alive: C holds the pointer
+        S.ConfigSettings.in_dll(lib, "config_settings").external_table_path = i._data_path
+    lib.init_ps()
+    icss = ics if isinstance(ics, S.InitialConditionsStruct) else api.ics_struct(ics)
+    return _perturb_halos(lib, inputs, redshift, icss, catalog, _box_struct(S.TsBoxStruct, prev_ts),
+                          _box_struct(S.IonizedBoxStruct, prev_ion), device)
+
+
 def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, lib=None,
                keep=("density", "velocity_z", "neutral_fraction", "z_reion", "brightness_temp") + TS_FIELDS,
-               progress=None, halo_catalogs=None, inspect=None):
+               progress=None, halo_catalogs=None, inspect=None, keep_perturbed_halos=False):
     """Evolve boxes through the library's entry points, mirroring ``run_coeval``: initial
     conditions once, then from the highest node redshift down: PerturbedField -> [HaloBox ->
     XraySourceBox ->] [TsBox ->] IonizedBox -> BrightnessTemp, every snapshot receiving the
@@ -356,7 +424,9 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
     redshift from the last node above it, like upstream -- and, under the key ``"history"``, the
     global signal (z, mean dT_b, mean x_HI, mean T_s) of every snapshot computed.
     ``inspect(z, ctx)``: test hook called after every snapshot with the structs its
-    ComputeIonizedBox call was given (``ctx["new_ion"]()`` allocates another output box)."""
+    ComputeIonizedBox call was given (``ctx["new_ion"]()`` allocates another output box).
+    ``keep_perturbed_halos``: with a catalogue source model, every requested redshift also gets
+    ``"perturbed_halos"``: its catalogue moved and converted (``perturb_halo_catalog``)."""
     lib = lib or load(require_gpu=True)
     out_redshifts = [float(np.float32(z)) for z in out_redshifts]
     all_redshifts, is_node = required_redshifts(inputs, out_redshifts)
@@ -365,7 +435,7 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
     mini = bool(inputs.astro_options.USE_MINI_HALOS)
     snaps = _snapshots(inputs, all_redshifts, is_node, inputs.evolution_required, data_path=data_path,
                        device=device, lib=lib, progress=progress, halo_catalogs=halo_catalogs,
-                       inspect=inspect, history=history)
+                       inspect=inspect, history=history, perturbed_halos=keep_perturbed_halos)
     if inputs.matter_options.KEEP_3D_VELOCITIES:  # the two extra components come back with velocity_z
         keep = tuple(keep) + tuple(k for k in ("velocity_x", "velocity_y") if k not in keep)
     ics = None
@@ -377,6 +447,8 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
                 snap["mean_f_coll_MINI"] = ion.mean_f_coll_MINI
                 snap["log10_Mturnover_ave"] = ion.log10_Mturnover_ave
                 snap["log10_Mturnover_MINI_ave"] = ion.log10_Mturnover_MINI_ave
+            if "perturbed_halos" in boxes:
+                snap["perturbed_halos"] = boxes["perturbed_halos"]
             result[z] = snap
     result["history"] = history
     result["initial_conditions"] = ics
@@ -384,13 +456,14 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
 
 
 def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, device, lib, progress,
-               halo_catalogs, inspect, history):
+               halo_catalogs, inspect, history, perturbed_halos=False):
     """The per-snapshot body shared by ``run_coeval`` and ``run_lightcone``: yields
     ``(z, boxes, ion, ts, ics)`` for every redshift of ``all_redshifts`` (descending), ``boxes`` the
     snapshot's arrays by name, ``ion`` / ``ts`` its IonizedBox / TsBox structs.  A node (``z in
     is_node``) becomes the next snapshot's "previous" one when ``chain`` is true (run_coeval: only
     for evolution runs, coeval.py:878-884; a lightcone: always).  Appends the global signal
-    (z, mean dT_b, mean x_HI, mean T_s) of every snapshot to ``history``."""
+    (z, mean dT_b, mean x_HI, mean T_s) of every snapshot to ``history``.  ``perturbed_halos``: with a
+    catalogue source model ``boxes["perturbed_halos"]`` holds the snapshot's PerturbedHalos."""
     from . import grid_api as api
 
     so, mo, ao, ap = (inputs.simulation_options, inputs.matter_options, inputs.astro_options,
@@ -464,7 +537,7 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
         pf_arr = {k: new() for k in pf_fields}
         pf = S.PerturbedFieldStruct(**{k: fp(v) for k, v in pf_arr.items()})
         check(lib.ComputePerturbedField(z, C.byref(icss), C.byref(pf)), "ComputePerturbedField")
-        hb_arr, hb = {}, S.HaloBoxStruct()
+        hb_arr, hb, moved = {}, S.HaloBoxStruct(), {}
         if lagrangian:
             names = (["n_ion", "halo_sfr"] + (["halo_xray"] if ts_on else [])
                      + (["whalo_sfr"] if recomb else []) + (["halo_sfr_mini"] if mini else []))
@@ -476,6 +549,9 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
                                      C.byref(prev_ts) if mini else None,
                                      C.byref(prev_ion) if mini else None, C.byref(hb)),
                   "ComputeHaloBox")
+            if perturbed_halos and cat is not None:
+                moved["perturbed_halos"] = _perturb_halos(lib, inputs, z, icss, cat, prev_ts if mini else None,
+                                                          prev_ion if mini else None, device)
         ts_arr, ts = ({}, S.TsBoxStruct())
         if ts_on:
             srcs = None
@@ -528,7 +604,7 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
             inspect(z, dict(prev_z=prev_z, pf=pf, prev_pf=prev_pf, prev_ion=prev_ion, ts=ts, hb=hb,
                             icss=icss, ion=ion, ion_arr=ion_arr, ts_arr=ts_arr, pf_arr=pf_arr,
                             new_ion=new_ion))
-        yield z, {**pf_arr, **hb_arr, **ts_arr, **ion_arr, **bt_arr}, ion, ts, ics
+        yield z, {**pf_arr, **hb_arr, **ts_arr, **ion_arr, **bt_arr, **moved}, ion, ts, ics
         if z in is_node:
             prev_means = (ion.mean_f_coll, ion.mean_f_coll_MINI)
         if chain and z in is_node:  # only nodes are the next one's "previous"
@@ -834,7 +910,7 @@ def lightcone_fields(inputs: Inputs) -> set:
 
 def run_lightcone(inputs: Inputs, lightconer, node_redshifts, *, data_path=None,
                   device=None, lib=None, include_dvdr_in_tau21=True, apply_rsds=False, n_rsd_subcells=4,
-                  rsd_buffer_slices=(0, 0), halo_catalogs=None, progress=None):
+                  rsd_buffer_slices=(0, 0), halo_catalogs=None, progress=None, keep_perturbed_halos=False):
     """Evolve the node boxes as ``run_coeval`` does and assemble a rectilinear lightcone between
     every pair of nodes on the MI355X (generate_lightcone, drivers/lightcone.py:544-575,596-720).
     Unlike ``run_coeval`` every node is the next one's "previous" snapshot, with or without
@@ -861,7 +937,8 @@ def run_lightcone(inputs: Inputs, lightconer, node_redshifts, *, data_path=None,
     same kernels.  Returns a dict: ``lightcones`` {quantity: (HII_DIM, HII_DIM, n_slices) or, angular,
     (n_pix, n_slices)}, ``lightcone_distances`` [Mpc], ``lightcone_redshifts``, ``node_redshifts``
     (descending), ``global_quantities`` {quantity: per-node box means (fp64)} and ``history`` as
-    run_coeval's; an angular run adds ``latitude`` and ``longitude``."""
+    run_coeval's; an angular run adds ``latitude`` and ``longitude``.  ``keep_perturbed_halos`` with a
+    catalogue source model adds ``perturbed_halos`` {node redshift: PerturbedHalos}."""
     so, ao, cp = inputs.simulation_options, inputs.astro_options, inputs.cosmo_params
     angular = isinstance(lightconer, AngularLightconer)
     if not (angular or isinstance(lightconer, RectilinearLightconer)):
@@ -963,8 +1040,12 @@ def run_lightcone(inputs: Inputs, lightconer, node_redshifts, *, data_path=None,
     history = []
     prev, prev_z = None, None
     snaps = _snapshots(inputs, nodes32, set(nodes32), True, data_path=data_path, device=device, lib=lib,
-                       progress=progress, halo_catalogs=halo_catalogs, inspect=None, history=history)
+                       progress=progress, halo_catalogs=halo_catalogs, inspect=None, history=history,
+                       perturbed_halos=keep_perturbed_halos)
+    moved = {}
     for iz, (z, boxes, _ion, _ts, _ics) in enumerate(snaps):
+        if "perturbed_halos" in boxes:
+            moved[z64[z]] = boxes["perturbed_halos"]
         for q in glob:
             glob[q][iz] = mean(boxes[q])
         cur = node_boxes(boxes)
@@ -1002,4 +1083,6 @@ def run_lightcone(inputs: Inputs, lightconer, node_redshifts, *, data_path=None,
            "node_redshifts": tuple(nodes64), "global_quantities": glob, "history": history}
     if angular:
         out["latitude"], out["longitude"] = requested.latitude.copy(), requested.longitude.copy()
+    if keep_perturbed_halos and moved:
+        out["perturbed_halos"] = moved
     return out

@@ -673,6 +673,25 @@ def grid_minmax(values, stream=None):
     return mm[0], mm[1]
 
 
+def perturb_halos_grids(spec: S.PerturbHalosSpec, consts: S.HaloConsts, ics: dict,
+                        catalog: S.HaloCatalogStruct, out: S.PerturbedHaloCatalogStruct,
+                        log10_mturn_acg=None, log10_mturn_mcg=None, stream=None):
+    """ComputePerturbedHaloCatalog with explicit scalars on the MI355X (reference:
+    PerturbedHaloCatalog.c:25-149, HaloBox.c:781-880): the halos of ``catalog`` displaced with the
+    velocity grids of ``ics`` and converted to galaxy properties into the arrays of ``out``
+    (structs.perturbed_halo_catalog, or any PerturbedHaloCatalogStruct; NULL optional arrays are
+    skipped).  The turnover grids are read with ``consts.use_mini_halos``.  Returns ``out``."""
+    lib = load(require_gpu=True)
+    lib.c21cm_perturb_halos_grids.restype = C.c_int
+    lib.c21cm_perturb_halos_grids.argtypes = [C.c_void_p] * 3 + [S.c_float_p] * 2 + [C.c_void_p] * 3
+    icss = ics_struct(ics)
+    check(lib.c21cm_perturb_halos_grids(C.byref(spec), C.byref(consts), C.byref(icss),
+                                        _fptr(log10_mturn_acg), _fptr(log10_mturn_mcg),
+                                        C.byref(catalog), C.byref(out), _stream(stream)),
+          "c21cm_perturb_halos_grids")
+    return out
+
+
 def halobox_turnovers(spec: S.MturnSpec, m_turn, below_z_heat_max, n_threads, prev_G12,
                       prev_z_reion, J_21_LW, vcb=None, like=None, stream=None):
     """get_log10_turnovers (HaloBox.c:465-516) on the MI355X: (log10 M_turn,a, log10 M_turn,m,

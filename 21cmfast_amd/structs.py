@@ -280,6 +280,63 @@ def halo_catalog(masses, coords, star_rng, sfr_rng, xray_rng=None) -> "HaloCatal
     return cat
 
 
+class PerturbedHaloCatalogStruct(_Base):
+    """``PerturbedHaloCatalog`` (include/c21cm_abi.h; reference _outputstructs_wrapper.h:30-45)."""
+
+    _fields_ = [("n_halos", C.c_ulonglong), ("buffer_size", C.c_ulonglong)] + [
+        (n, c_float_p) for n in (
+            "halo_masses", "halo_coords", "sfr", "stellar_masses", "ion_emissivity", "xray_emissivity",
+            "fesc_sfr", "stellar_mini", "sfr_mini")]
+
+
+PERTURBED_HALO_FIELDS = tuple(n for n, _ in PerturbedHaloCatalogStruct._fields_[2:])
+
+
+def perturbed_halo_fields(inputs) -> tuple:
+    """The arrays of a PerturbedHaloCatalog that the options of ``inputs`` (anything with
+    ``astro_options``) fill: convert_halo_props, HaloBox.c:847-861."""
+    ao = inputs.astro_options
+    return (("halo_masses", "halo_coords", "sfr", "stellar_masses", "ion_emissivity")
+            + (("xray_emissivity",) if ao.USE_TS_FLUCT else ())
+            + (("fesc_sfr",) if ao.RECOMB_MODEL else ())
+            + (("stellar_mini", "sfr_mini") if ao.USE_MINI_HALOS else ()))
+
+
+def perturbed_halo_catalog(n, inputs, device=None) -> "PerturbedHaloCatalogStruct":
+    """A zeroed PerturbedHaloCatalog of ``n`` rows: float32 numpy arrays, or torch tensors on
+    ``device``; only the arrays that the options of ``inputs`` need (the others stay NULL).  The
+    arrays are kept on the struct as ``arrays`` {field: array}; ``halo_coords`` is [n, 3]."""
+    import numpy as np
+
+    n = int(n)
+    cat = PerturbedHaloCatalogStruct(n_halos=0, buffer_size=n)
+    cat.arrays = {}
+    for name in perturbed_halo_fields(inputs):
+        shape = (n, 3) if name == "halo_coords" else (n,)
+        if device is not None:
+            import torch
+
+            a = torch.zeros(shape, dtype=torch.float32, device=device)
+            ptr = C.cast(a.data_ptr(), c_float_p) if n else None
+        else:
+            a = np.zeros(shape, np.float32)
+            ptr = a.ctypes.data_as(c_float_p)
+        cat.arrays[name] = a
+        setattr(cat, name, ptr)
+    return cat
+
+
+class PerturbHalosSpec(_Base):
+    """``c21cm_perturb_halos_spec`` (include/c21cm_grid.h)."""
+
+    _fields_ = [
+        ("dim", C.c_int), ("dim_z", C.c_int), ("hii_dim", C.c_int), ("hii_dim_z", C.c_int),
+        ("box_len", C.c_double), ("box_len_z", C.c_double),
+        ("perturb_on_high_res", C.c_int), ("lpt2", C.c_int),
+        ("velocity_displacement_factor", C.c_double), ("velocity_displacement_factor_2lpt", C.c_double),
+    ]
+
+
 class HaloConsts(_Base):
     """``c21cm_halo_consts`` (include/c21cm_grid.h)."""
 

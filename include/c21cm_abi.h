@@ -376,6 +376,35 @@ typedef struct HaloCatalog {
 int ComputeHaloBox(double redshift, InitialConditions *ini_boxes, HaloCatalog *halos,
                    TsBox *previous_spin_temp, IonizedBox *previous_ionize_box, HaloBox *grids);
 
+/* reference: src/py21cmfast/src/_outputstructs_wrapper.h:30-44.  The catalogue at its Eulerian
+ * positions with the galaxy properties of every halo; buffer_size rows are allocated, n_halos are
+ * filled.  stellar_mini / sfr_mini exist with USE_MINI_HALOS, fesc_sfr with a recombination model,
+ * xray_emissivity with USE_TS_FLUCT; an array that the options switch off may be NULL. */
+typedef struct PerturbedHaloCatalog {
+    unsigned long long int n_halos;
+    unsigned long long int buffer_size;
+    float *halo_masses;
+    float *halo_coords; /* [3 n_halos], Mpc, inside the box */
+    float *sfr;
+    float *stellar_masses;
+    float *ion_emissivity;
+    float *xray_emissivity; /* 1e38 erg/s */
+    float *fesc_sfr;
+    float *stellar_mini;
+    float *sfr_mini;
+} PerturbedHaloCatalog;
+/* reference: src/py21cmfast/src/PerturbedHaloCatalog.c:25-149 with convert_halo_props
+ * (HaloBox.c:781-880; _functionprototypes_wrapper.h).  Every halo is moved with the velocities of its
+ * Lagrangian cell (coordinates are written for all of them); halos of non-zero mass get their
+ * properties, with USE_MINI_HALOS from the turnover grids of get_log10_turnovers (the previous boxes
+ * are read below Z_HEAT_MAX only, lowres_vcb with V_CB_MODEL = FLUCTS only).  Rows of halos with zero
+ * mass are left as they are.  Arrays host or device.  ValueError (3) with a message for a missing
+ * array, buffer_size < n_halos, missing previous boxes, a SOURCE_MODEL without catalogues,
+ * USE_MINI_HALOS with PERTURB_ON_HIGH_RES and PHOTON_CONS_TYPE != none. */
+int ComputePerturbedHaloCatalog(float redshift, InitialConditions *boxes, TsBox *prev_ts,
+                                IonizedBox *prev_ion, HaloCatalog *halos,
+                                PerturbedHaloCatalog *halos_perturbed);
+
 /* reference: src/py21cmfast/src/HaloBox.c:658-779 (_functionprototypes_wrapper.h:127-130; bound by
  * py21cmfast's cfuncs.convert_halo_properties).  Twelve floats per halo: mass, M*, SFR, L_X
  * [1e38 erg/s], n_ion, f_esc-weighted SFR, M*_mini, SFR_mini, M_turn (atomic, molecular,

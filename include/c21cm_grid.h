@@ -542,6 +542,34 @@ int c21cm_halobox_turnovers(const c21cm_mturn_spec *spec, double m_turn, int bel
                             const float *J_21_LW, const float *vcb, float *log10_mturn_acg,
                             float *log10_mturn_mcg, double averages[2], void *stream);
 
+/* ---- ComputePerturbedHaloCatalog: PerturbedHaloCatalog.c:25-149 + convert_halo_props
+ * (HaloBox.c:781-880) with explicit scalars.  Every halo of `halos` is displaced by
+ * v[cell] * velocity_displacement_factor (2LPT: minus v2[cell] * velocity_displacement_factor_2lpt),
+ * `cell` the nearest cell of the velocity grid (hires_v* on dim x dim x dim_z with
+ * perturb_on_high_res, else lowres_v* on hii_dim x hii_dim x hii_dim_z), wrapped into
+ * {box_len, box_len, box_len_z} in fp64 and stored as float: out->halo_coords, for every halo.
+ * Halos of non-zero mass then get set_halo_properties: with consts->use_mini_halos the turnover
+ * masses are 10^CIC-read of the two log10 grids [hii_dim, hii_dim, hii_dim_z] at the stored
+ * coordinate times hii_dim / dim (upstream's scale, HaloBox.c:825-827), else the constants.
+ * Required outputs: halo_coords, halo_masses, stellar_masses, sfr, ion_emissivity.  Written where
+ * non-NULL: fesc_sfr; xray_emissivity (consts->use_xray only); stellar_mini, sfr_mini
+ * (consts->use_mini_halos only).  Rows of zero-mass halos keep their property values.  Sets
+ * out->n_halos; n_halos == 0 launches nothing.  Catalogue arrays and grids: host or device. */
+typedef struct c21cm_perturb_halos_spec {
+    int dim, dim_z;         /* high-resolution grid */
+    int hii_dim, hii_dim_z; /* low-resolution grid (the turnover grids) */
+    double box_len, box_len_z;
+    int perturb_on_high_res; /* velocities: hires_v*, else lowres_v* */
+    int lpt2;                /* PERTURB_ALGORITHM == 2LPT */
+    double velocity_displacement_factor;      /* D(z) - D(z_init) */
+    double velocity_displacement_factor_2lpt; /* D2(z) - D2(z_init), D2 = -3/7 D^2 */
+} c21cm_perturb_halos_spec;
+
+int c21cm_perturb_halos_grids(const c21cm_perturb_halos_spec *spec, const c21cm_halo_consts *consts,
+                              const InitialConditions *ics, const float *log10_mturn_acg,
+                              const float *log10_mturn_mcg, const HaloCatalog *halos,
+                              PerturbedHaloCatalog *out, void *stream);
+
 /* min and max of n floats (host or device array), e.g. the table range of the above */
 int c21cm_grid_minmax(const float *values, size_t n, double out_minmax[2], void *stream);
 
