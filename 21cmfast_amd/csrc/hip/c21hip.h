@@ -13,6 +13,8 @@
 
 #include <stddef.h>
 
+#include "ws_slots.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -23,6 +25,10 @@ int c21hip_current_device(void);     /* -1 when there is none */
 int c21hip_use_device(int device);   /* per-thread: for helper threads of the host drivers */
 int c21hip_is_device_ptr(const void *p);     /* 1 = MI355X HBM, 0 = host          */
 void *c21hip_ws(int slot, size_t bytes);     /* cached device scratch, NULL = OOM */
+/* host/stage.c: the device copy of an input array.  A device pointer comes back as it is; a host array is
+ * uploaded into `slot` on `stream`.  NULL in, or *status already set: NULL, and *status stays as it was.
+ * (Internal to the library: not exported.) */
+__attribute__((visibility("hidden"))) const void *c21_stage_in(int slot, const void *p, size_t bytes, void *stream, int *status);
 /* placement shopping (ionize_driver.c: place_work_partner): what a slot holds, a buffer handed to a slot, plain
  * allocations outside the workspace, free device memory; the timed two-grid pass Y that tells whether two work
  * spectra sit well together (fft_native.hip) */

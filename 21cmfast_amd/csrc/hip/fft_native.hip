@@ -3640,7 +3640,7 @@ struct WinTables {
 static int win_tables(int table_slot, int n_grids, const int filter_type[2], float R,
                       const float R_param[2], float R_star, int nx, int ny, int nz, double box_len,
                       double box_len_z, bool build, hipStream_t stream, WinTables &w) {
-    static const int ws_slot[4] = {49, 46, 94, 95};
+    static_assert(WS_WIN_TAB_LAST - WS_WIN_TAB0 == 3, "one workspace slot per table slot");
     if (table_slot < 0 || table_slot > 3) return C21CM_VALUE_ERROR;
     const int H = nz / 2;
     // the window's parameters beyond (type, R): R_param matters for types 3 and 4 only
@@ -3649,7 +3649,7 @@ static int win_tables(int table_slot, int n_grids, const int filter_type[2], flo
     const size_t n_main = (size_t)(ny / 2 + 1) * (nx / 2 + 1) * H;
     const size_t n_nyq = (size_t)(nx / 2 + 1) * (ny / 2 + 1);
     const size_t per = (n_main + n_nyq + 3) & ~(size_t)3;  // keep table b 16-byte aligned
-    wtab_t *tab = (wtab_t *)c21hip_ws(ws_slot[table_slot], sizeof(wtab_t) * per * (dual ? 2 : 1));
+    wtab_t *tab = (wtab_t *)c21hip_ws(WS_WIN_TAB0 + table_slot, sizeof(wtab_t) * per * (dual ? 2 : 1));
     if (!tab) return C21CM_MEMORY_ALLOC_ERROR;
     WTableArgs t{};
     fill_filter(t.pa, filter_type[0], R, R_param[0], box_len, box_len_z);
@@ -4174,9 +4174,9 @@ extern "C" int c21hip_wev_prepare(int filter_a, float R_param_a, int filter_b, f
         w.first_type = 0;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    w.nodes = (float *)c21hip_ws(240, sizeof(float) * 3 * (size_t)w.n_nodes * w.n_tabs);
+    w.nodes = (float *)c21hip_ws(WS_WEV_NODES, sizeof(float) * 3 * (size_t)w.n_nodes * w.n_tabs);
     const int n_mfp = n_mfp_windows * n_R;
-    ExpMfpConsts *mfp_dev = (ExpMfpConsts *)c21hip_ws(241, sizeof(ExpMfpConsts) * (size_t)(n_mfp > 0 ? n_mfp : 1));
+    ExpMfpConsts *mfp_dev = (ExpMfpConsts *)c21hip_ws(WS_WEV_MFP, sizeof(ExpMfpConsts) * (size_t)(n_mfp > 0 ? n_mfp : 1));
     if (!w.nodes || !mfp_dev) return C21CM_MEMORY_ALLOC_ERROR;
     if (n_mfp > 0) {
         static std::vector<ExpMfpConsts> host;  // must outlive the asynchronous copy
@@ -5066,12 +5066,12 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
     hipStream_t stream = (hipStream_t)stream_;
     if (!c21hip_native_fft_supported(n, n, n)) return C21CM_VALUE_ERROR;
     const size_t nf = c21hip_split_floats(n, n, n);
-    float *a = (float *)c21hip_ws(58, nf * sizeof(float));
-    float *b = (float *)c21hip_ws(59, nf * sizeof(float));
-    float *real = (float *)c21hip_ws(60, nf * sizeof(float));
-    float *real2 = (float *)c21hip_ws(63, nf * sizeof(float));
-    unsigned char *mask = (unsigned char *)c21hip_ws(61, (size_t)n * n * n);
-    double *partials = (double *)c21hip_ws(62, ((size_t)n * n / 2 + 128) * sizeof(double));
+    float *a = (float *)c21hip_ws(WS_BENCH_A, nf * sizeof(float));
+    float *b = (float *)c21hip_ws(WS_BENCH_B, nf * sizeof(float));
+    float *real = (float *)c21hip_ws(WS_BENCH_REAL, nf * sizeof(float));
+    float *real2 = (float *)c21hip_ws(WS_BENCH_REAL2, nf * sizeof(float));
+    unsigned char *mask = (unsigned char *)c21hip_ws(WS_BENCH_MASK, (size_t)n * n * n);
+    double *partials = (double *)c21hip_ws(WS_BENCH_PARTIALS, ((size_t)n * n / 2 + 128) * sizeof(double));
     if (!a || !b || !real || !real2 || !mask || !partials) return C21CM_MEMORY_ALLOC_ERROR;
     hipLaunchKernelGGL(pattern_fill_kernel, dim3(2048), dim3(kBlock), 0, stream, a, nf);
     hipLaunchKernelGGL(pattern_fill_kernel, dim3(2048), dim3(kBlock), 0, stream, b, nf);
@@ -5088,8 +5088,8 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
     float *pair2[2] = {nullptr, nullptr};
     if (kind == 6) {  // two-radius pass X: second outputs, tables of R and 0.9 R
         if (n >= 1024) return C21CM_VALUE_ERROR;
-        pair2[0] = (float *)c21hip_ws(92, nf * sizeof(float));
-        pair2[1] = (float *)c21hip_ws(93, nf * sizeof(float));
+        pair2[0] = (float *)c21hip_ws(WS_BENCH_A2, nf * sizeof(float));
+        pair2[1] = (float *)c21hip_ws(WS_BENCH_B2, nf * sizeof(float));
         if (!pair2[0] || !pair2[1]) return C21CM_MEMORY_ALLOC_ERROR;
         st = filter_xy_pair(a, real, pair2[0], filter_a, 0.f, b, real2, pair2[1], filter_b,
                             R_param_b, n, n, n, box_len, box_len, R, 0.9f * R, 0, 1, 1, stream_);
@@ -5102,8 +5102,8 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
                                 n, box_len, box_len, kind == 8, &enabled, stream_);
         if (!st && !enabled) st = C21CM_VALUE_ERROR;
         if (kind == 8) {
-            pair2[0] = (float *)c21hip_ws(92, nf * sizeof(float));
-            pair2[1] = (float *)c21hip_ws(93, nf * sizeof(float));
+            pair2[0] = (float *)c21hip_ws(WS_BENCH_A2, nf * sizeof(float));
+            pair2[1] = (float *)c21hip_ws(WS_BENCH_B2, nf * sizeof(float));
             if (!pair2[0] || !pair2[1]) return C21CM_MEMORY_ALLOC_ERROR;
         }
     }
@@ -5158,7 +5158,7 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
 // PerturbedField / InitialConditions drivers for power-of-two grids).
 extern "C" int c21hip_native_fft_c2r(float *padded, int nx, int ny, int nz, void *stream) {
     const size_t bytes = c21hip_split_floats(nx, ny, nz) * sizeof(float);
-    float *split = (float *)c21hip_ws(48, bytes);
+    float *split = (float *)c21hip_ws(WS_NATIVE_C2R_SPLIT, bytes);
     if (!split) return C21CM_MEMORY_ALLOC_ERROR;
     int st = c21hip_padded_to_split(padded, split, nx, ny, nz, stream);
     if (st) return st;

@@ -2163,7 +2163,7 @@ extern "C" int c21hip_neutral_box(const float *density, const float *xe, const f
 
 // *flag_host = 1 if any element of the device array is non-zero (synchronises)
 extern "C" int c21hip_any_nonzero(const float *a, size_t n, int *flag_host, void *stream) {
-    int *flag = (int *)c21hip_ws(47, sizeof(int));
+    int *flag = (int *)c21hip_ws(WS_ANY_NONZERO_FLAG, sizeof(int));
     if (!flag) return C21CM_MEMORY_ALLOC_ERROR;
     int st = c21hip_memset(flag, 0, sizeof(int), stream);
     if (st) return st;

@@ -20,7 +20,7 @@
 #include "c21cm_abi.h"
 
 namespace {
-constexpr int kMaxSlots = 296;  // ids 256.. : shard_rccl.c (status word, slab exchange); 288..: power_driver.c
+constexpr int kMaxSlots = WS_COUNT;
 struct Slot {
     void *ptr = nullptr;
     size_t bytes = 0;

@@ -471,8 +471,8 @@ int ComputeIonizedBox(float redshift, float prev_redshift, PerturbedField *pertu
                 for (size_t i = 0; i < ntot; i++) pd[i] = -1.5f;
             }
         }
-        float *mta = (float *)c21hip_ws(205, ntot * sizeof(float));
-        float *mtm = (float *)c21hip_ws(206, ntot * sizeof(float));
+        float *mta = (float *)c21hip_ws(WS_ABI_ION_MTA, ntot * sizeof(float));
+        float *mtm = (float *)c21hip_ws(WS_ABI_ION_MTM, ntot * sizeof(float));
         if (!mta || !mtm) {
             st = C21CM_MEMORY_ALLOC_ERROR;
             goto done;
@@ -739,7 +739,7 @@ static double wall_seconds(void) {
 /* Box mean as ts_main takes it (:1479-1489): double sum, divided by (float)N. */
 static int box_mean(const float *v, size_t n, double *mean) {
     if (c21hip_is_device_ptr(v)) {
-        double *scratch = (double *)c21hip_ws(171, (C21HIP_PARTIALS + 1) * sizeof(double));
+        double *scratch = (double *)c21hip_ws(WS_ABI_MEAN_PART, (C21HIP_PARTIALS + 1) * sizeof(double));
         if (!scratch) return C21CM_MEMORY_ALLOC_ERROR;
         int st = c21hip_sum_float(v, n, scratch + 1, scratch, NULL);
         if (st) return st;
@@ -1010,7 +1010,7 @@ static int ts_box_run(float redshift, float prev_redshift, float perturbed_field
         r->min_value = -1;
         r->const_factor = 1. / dicke(perturbed_field_redshift);
         job.input = perturbed_field->density;
-        job.result = (float *)c21hip_ws(170, (size_t)tab->n_step * ntot * sizeof(float));
+        job.result = (float *)c21hip_ws(WS_ABI_TS_FILTERED, (size_t)tab->n_step * ntot * sizeof(float));
         if (!job.result) {
             c21hip_set_error("ComputeTsBox: out of device memory for %d filtered density grids", tab->n_step);
             st = C21CM_MEMORY_ALLOC_ERROR;
@@ -1039,8 +1039,8 @@ static int ts_box_run(float redshift, float prev_redshift, float perturbed_field
             ms.A_LW = astro_params_global->A_LW, ms.BETA_LW = astro_params_global->BETA_LW;
             ms.A_VCB = astro_params_global->A_VCB, ms.BETA_VCB = astro_params_global->BETA_VCB;
             ms.sigma_vcb = cosmo_tables_global->V_CB_AVG * sqrt(3 * M_PI / 8);
-            float *mcrit = (float *)c21hip_ws(172, ntot * sizeof(float));
-            float *mcrit_R = (float *)c21hip_ws(173, (size_t)tab->n_step * ntot * sizeof(float));
+            float *mcrit = (float *)c21hip_ws(WS_ABI_TS_MCRIT, ntot * sizeof(float));
+            float *mcrit_R = (float *)c21hip_ws(WS_ABI_TS_MCRIT_R, (size_t)tab->n_step * ntot * sizeof(float));
             if (!mcrit || !mcrit_R) {
                 st = C21CM_MEMORY_ALLOC_ERROR;
                 goto done;
@@ -1213,29 +1213,16 @@ int test_halo_props(double redshift, float *vcb_grid, float *J21_LW_grid, float 
     hii[1] = hii[0];
     const size_t nh = (size_t)n_halos, fb = nh * sizeof(float);
     const size_t gb = (size_t)hii[0] * hii[1] * hii[2] * sizeof(float);
-    enum { WS_HP0 = 238 };
     const float *in[5] = {halo_masses, halo_coords, star_rng, sfr_rng, xray_rng};
     const float *grid_in[4] = {vcb_grid, J21_LW_grid, z_re_grid, Gamma12_ion_grid};
     const float *dev[5], *gdev[4] = {NULL, NULL, NULL, NULL};
-    for (int k = 0; k < 5; k++) {
-        dev[k] = in[k];
-        if (!c21hip_is_device_ptr(in[k])) {
-            void *d = c21hip_ws(WS_HP0 + k, k == 1 ? 3 * fb : fb);
-            if (!d) return C21CM_MEMORY_ALLOC_ERROR;
-            if ((st = c21hip_h2d(d, in[k], k == 1 ? 3 * fb : fb, NULL))) return st;
-            dev[k] = (const float *)d;
-        }
-    }
+    _Static_assert(WS_HP_LAST - WS_HP0 == 9, "five catalogue arrays, four grids, the property rows");
+    for (int k = 0; k < 5; k++) dev[k] = c21_stage_in(WS_HP0 + k, in[k], k == 1 ? 3 * fb : fb, NULL, &st);
     for (int k = 0; k < 4 && mini; k++) {
-        if (!grid_in[k] || (k == 0 ? !flucts : !below)) continue;
-        gdev[k] = grid_in[k];
-        if (!c21hip_is_device_ptr(grid_in[k])) {
-            void *d = c21hip_ws(WS_HP0 + 5 + k, gb);
-            if (!d) return C21CM_MEMORY_ALLOC_ERROR;
-            if ((st = c21hip_h2d(d, grid_in[k], gb, NULL))) return st;
-            gdev[k] = (const float *)d;
-        }
+        if (k == 0 ? !flucts : !below) continue;
+        gdev[k] = c21_stage_in(WS_HP0 + 5 + k, grid_in[k], gb, NULL, &st);
     }
+    if (st) return st;
     float *out = halo_props_out;
     if (!c21hip_is_device_ptr(out)) {
         if (!(out = (float *)c21hip_ws(WS_HP0 + 9, 12 * fb))) return C21CM_MEMORY_ALLOC_ERROR;
@@ -1386,8 +1373,8 @@ int ComputeHaloBox(double redshift, InitialConditions *ini_boxes, HaloCatalog *h
                              "(with V_CB_MODEL = FLUCTS also lowres_vcb)");
             return C21CM_VALUE_ERROR;
         }
-        float *mta = (float *)c21hip_ws(229, n_out * sizeof(float));
-        float *mtm = (float *)c21hip_ws(230, n_out * sizeof(float));
+        float *mta = (float *)c21hip_ws(WS_ABI_HB_MTA, n_out * sizeof(float));
+        float *mtm = (float *)c21hip_ws(WS_ABI_HB_MTM, n_out * sizeof(float));
         if (!mta || !mtm) return C21CM_MEMORY_ALLOC_ERROR;
         c21cm_mturn_spec ms;
         memset(&ms, 0, sizeof(ms));
@@ -1547,8 +1534,8 @@ int ComputePerturbedHaloCatalog(float redshift, InitialConditions *boxes, TsBox 
     float *mta = NULL, *mtm = NULL;
     if (mini) {
         const size_t n_lo = (size_t)s.hii_dim * s.hii_dim * s.hii_dim_z;
-        mta = (float *)c21hip_ws(229, n_lo * sizeof(float));
-        mtm = (float *)c21hip_ws(230, n_lo * sizeof(float));
+        mta = (float *)c21hip_ws(WS_ABI_HB_MTA, n_lo * sizeof(float));
+        mtm = (float *)c21hip_ws(WS_ABI_HB_MTM, n_lo * sizeof(float));
         if (!mta || !mtm) return C21CM_MEMORY_ALLOC_ERROR;
         c21cm_mturn_spec ms;
         memset(&ms, 0, sizeof(ms));

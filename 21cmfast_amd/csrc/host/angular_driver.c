@@ -14,17 +14,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-/* slot ids after rsd_driver.c's 275-279; runtime.hip allows ids below 288 */
-enum {
-    WS_ANG_NHAT = 280,
-    WS_ANG_TAB = 281,
-    WS_ANG_BOXES = 282,
-    WS_ANG_SLAB = 283,
-    WS_ANG_FLAG = 284,
-    WS_PREFILTER_IN = 285,
-    WS_PREFILTER_OUT = 286
-};
-
 #define TRY(expr)         \
     do {                  \
         int st_ = (expr); \

@@ -8,8 +8,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-enum { WS_MISC_A = 40, WS_MISC_B = 41, WS_MISC_C = 42, WS_MISC_D = 43 };
-
 const char *c21cm_version(void) { return "21cmfast_amd 0.1 (gfx950)"; }
 const char *c21cm_last_error(void) { return c21hip_get_error(); }
 int c21cm_device_synchronize(void) { return c21hip_device_sync(); }

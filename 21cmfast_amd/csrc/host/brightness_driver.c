@@ -9,8 +9,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-enum { WS_BT_DENS = 36, WS_BT_XH, WS_BT_TS, WS_BT_OUT, WS_BT_TAU = 44, WS_BT_PART = 45 };
-
 #define TRY(expr)         \
     do {                  \
         int st_ = (expr); \
@@ -19,17 +17,6 @@ enum { WS_BT_DENS = 36, WS_BT_XH, WS_BT_TS, WS_BT_OUT, WS_BT_TAU = 44, WS_BT_PAR
             goto done;    \
         }                 \
     } while (0)
-
-static const float *bt_in(int slot, const float *p, size_t bytes, void *stream, int *status) {
-    if (!p || *status || c21hip_is_device_ptr(p)) return p;
-    void *d = c21hip_ws(slot, bytes);
-    if (!d) {
-        *status = C21CM_MEMORY_ALLOC_ERROR;
-        return NULL;
-    }
-    *status = c21hip_h2d(d, p, bytes, stream);
-    return (const float *)d;
-}
 
 int c21cm_brightness_grids(const c21cm_brightness_spec *s, const float *density,
                            const float *neutral_fraction, const float *spin_temperature,
@@ -44,9 +31,9 @@ int c21cm_brightness_grids(const c21cm_brightness_spec *s, const float *density,
         return C21CM_VALUE_ERROR;
     }
     const size_t bytes = s->n_cells * sizeof(float);
-    const float *d_dens = bt_in(WS_BT_DENS, density, bytes, stream, &status);
-    const float *d_xh = bt_in(WS_BT_XH, neutral_fraction, bytes, stream, &status);
-    const float *d_ts = s->use_ts_fluct ? bt_in(WS_BT_TS, spin_temperature, bytes, stream, &status) : NULL;
+    const float *d_dens = c21_stage_in(WS_BT_DENS, density, bytes, stream, &status);
+    const float *d_xh = c21_stage_in(WS_BT_XH, neutral_fraction, bytes, stream, &status);
+    const float *d_ts = s->use_ts_fluct ? c21_stage_in(WS_BT_TS, spin_temperature, bytes, stream, &status) : NULL;
     if (status) return status;
     const int host_bt = !c21hip_is_device_ptr(brightness_temp);
     const int host_tau = s->use_ts_fluct && !c21hip_is_device_ptr(tau_21);

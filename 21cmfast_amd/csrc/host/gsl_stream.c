@@ -447,7 +447,7 @@ int c21_gsl_mode_deviates_device(unsigned long long seed, int n_threads, int nx,
         return C21CM_MEMORY_ALLOC_ERROR;
     }
     /* the generator kind of every row, then the conversion in place on the caller's stream */
-    unsigned char *kind_dev = (unsigned char *)c21hip_ws(255, (size_t)nx);
+    unsigned char *kind_dev = (unsigned char *)c21hip_ws(WS_GSL_ROW_KIND, (size_t)nx);
     if (!kind_dev) {
         free(row_kind);
         return C21CM_MEMORY_ALLOC_ERROR;

@@ -12,16 +12,8 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-enum {
-    WS_HB_ACC0 = 23, /* double accumulation grids (WS_PT_RESAMPLED and the next free slot) */
-    WS_HB_IN0 = 24,  /* .. +6 staged IC arrays (WS_PT_IN0 ..) */
-    WS_HB_OUT0 = 32, /* .. +2 staged outputs */
-    WS_HB_ACC1 = 35,
-    WS_HB_ACC2 = 87,
-    WS_HB_OUT3 = 88,
-    WS_HB_TABLES = 38,
-    WS_HB_PART = 39
-};
+/* the slot ranges this file indexes: density + 3 velocities + 3 2LPT velocities in; three outputs */
+_Static_assert(WS_HB_IN_LAST - WS_HB_IN0 == 6 && WS_HB_OUT_LAST - WS_HB_OUT0 == 2, "halobox: staging slot ranges");
 
 #define TRY(expr)         \
     do {                  \
@@ -32,21 +24,10 @@ enum {
         }                 \
     } while (0)
 
-static const float *hb_in(int slot, const float *p, size_t bytes, void *stream, int *status) {
-    if (!p || *status || c21hip_is_device_ptr(p)) return p;
-    void *d = c21hip_ws(slot, bytes);
-    if (!d) {
-        *status = C21CM_MEMORY_ALLOC_ERROR;
-        return NULL;
-    }
-    *status = c21hip_h2d(d, p, bytes, stream);
-    return (const float *)d;
-}
-
 int c21cm_grid_minmax(const float *values, size_t n, double out_minmax[2], void *stream) {
     int status = 0;
     if (!values || !n || !out_minmax) return C21CM_VALUE_ERROR;
-    const float *d = hb_in(WS_HB_IN0, values, n * sizeof(float), stream, &status);
+    const float *d = c21_stage_in(WS_HB_IN0, values, n * sizeof(float), stream, &status);
     if (status) return status;
     double *part = (double *)c21hip_ws(WS_HB_PART, (2 * 2048 + 2) * sizeof(double));
     if (!part) return C21CM_MEMORY_ALLOC_ERROR;
@@ -61,8 +42,6 @@ done:
  * (map_mass.c:346-476) into the zeroed accumulation grids, before the integrated deposit adds the
  * sources below the catalogue's mass limit.  acc = {n_ion, halo_sfr, halo_sfr_mini, halo_xray,
  * whalo_sfr}; entries may be NULL. */
-enum { WS_HC_MASS = 231, WS_HC_COORD, WS_HC_RNG0, WS_HC_RNG1, WS_HC_RNG2, WS_HC_WSFR, WS_HC_BINS };
-
 static int deposit_halos(const c21cm_halobox_spec *s, const float *const vel[3],
                          const float *const vel2[3], const int vel_dim[3], const float *mta,
                          const float *mtm, double *const acc[5], void *stream) {
@@ -77,11 +56,11 @@ static int deposit_halos(const c21cm_halobox_spec *s, const float *const vel[3],
     }
     int status = 0;
     const size_t nh = (size_t)h->n_halos, fb = nh * sizeof(float);
-    const float *mass = hb_in(WS_HC_MASS, h->halo_masses, fb, stream, &status);
-    const float *coord = hb_in(WS_HC_COORD, h->halo_coords, 3 * fb, stream, &status);
-    const float *r0 = hb_in(WS_HC_RNG0, h->star_rng, fb, stream, &status);
-    const float *r1 = hb_in(WS_HC_RNG1, h->sfr_rng, fb, stream, &status);
-    const float *r2 = c->use_xray ? hb_in(WS_HC_RNG2, h->xray_rng, fb, stream, &status) : NULL;
+    const float *mass = c21_stage_in(WS_HC_MASS, h->halo_masses, fb, stream, &status);
+    const float *coord = c21_stage_in(WS_HC_COORD, h->halo_coords, 3 * fb, stream, &status);
+    const float *r0 = c21_stage_in(WS_HC_RNG0, h->star_rng, fb, stream, &status);
+    const float *r1 = c21_stage_in(WS_HC_RNG1, h->sfr_rng, fb, stream, &status);
+    const float *r2 = c->use_xray ? c21_stage_in(WS_HC_RNG2, h->xray_rng, fb, stream, &status) : NULL;
     if (status) return status;
     const int out_dim[3] = {s->hii_dim, s->hii_dim, s->hii_dim_z};
     int *bins = (int *)c21hip_ws(WS_HC_BINS, c21hip_halo_deposit_scratch_ints(h->n_halos, out_dim) * sizeof(int));
@@ -92,9 +71,6 @@ static int deposit_halos(const c21cm_halobox_spec *s, const float *const vel[3],
 }
 
 /* USE_MINI_HALOS (HaloBox.c:245-283, map_mass.c:285-321) */
-enum { WS_HBM_MTA = 217, WS_HBM_MTM, WS_HBM_TAB, WS_HBM_ACC3, WS_HBM_OUT4, WS_HBM_G12, WS_HBM_ZRE,
-       WS_HBM_J21, WS_HBM_VCB, WS_HBM_OUTA, WS_HBM_OUTM, WS_HBM_SUMS };
-
 static int halobox_grids_mini(const c21cm_halobox_spec *s, const InitialConditions *ics,
                               HaloBox *grids, void *stream) {
     int status = 0;
@@ -120,14 +96,14 @@ static int halobox_grids_mini(const c21cm_halobox_spec *s, const InitialConditio
         c21hip_set_error("halobox: required InitialConditions arrays are missing");
         return C21CM_VALUE_ERROR;
     }
-    const float *dens = hb_in(WS_HB_IN0, ics->lowres_density, fb, stream, &status);
+    const float *dens = c21_stage_in(WS_HB_IN0, ics->lowres_density, fb, stream, &status);
     const float *vel[3], *vel2[3] = {NULL, NULL, NULL};
     for (int a = 0; a < 3; a++) {
-        vel[a] = hb_in(WS_HB_IN0 + 1 + a, vel_h[a], fb, stream, &status);
-        if (s->lpt2) vel2[a] = hb_in(WS_HB_IN0 + 4 + a, vel2_h[a], fb, stream, &status);
+        vel[a] = c21_stage_in(WS_HB_IN0 + 1 + a, vel_h[a], fb, stream, &status);
+        if (s->lpt2) vel2[a] = c21_stage_in(WS_HB_IN0 + 4 + a, vel2_h[a], fb, stream, &status);
     }
-    const float *mta = hb_in(WS_HBM_MTA, s->log10_mturn_acg, fb, stream, &status);
-    const float *mtm = hb_in(WS_HBM_MTM, s->log10_mturn_mcg, fb, stream, &status);
+    const float *mta = c21_stage_in(WS_HBM_MTA, s->log10_mturn_acg, fb, stream, &status);
+    const float *mtm = c21_stage_in(WS_HBM_MTM, s->log10_mturn_mcg, fb, stream, &status);
     if (status) return status;
     const int xray = grids->halo_xray && (integral ? s->ln_xray_table2d != NULL
                                                     : (s->halo_consts && s->halo_consts->use_xray));
@@ -205,10 +181,10 @@ int c21cm_halobox_turnovers(const c21cm_mturn_spec *m, double m_turn, int below_
         return C21CM_VALUE_ERROR;
     }
     const size_t n = (size_t)m->hii_dim * m->hii_dim * m->hii_dim_z, fb = n * sizeof(float);
-    const float *g12 = below_z_heat_max ? hb_in(WS_HBM_G12, prev_G12, fb, stream, &status) : NULL;
-    const float *zre = below_z_heat_max ? hb_in(WS_HBM_ZRE, prev_z_reion, fb, stream, &status) : NULL;
-    const float *j21 = below_z_heat_max ? hb_in(WS_HBM_J21, J_21_LW, fb, stream, &status) : NULL;
-    const float *v = vcb ? hb_in(WS_HBM_VCB, vcb, fb, stream, &status) : NULL;
+    const float *g12 = below_z_heat_max ? c21_stage_in(WS_HBM_G12, prev_G12, fb, stream, &status) : NULL;
+    const float *zre = below_z_heat_max ? c21_stage_in(WS_HBM_ZRE, prev_z_reion, fb, stream, &status) : NULL;
+    const float *j21 = below_z_heat_max ? c21_stage_in(WS_HBM_J21, J_21_LW, fb, stream, &status) : NULL;
+    const float *v = vcb ? c21_stage_in(WS_HBM_VCB, vcb, fb, stream, &status) : NULL;
     if (status) return status;
     float *oa = c21hip_is_device_ptr(log10_mturn_acg) ? log10_mturn_acg : (float *)c21hip_ws(WS_HBM_OUTA, fb);
     float *om = c21hip_is_device_ptr(log10_mturn_mcg) ? log10_mturn_mcg : (float *)c21hip_ws(WS_HBM_OUTM, fb);
@@ -265,11 +241,11 @@ int c21cm_halobox_grids(const c21cm_halobox_spec *s, const InitialConditions *ic
         c21hip_set_error("halobox: required InitialConditions arrays are missing");
         return C21CM_VALUE_ERROR;
     }
-    const float *dens = hb_in(WS_HB_IN0, dens_h, n_src * sizeof(float), stream, &status);
+    const float *dens = c21_stage_in(WS_HB_IN0, dens_h, n_src * sizeof(float), stream, &status);
     const float *vel[3], *vel2[3] = {NULL, NULL, NULL};
     for (int a = 0; a < 3; a++) {
-        vel[a] = hb_in(WS_HB_IN0 + 1 + a, vel_h[a], n_src * sizeof(float), stream, &status);
-        if (s->lpt2) vel2[a] = hb_in(WS_HB_IN0 + 4 + a, vel2_h[a], n_src * sizeof(float), stream, &status);
+        vel[a] = c21_stage_in(WS_HB_IN0 + 1 + a, vel_h[a], n_src * sizeof(float), stream, &status);
+        if (s->lpt2) vel2[a] = c21_stage_in(WS_HB_IN0 + 4 + a, vel2_h[a], n_src * sizeof(float), stream, &status);
     }
     if (status) return status;
     const int xray = grids->halo_xray && (integral ? s->ln_xray_table != NULL

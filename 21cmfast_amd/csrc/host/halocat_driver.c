@@ -10,8 +10,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-enum { WS_PH_IN = 293, WS_PH_OUT = 294, WS_PH_GRIDS = 295 };
-
 #define TRY(expr)         \
     do {                  \
         int st_ = (expr); \

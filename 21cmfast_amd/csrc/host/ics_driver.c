@@ -17,17 +17,11 @@
 
 #define L_FACTOR 0.620350491 /* reference: src/py21cmfast/src/Constants.c:41 */
 
-enum {
-    WS_IC_BOX = 50,
-    WS_IC_SAVED,
-    WS_IC_PHI,
-    WS_IC_DIAG0, /* +1, +2 */
-    WS_IC_PK = 55,
-    WS_IC_IN = 56,
-    WS_IC_OUT0 = 57, /* staged outputs, reused one at a time */
-    WS_IC_DEVIATES = 58,
-    WS_IC_VCBTAB = 59
-};
+/* the slot ranges this file indexes: three diagonals; three derivatives of each kind; up to four folded spectra of
+ * one fold, the first in WS_IS_LO */
+_Static_assert(WS_IC_DIAG_LAST - WS_IC_DIAG0 == 2 && WS_IS_D_LAST - WS_IS_D0 == 2 && WS_IS_O_LAST - WS_IS_O0 == 2 &&
+                   WS_IS_LO1_LAST - WS_IS_LO1 == 2,
+               "ics: slot ranges");
 
 #define TRY(expr)         \
     do {                  \
@@ -110,14 +104,6 @@ static int emit(const float *box, const int hi_dim[3], float *target, const int 
  * default configuration) is the small transform of the FOLDED spectrum (c21hip_split_fold)
  * instead of a DIM^3 transform followed by subsampling.  C21CM_ICS=padded selects the older
  * padded-layout pipeline below. */
-enum {
-    WS_IS_SAVED = 100, WS_IS_FILT, WS_IS_WORK, WS_IS_LO, WS_IS_LOWORK, WS_IS_BOX,
-    WS_IS_D0 = 106, /* 107, 108 */
-    WS_IS_O0 = 109, /* 110, 111 */
-    WS_IS_OUT = 112, WS_IS_IN = 113, WS_IS_PK2 = 114,
-    WS_IS_LO1 = 115 /* 116, 117: the folded spectra of one fused fold (lo_fields) */
-};
-
 typedef struct {
     const c21cm_ics_spec *s;
     int hi[3], lo[3], f;

@@ -25,86 +25,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-/* workspace slots */
-enum {
-    WS_DELTA_UNF = 0,
-    WS_DELTA_FIL,
-    WS_STARS_UNF,
-    WS_STARS_FIL,
-    WS_XE_UNF,
-    WS_XE_FIL,
-    WS_DENSITY,
-    WS_NION,
-    WS_XE_DENSE,
-    WS_TNEUTRAL,
-    WS_PREV_ZRE,
-    WS_XH,
-    WS_ZRE,
-    WS_TK,
-    WS_NION_DENSE,
-    WS_SCALARS,
-    WS_TABLE,
-    WS_FIRST_CROSS,
-    WS_DELTA_WORK,
-    WS_STARS_WORK,
-    WS_XE_WORK,
-    WS_PARTIALS,
-    WS_DEF_PARTIALS = 84,
-    WS_DELTA_WORK2 = 92, /* second radius of a two-radius sweep */
-    WS_STARS_WORK2 = 93,
-    WS_XE_WORK2 = 96,
-    WS_EUL_DFIL2 = 97, /* Eulerian table loop: second delta_R buffer, two dense x_e(R) buffers */
-    WS_EUL_XE0 = 98,
-    WS_EUL_XE1 = 99,
-    /* recombination models: filtered whalo_sfr and N_rec grids, staged arrays, rate tables */
-    WS_SFR_UNF = 120,
-    WS_SFR_FIL,
-    WS_SFR_WORK,
-    WS_NREC_UNF,
-    WS_NREC_FIL,
-    WS_NREC_WORK,
-    WS_WSFR,
-    WS_PREV_NREC,
-    WS_G12,
-    WS_MFP,
-    WS_NREC_OUT,
-    WS_RR_TABLES,
-    /* rank-local state of a sharded run with a recombination model */
-    WS_SH_XH,
-    WS_SH_ZRE,
-    WS_SH_G12,
-    WS_SH_MFP,
-    /* USE_MINI_HALOS: previous delta and the two turnover-mass grids (spectra, scratch, filtered),
-     * staged inputs, 2-D tables, per-radius f_coll history in and out */
-    WS_MINI_PD_UNF = 180,
-    WS_MINI_PD_WORK,
-    WS_MINI_PD_FIL,
-    WS_MINI_MTA_UNF,
-    WS_MINI_MTA_WORK,
-    WS_MINI_MTA_FIL,
-    WS_MINI_MTM_UNF,
-    WS_MINI_MTM_WORK,
-    WS_MINI_MTM_FIL,
-    WS_MINI_PDENS,
-    WS_MINI_MTA,
-    WS_MINI_MTM,
-    WS_MINI_TABLES,
-    WS_MINI_HIST_A,
-    WS_MINI_HIST_M,
-    WS_MINI_OUT_A,
-    WS_MINI_OUT_M,
-    WS_SPHERE_RSQ = 216,
-    WS_SFR_WORK2 = 246, /* fused recombination loop: whalo_sfr of the second radius of a sweep */
-    WS_R_DEV = 247,     /* float R per radius index (mean free path of a first crossing) */
-    WS_EUL_XEPEND = 253, /* banded barrier with an x_e grid: clipped x_e of the undecided cells (sparse) */
-    WS_NION_DENSE2 = 254, /* closed-form Eulerian loop: second dense f_coll buffer (deferred barrier) */
-    /* (256 and 257 are shard_rccl.c's: WS_SHARD_STATUS, WS_SHARD_SLABBITS) */
-    WS_NREC_WORK2 = 259, /* fused recombination loop with x_e AND a filtered N_rec: N_rec of the second radius */
-    WS_EUL_WORK3 = 261,   /* Eulerian table loop, two radii per pass-X sweep: the second set of k-space buffers */
-    WS_EUL_WORK4 = 262,
-    WS_ARENA = 258        /* experiment: the spectra of the two-grid loop out of one allocation (C21CM_ARENA) */
-};
-
 #define MAX_COPYBACK 12
 typedef struct {
     void *host[MAX_COPYBACK];
@@ -142,19 +62,6 @@ typedef struct {
             goto done;              \
         }                           \
     } while (0)
-
-static const float *stage_in(int slot, const float *p, size_t bytes, void *stream, int *status) {
-    if (!p || *status) return NULL;
-    if (c21hip_is_device_ptr(p)) return p;
-    void *d = c21hip_ws(slot, bytes);
-    if (!d) {
-        *status = C21CM_MEMORY_ALLOC_ERROR;
-        return NULL;
-    }
-    int st = c21hip_h2d(d, p, bytes, stream);
-    if (st) *status = st;
-    return (const float *)d;
-}
 
 /* in/out array: upload the caller's initial contents, remember to copy back */
 static float *stage_inout(int slot, float *p, size_t bytes, int upload, copyback_list *cb,
@@ -624,15 +531,15 @@ static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedFiel
     status = c21hip_memset(c->scalars, 0, SC_COUNT * sizeof(double), stream);
     if (status) return status;
 
-    c->density = stage_in(WS_DENSITY, pf->density, dbytes, stream, &status);
-    if (c->lagrangian) c->n_ion = stage_in(WS_NION, halos->n_ion, dbytes, stream, &status);
+    c->density = c21_stage_in(WS_DENSITY, pf->density, dbytes, stream, &status);
+    if (c->lagrangian) c->n_ion = c21_stage_in(WS_NION, halos->n_ion, dbytes, stream, &status);
     if (s->use_ts_fluct) {
-        c->xe_dense = stage_in(WS_XE_DENSE, ts->xray_ionised_fraction, dbytes, stream, &status);
+        c->xe_dense = c21_stage_in(WS_XE_DENSE, ts->xray_ionised_fraction, dbytes, stream, &status);
         if (!s->minimize_memory)
-            c->Tneutral = stage_in(WS_TNEUTRAL, ts->kinetic_temp_neutral, dbytes, stream, &status);
+            c->Tneutral = c21_stage_in(WS_TNEUTRAL, ts->kinetic_temp_neutral, dbytes, stream, &status);
     }
     if (!s->first_snapshot && prev && prev->z_reion)
-        c->prev_zre = stage_in(WS_PREV_ZRE, prev->z_reion, dbytes, stream, &status);
+        c->prev_zre = c21_stage_in(WS_PREV_ZRE, prev->z_reion, dbytes, stream, &status);
     if (!s->first_snapshot && !c->prev_zre && !status) {
         c21hip_set_error("ionize: previous z_reion is required after the first snapshot");
         return C21CM_VALUE_ERROR;
@@ -651,11 +558,11 @@ static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedFiel
             return C21CM_VALUE_ERROR;
         }
         const size_t hbytes = dbytes * (size_t)s->n_radii; /* one grid per radius (:783-784) */
-        c->prev_density = stage_in(WS_MINI_PDENS, s->prev_density, dbytes, stream, &status);
-        c->mta_dense = stage_in(WS_MINI_MTA, s->log10_mturn_acg, dbytes, stream, &status);
-        c->mtm_dense = stage_in(WS_MINI_MTM, s->log10_mturn_mcg, dbytes, stream, &status);
-        c->hist_a = stage_in(WS_MINI_HIST_A, prev->unnormalised_nion, hbytes, stream, &status);
-        c->hist_m = stage_in(WS_MINI_HIST_M, prev->unnormalised_nion_mini, hbytes, stream, &status);
+        c->prev_density = c21_stage_in(WS_MINI_PDENS, s->prev_density, dbytes, stream, &status);
+        c->mta_dense = c21_stage_in(WS_MINI_MTA, s->log10_mturn_acg, dbytes, stream, &status);
+        c->mtm_dense = c21_stage_in(WS_MINI_MTM, s->log10_mturn_mcg, dbytes, stream, &status);
+        c->hist_a = c21_stage_in(WS_MINI_HIST_A, prev->unnormalised_nion, hbytes, stream, &status);
+        c->hist_m = c21_stage_in(WS_MINI_HIST_M, prev->unnormalised_nion_mini, hbytes, stream, &status);
         c->nion_all = stage_inout(WS_MINI_OUT_A, box->unnormalised_nion, hbytes, 0, &c->cb, stream,
                                   &status);
         c->mini_all = stage_inout(WS_MINI_OUT_M, box->unnormalised_nion_mini, hbytes, 0, &c->cb,
@@ -670,10 +577,10 @@ static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedFiel
             return C21CM_VALUE_ERROR;
         }
         const size_t rbytes = c->inhomo ? dbytes : sizeof(float); /* homogeneous: one number */
-        c->prev_nrec = stage_in(WS_PREV_NREC, prev->cumulative_recombinations, rbytes, stream,
-                                &status);
+        c->prev_nrec = c21_stage_in(WS_PREV_NREC, prev->cumulative_recombinations, rbytes, stream,
+                                    &status);
         if (c->lagrangian)
-            c->whalo_sfr = stage_in(WS_WSFR, halos->whalo_sfr, dbytes, stream, &status);
+            c->whalo_sfr = c21_stage_in(WS_WSFR, halos->whalo_sfr, dbytes, stream, &status);
         if (need_outputs) {
             /* Gamma_12 / mean free path keep the caller's values where no barrier is crossed */
             c->G12 = stage_inout(WS_G12, box->ionisation_rate_G12, dbytes, 1, &c->cb, stream,
@@ -2922,11 +2829,11 @@ int c21cm_neutral_box(const c21cm_ionize_spec *spec, const PerturbedField *pertu
         return C21CM_VALUE_ERROR;
     }
     if (ts) {
-        xe = stage_in(WS_XE_DENSE, spin_temp->xray_ionised_fraction, bytes, stream, &status);
+        xe = c21_stage_in(WS_XE_DENSE, spin_temp->xray_ionised_fraction, bytes, stream, &status);
         if (!spec->minimize_memory)
-            Tn = stage_in(WS_TNEUTRAL, spin_temp->kinetic_temp_neutral, bytes, stream, &status);
+            Tn = c21_stage_in(WS_TNEUTRAL, spin_temp->kinetic_temp_neutral, bytes, stream, &status);
     } else if (!spec->minimize_memory) {
-        density = stage_in(WS_DENSITY, perturbed_field->density, bytes, stream, &status);
+        density = c21_stage_in(WS_DENSITY, perturbed_field->density, bytes, stream, &status);
     }
     float *xH = stage_inout(WS_XH, box->neutral_fraction, bytes, 0, &cb, stream, &status);
     float *zre = stage_inout(WS_ZRE, box->z_reion, bytes, 0, &cb, stream, &status);
@@ -2950,8 +2857,6 @@ int c21cm_mturn_grids(const c21cm_mturn_spec *spec, const float *prev_G12,
                       const float *prev_z_reion, const float *J_21_LW, const float *vcb,
                       float *log10_mturn_acg, float *log10_mturn_mcg, double *ave_acg,
                       double *ave_mcg, void *stream) {
-    enum { WS_MT_G12 = 197, WS_MT_ZRE, WS_MT_J21, WS_MT_VCB, WS_MT_OUT_A, WS_MT_OUT_M, WS_MT_SC,
-           WS_MT_PART };
     int status = 0;
     if (!spec || !prev_G12 || !J_21_LW || !log10_mturn_acg || !log10_mturn_mcg ||
         (!spec->first_snapshot && !prev_z_reion) || spec->hii_dim < 1 || spec->hii_dim_z < 1) {
@@ -2963,12 +2868,12 @@ int c21cm_mturn_grids(const c21cm_mturn_spec *spec, const float *prev_G12,
     const size_t dbytes = ntot * sizeof(float);
     copyback_list cb;
     cb.n = 0;
-    const float *g12 = stage_in(WS_MT_G12, prev_G12, dbytes, stream, &status);
+    const float *g12 = c21_stage_in(WS_MT_G12, prev_G12, dbytes, stream, &status);
     const float *zre = spec->first_snapshot
                            ? NULL
-                           : stage_in(WS_MT_ZRE, prev_z_reion, dbytes, stream, &status);
-    const float *j21 = stage_in(WS_MT_J21, J_21_LW, dbytes, stream, &status);
-    const float *v = vcb ? stage_in(WS_MT_VCB, vcb, dbytes, stream, &status) : NULL;
+                           : c21_stage_in(WS_MT_ZRE, prev_z_reion, dbytes, stream, &status);
+    const float *j21 = c21_stage_in(WS_MT_J21, J_21_LW, dbytes, stream, &status);
+    const float *v = vcb ? c21_stage_in(WS_MT_VCB, vcb, dbytes, stream, &status) : NULL;
     float *out_a = stage_inout(WS_MT_OUT_A, log10_mturn_acg, dbytes, 0, &cb, stream, &status);
     float *out_m = stage_inout(WS_MT_OUT_M, log10_mturn_mcg, dbytes, 0, &cb, stream, &status);
     double *sc = (double *)c21hip_ws(WS_MT_SC, 4 * sizeof(double));

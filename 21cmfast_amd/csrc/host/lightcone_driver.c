@@ -14,8 +14,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-enum { WS_LC_TAB = 270, WS_LC_BOXES = 271, WS_LC_SLAB = 272, WS_LC_HUBBLE = 273, WS_LC_DVDR = 274 };
-
 #define TRY(expr)         \
     do {                  \
         int st_ = (expr); \

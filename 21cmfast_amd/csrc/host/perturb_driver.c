@@ -18,15 +18,11 @@
 
 #define L_FACTOR 0.620350491 /* reference: src/py21cmfast/src/Constants.c:41 */
 
-enum {
-    WS_PT_LOW = 20,
-    WS_PT_HIGH,
-    WS_PT_SAVED,
-    WS_PT_RESAMPLED,
-    WS_PT_IN0, /* .. +7 staged IC arrays */
-    WS_PT_OUT0 = 32, /* .. +3 staged outputs */
-    WS_PT_SPLIT = 89 /* .. +2 split-layout spectra */
-};
+/* the slot ranges this file indexes: density + 3 velocities + 3 2LPT velocities in; density + 3 velocities out;
+ * spectrum, work copy, saved delta_k */
+_Static_assert(WS_PT_IN_LAST - WS_PT_IN0 == 6 && WS_PT_OUT_LAST - WS_PT_OUT0 == 3 &&
+                   WS_PT_SPLIT_LAST - WS_PT_SPLIT == 2,
+               "perturb: staging slot ranges");
 
 /* C21CM_PT=padded keeps the k-space part of the low-resolution branch on the padded layout */
 static int pt_split_supported(const int lo_dim[3]) {
@@ -44,19 +40,6 @@ static int pt_split_supported(const int lo_dim[3]) {
             goto done;    \
         }                 \
     } while (0)
-
-static const float *stage_in(int slot, const float *p, size_t bytes, void *stream, int *status) {
-    if (!p || *status) return NULL;
-    if (c21hip_is_device_ptr(p)) return p;
-    void *d = c21hip_ws(slot, bytes);
-    if (!d) {
-        *status = C21CM_MEMORY_ALLOC_ERROR;
-        return NULL;
-    }
-    int st = c21hip_h2d(d, p, bytes, stream);
-    if (st) *status = st;
-    return (const float *)d;
-}
 
 int c21cm_perturb_grids(const c21cm_perturb_spec *s, const InitialConditions *ics,
                         PerturbedField *pf, void *stream) {
@@ -110,19 +93,19 @@ int c21cm_perturb_grids(const c21cm_perturb_spec *s, const InitialConditions *ic
 
     /* ---- make_density_grid */
     if (linear) {
-        const float *d = stage_in(WS_PT_IN0, dens_box_h, b_tot * sizeof(float), stream, &status);
+        const float *d = c21_stage_in(WS_PT_IN0, dens_box_h, b_tot * sizeof(float), stream, &status);
         if (status) return status;
         TRY(c21hip_scale_pack(d, grid, box_dim[0], box_dim[1], box_dim[2], s->growth_factor,
                               stream));
     } else {
         const float *d_dens =
-            stage_in(WS_PT_IN0, ics->hires_density, hi_tot * sizeof(float), stream, &status);
+            c21_stage_in(WS_PT_IN0, ics->hires_density, hi_tot * sizeof(float), stream, &status);
         const float *vel[3], *vel2[3] = {NULL, NULL, NULL};
         for (int a = 0; a < 3; a++) {
-            vel[a] = stage_in(WS_PT_IN0 + 1 + a, vel_h[a], b_tot * sizeof(float), stream, &status);
+            vel[a] = c21_stage_in(WS_PT_IN0 + 1 + a, vel_h[a], b_tot * sizeof(float), stream, &status);
             if (lpt2)
-                vel2[a] = stage_in(WS_PT_IN0 + 4 + a, vel2_h[a], b_tot * sizeof(float), stream,
-                                   &status);
+                vel2[a] = c21_stage_in(WS_PT_IN0 + 4 + a, vel2_h[a], b_tot * sizeof(float), stream,
+                                       &status);
         }
         if (status) return status;
         double *resampled = (double *)c21hip_ws(WS_PT_RESAMPLED, b_tot * sizeof(double));

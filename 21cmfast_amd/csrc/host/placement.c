@@ -45,7 +45,7 @@
  * says so in its line), =force / 2 also with other tenants; C21CM_WS_TRACE=1 prints the candidates;
  * c21cm_placement_report() tells what the last call decided and what it cost. */
 
-enum { PLACE_SLOTS = 384, MAXH = 128, PLACE_VMM_DEFAULT = 1 };
+enum { MAXH = 128, PLACE_VMM_DEFAULT = 1 };
 enum {
     PL_PLACED = 0,       /* a faster region was found and adopted */
     PL_OFF = 1,          /* C21CM_WS_PLACE=0 / no partner / small buffer */
@@ -62,7 +62,7 @@ typedef struct {
     int decided, mode_gen;
     size_t failed_bytes; /* a walk for this size found nothing */
 } place_rec;
-static place_rec g_rec[PLACE_SLOTS];
+static place_rec g_rec[WS_COUNT];
 static struct {
     int outcome, probes, tenants, walks, slot;
     double held_gb, wall_ms;
@@ -137,7 +137,7 @@ float *c21_place_work_partner(int slot_partner, int slot_new, size_t bytes, int 
     size_t have = 0, phave = 0;
     float *cur = (float *)c21hip_ws_peek(slot_new, &have);
     float *partner = (float *)c21hip_ws_peek(slot_partner, &phave);
-    place_rec *rec = (slot_new >= 0 && slot_new < PLACE_SLOTS) ? &g_rec[slot_new] : NULL;
+    place_rec *rec = (slot_new >= 0 && slot_new < WS_COUNT) ? &g_rec[slot_new] : NULL;
     if (cur && have >= bytes &&
         (!rec || (rec->decided && rec->mode_gen == g_mode_gen && rec->ptr == (void *)cur && rec->partner == (void *)partner)))
         return cur; /* the decision taken for this pair of buffers stands */

@@ -12,9 +12,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-/* slot ids after angular_driver.c's 280-286; runtime.hip allows ids below 296 */
-enum { WS_PW_TAB = 288, WS_PW_IN = 289, WS_PW_PAD = 290, WS_PW_SUMS = 291, WS_PW_FLAG = 292 };
-
 /* half-spectrum modes one workgroup aims for (at most), and workgroups a launch aims for (at least) */
 #define PW_MODES_PER_WG 32768
 #define PW_MIN_WGS 1024

@@ -13,9 +13,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-/* slot ids after lightcone_driver.c's 270-274; runtime.hip allows ids below 288 */
-enum { WS_RSD_SCALE = 275, WS_RSD_IN = 276, WS_RSD_OUT = 277, WS_RSD_FLAG = 278, WS_RSD_VEL = 279 };
-
 /* LDS a launch aims for: two workgroups per CU */
 #define RSD_LDS_TARGET (80 * 1024)
 

@@ -104,12 +104,6 @@ static struct {
     const char *(*error_string)(int);
 } R;
 
-/* (256 and 257 are this file's; ionize_driver.c holds 258 and 259 -- each file's enum names the other's.
- * 253 collided with the Eulerian loop's sparse x_e buffer,
- * whose reallocation freed the status word a rank out of memory still needs -- ADVICE r4) */
-enum { WS_SHARD_GRID = 140, WS_SHARD_STAGE = 141, WS_SHARD_SCALARS = 142, WS_SHARD_BITS = 143,
-       WS_SHARD_STATUS = 256, WS_SHARD_SLABBITS = 257 };
-
 static int rccl_check(int rc, const char *what);
 
 /* The exchange of the uint8 first-crossing grid.  The finish phase only tests it for non-zero,
@@ -168,7 +162,6 @@ static int exchange_mask(unsigned char *fc, unsigned *bits, size_t ntot, int own
  *      receives its own slab from everybody; c21hip_combine_cross_g12 keeps the winners;
  *   2. the finishing rank receives every combined slab in place.
  * Slab bounds as for the TsBox sums (multiples of 4 cells). */
-enum { WS_SHARD_RC_MASK = 248, WS_SHARD_RC_G12 = 249 };
 static int agree_status(int st_local, void *stream);
 static size_t rc_slab_maxlen(size_t ntot, int world) {
     size_t maxlen = 0;
@@ -849,7 +842,6 @@ int c21cm_ionize_sharded(const c21cm_ionize_spec *spec, const PerturbedField *pe
  * boxes (again one message per peer and box).  Volumes at 512^3, 8 ranks, 4 rows: 537 MB per link
  * for the sums in double (C21CM_TS_SHARD_EXCHANGE=f32: partials as floats scaled by a per-row power of two
  * -- the rows are rates of 1e27 .. 1e49 --, 268 MB), 3 x 67 MB per link for the outputs. */
-enum { WS_TSS_SUMS = 242, WS_TSS_SEND = 243, WS_TSS_RECV = 244, WS_TSS_SLAB = 245, WS_TSS_ROWMAX = 260 };
 
 /* how many times this process took the sharded ComputeTsBox (tests: did the call shard?) */
 static int g_ts_sharded_calls;

@@ -18,16 +18,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-/* slots 150-169 (0-143 belong to the other drivers) */
-enum {
-    WS_TS_DENS = 150, WS_TS_PTS, WS_TS_PTK, WS_TS_PXE, WS_TS_GRID_A, WS_TS_GRID_B, WS_TS_TAB,
-    WS_TS_SFRDTAB, WS_TS_LYA_C, WS_TS_LYA_I, WS_TS_OTS, WS_TS_OTK, WS_TS_OXE, WS_TS_PART,
-    WS_TS_SMALL, WS_TS_MEANSFR, WS_TS_SFRDTAB2, WS_TS_SUMS
-};
-/* USE_MINI_HALOS: 2-D tables, filtered turnover grids, mini shell rows, J_21_LW staging */
-enum { WS_TS_MINI_TAB = 208, WS_TS_MINI_MCRIT, WS_TS_MINI_SHELL, WS_TS_MINI_J21, WS_TS_MINI_MEAN,
-       WS_TS_MCRIT_J21, WS_TS_MCRIT_VCB, WS_TS_MCRIT_OUT };
-
 #define TRY(expr)         \
     do {                  \
         int st_ = (expr); \
@@ -36,18 +26,6 @@ enum { WS_TS_MINI_TAB = 208, WS_TS_MINI_MCRIT, WS_TS_MINI_SHELL, WS_TS_MINI_J21,
             goto done;    \
         }                 \
     } while (0)
-
-static const void *stage_in(int slot, const void *p, size_t bytes, void *stream, int *status) {
-    if (*status || !p || c21hip_is_device_ptr(p)) return p;
-    void *d = c21hip_ws(slot, bytes);
-    if (!d) {
-        c21hip_set_error("spin temperature: out of device memory staging %zu bytes", bytes);
-        *status = C21CM_MEMORY_ALLOC_ERROR;
-        return NULL;
-    }
-    *status = c21hip_h2d(d, p, bytes, stream);
-    return d;
-}
 
 /* a per-shell table set: copied with one float of slack, because upstream's lookup reads y[idx + 1]
  * with weight 0 when a cell sits exactly on the last knot (interpolation.c:123-131) */
@@ -233,26 +211,26 @@ static int ts_grids_impl(const c21cm_ts_spec *s, const float *density, const TsB
     }
     if (s->use_lya_heating) {
         const size_t lb = (size_t)C21CM_LYA_NT * C21CM_LYA_NT * C21CM_LYA_NGP * sizeof(double);
-        lya_c = (const double *)stage_in(WS_TS_LYA_C, s->lya_dEC, lb, stream, &status);
-        lya_i = (const double *)stage_in(WS_TS_LYA_I, s->lya_dEI, lb, stream, &status);
+        lya_c = c21_stage_in(WS_TS_LYA_C, s->lya_dEC, lb, stream, &status);
+        lya_i = c21_stage_in(WS_TS_LYA_I, s->lya_dEI, lb, stream, &status);
     }
     if (status) goto done;
 
     /* ---- grids */
-    const float *d_dens = (const float *)stage_in(WS_TS_DENS, density, bytes, stream, &status);
-    const float *d_pts = (const float *)stage_in(WS_TS_PTS, previous->spin_temperature, bytes, stream, &status);
-    const float *d_ptk = (const float *)stage_in(WS_TS_PTK, previous->kinetic_temp_neutral, bytes, stream, &status);
-    const float *d_pxe = (const float *)stage_in(WS_TS_PXE, previous->xray_ionised_fraction, bytes, stream, &status);
+    const float *d_dens = c21_stage_in(WS_TS_DENS, density, bytes, stream, &status);
+    const float *d_pts = c21_stage_in(WS_TS_PTS, previous->spin_temperature, bytes, stream, &status);
+    const float *d_ptk = c21_stage_in(WS_TS_PTK, previous->kinetic_temp_neutral, bytes, stream, &status);
+    const float *d_pxe = c21_stage_in(WS_TS_PXE, previous->xray_ionised_fraction, bytes, stream, &status);
     if (mode == 2) { /* the slab [cell0, cell0 + ncell) of device arrays */
         d_dens += cell0, d_pts += cell0, d_ptk += cell0, d_pxe += cell0;
     }
     const float *grid_a = NULL, *grid_b = NULL;
     if (mode != 2 && !s->no_light) {
         if (lagrangian) {
-            grid_a = (const float *)stage_in(WS_TS_GRID_A, source_box->filtered_sfr, bytes * n, stream, &status);
-            grid_b = (const float *)stage_in(WS_TS_GRID_B, source_box->filtered_xray, bytes * n, stream, &status);
+            grid_a = c21_stage_in(WS_TS_GRID_A, source_box->filtered_sfr, bytes * n, stream, &status);
+            grid_b = c21_stage_in(WS_TS_GRID_B, source_box->filtered_xray, bytes * n, stream, &status);
         } else {
-            grid_a = (const float *)stage_in(WS_TS_GRID_A, filtered_density, bytes * n, stream, &status);
+            grid_a = c21_stage_in(WS_TS_GRID_A, filtered_density, bytes * n, stream, &status);
         }
     }
     float *o_ts = stage_out(WS_TS_OTS, out->spin_temperature, bytes, &status);
@@ -326,14 +304,13 @@ static int ts_grids_impl(const c21cm_ts_spec *s, const float *density, const TsB
                 for (int i = 0; i < n; i++) rows[r * n + i] = src[r] ? src[r][i] : 1.;
             TRY(c21hip_h2d(mini_shell, rows, (size_t)C21HIP_TS_MINI_ROWS * n * sizeof(double), stream));
             TRY(c21hip_sync(stream)); /* `rows` is a stack buffer */
-            const float *g_mini = (const float *)stage_in(WS_TS_MINI_MCRIT, source_box->filtered_sfr_mini,
-                                                          bytes * n, stream, &status);
+            const float *g_mini = c21_stage_in(WS_TS_MINI_MCRIT, source_box->filtered_sfr_mini, bytes * n, stream,
+                                               &status);
             const float *g_lw = NULL, *g_mini_lw = NULL;
             if (source_box->filtered_sfr_lw && source_box->filtered_sfr_mini_lw) {
-                g_lw = (const float *)stage_in(WS_TS_MINI_TAB, source_box->filtered_sfr_lw, bytes * n,
-                                               stream, &status);
-                g_mini_lw = (const float *)stage_in(WS_TS_MINI_MEAN, source_box->filtered_sfr_mini_lw,
-                                                    bytes * n, stream, &status);
+                g_lw = c21_stage_in(WS_TS_MINI_TAB, source_box->filtered_sfr_lw, bytes * n, stream, &status);
+                g_mini_lw = c21_stage_in(WS_TS_MINI_MEAN, source_box->filtered_sfr_mini_lw, bytes * n, stream,
+                                         &status);
             }
             if (status) goto done;
             TRY(c21hip_ts_accumulate_grids_mini(&a, d_pxe, grid_a, grid_b, g_mini, g_lw, g_mini_lw,
@@ -354,8 +331,8 @@ static int ts_grids_impl(const c21cm_ts_spec *s, const float *density, const TsB
                 TRY(c21hip_d2d(tab2, s->ln_sfrd_tables_mini, t2b, stream));
             else
                 TRY(c21hip_h2d(tab2, s->ln_sfrd_tables_mini, t2b, stream));
-            const float *d_mcrit = (const float *)stage_in(WS_TS_MINI_MCRIT, s->filtered_log10_mcrit,
-                                                           bytes * n, stream, &status);
+            const float *d_mcrit = c21_stage_in(WS_TS_MINI_MCRIT, s->filtered_log10_mcrit, bytes * n, stream,
+                                                &status);
             if (status) goto done;
             double rows[(C21HIP_TS_MINI_ROWS + 2) * C21CM_MAX_TS_RADII];
             const double *src[C21HIP_TS_MINI_ROWS] = {
@@ -438,7 +415,7 @@ int c21cm_ts_first_grids(const c21cm_ts_first_spec *s, const float *density, TsB
         return C21CM_IO_ERROR;
     }
     const size_t ntot = (size_t)s->hii_dim * s->hii_dim * s->hii_dim_z, bytes = ntot * sizeof(float);
-    const float *d_dens = (const float *)stage_in(WS_TS_DENS, density, bytes, stream, &status);
+    const float *d_dens = c21_stage_in(WS_TS_DENS, density, bytes, stream, &status);
     float *o_ts = stage_out(WS_TS_OTS, out->spin_temperature, bytes, &status);
     float *o_tk = stage_out(WS_TS_OTK, out->kinetic_temp_neutral, bytes, &status);
     float *o_xe = stage_out(WS_TS_OXE, out->xray_ionised_fraction, bytes, &status);
@@ -462,8 +439,8 @@ int c21cm_ts_mcrit_grid(const c21cm_mturn_spec *spec, double m_turn, const float
     }
     const size_t ntot = (size_t)spec->hii_dim * spec->hii_dim * spec->hii_dim_z;
     const size_t bytes = ntot * sizeof(float);
-    const float *j21 = (const float *)stage_in(WS_TS_MCRIT_J21, J_21_LW, bytes, stream, &status);
-    const float *v = vcb ? (const float *)stage_in(WS_TS_MCRIT_VCB, vcb, bytes, stream, &status) : NULL;
+    const float *j21 = c21_stage_in(WS_TS_MCRIT_J21, J_21_LW, bytes, stream, &status);
+    const float *v = vcb ? c21_stage_in(WS_TS_MCRIT_VCB, vcb, bytes, stream, &status) : NULL;
     float *o = stage_out(WS_TS_MCRIT_OUT, log10_mcrit, bytes, &status);
     if (status) goto done;
     TRY(c21hip_ts_mcrit_grid(j21, v, spec->vcb_const, spec->redshift, spec->A_LW, spec->BETA_LW,

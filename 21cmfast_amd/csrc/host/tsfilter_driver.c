@@ -16,9 +16,6 @@
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
 
-/* slots 0-63 belong to the other drivers */
-enum { WS_TF_IN = 64, WS_TF_UNF, WS_TF_WORK, WS_TF_OUT, WS_TF_PART, WS_TF_UNF2, WS_TF_WORK2, WS_TF_IN2, WS_TF_OUT2, WS_TF_RPART };
-
 #define TRY(expr)         \
     do {                  \
         int st_ = (expr); \
@@ -95,17 +92,6 @@ static int tf_window(tf_ctx *c, int filter_type, float R, float R_param, int app
     if ((st = c21hip_fft_c2r(c->work, c->nx, c->ny, c->nz, c->stream))) return st;
     return c21hip_floor_scale_stats(c->work, 2 * (long)(c->nz / 2 + 1), d_out, c->nx, c->ny, c->nz,
                                     min_value, const_factor, c->partials, stats3, c->stream);
-}
-
-static const float *tf_stage_in(const float *p, size_t bytes, void *stream, int *status) {
-    if (*status || c21hip_is_device_ptr(p)) return p;
-    void *d = c21hip_ws(WS_TF_IN, bytes);
-    if (!d) {
-        *status = C21CM_MEMORY_ALLOC_ERROR;
-        return NULL;
-    }
-    *status = c21hip_h2d(d, p, bytes, stream);
-    return (const float *)d;
 }
 
 /* Native sizes: the W(kR) table of radius r+1 is built on the library's side stream while
@@ -247,7 +233,7 @@ int c21cm_fill_Rbox_grids(const c21cm_rbox_spec *s, const float *input, float *r
     tf_ctx c;
     TRY(tf_setup(&c, s->hii_dim, s->hii_dim_z, s->box_len, s->box_len_z, s->n_R, stream));
     const size_t bytes = c.ntot * sizeof(float);
-    const float *d_in = tf_stage_in(input, bytes, stream, &status);
+    const float *d_in = c21_stage_in(WS_TF_IN, input, bytes, stream, &status);
     if (status) return status;
     const int host_out = !c21hip_is_device_ptr(result);
     float *stage_out = host_out ? (float *)c21hip_ws(WS_TF_OUT, bytes) : NULL;
