@@ -279,6 +279,18 @@ int c21hip_split_z_ionise_stars_xe(const float *delta_work, const float *stars_w
                                    int r_index, double rhocrit_omb, double ion_eff,
                                    int mass_dep_zeta, double f_limit, void *stream);
 int c21hip_z_ionise_xe_supported(int nx, int ny, int nz);
+/* Crossing bits: the two-grid fused pass Z on 512-point z-lines writes this radius' barrier outcome as
+ * one bit per cell into its own plane (nx*ny*nz/8 bytes, write only) instead of updating the uint8
+ * mask; c21hip_resolve_crossings turns the planes of the radii r_hi ... r_lo (the plane of radius r at
+ * bits + (r - 1) * nlines * 16 words) into first_cross[nlines][512], every byte written.  The bit order
+ * is private to the two kernels.  C21CM_CROSS_BITS=0: _supported returns 0 (the mask path). */
+int c21hip_z_cross_bits_supported(int nx, int ny, int nz);
+int c21hip_split_z_ionise_stars_bits(const float *delta_work, const float *stars_work,
+                                     unsigned *cross_plane, double *partials, double *sum_out, int nx,
+                                     int ny, int nz, int r_index, double rhocrit_omb, double ion_eff,
+                                     int mass_dep_zeta, double f_limit, void *stream);
+int c21hip_resolve_crossings(const unsigned *bits, int r_hi, int r_lo, unsigned char *first_cross,
+                             size_t nlines, void *stream);
 /* passes X, Y of one grid with window a of the two-grid tables in buffer table_slot */
 int c21hip_split_filter_xy_shared(const float *src, float *work, int filter_type, int nx, int ny,
                                   int nz, double box_len, double box_len_z, float R, int apply,

@@ -1921,6 +1921,13 @@ struct ZFusedArgs {
     const float2 *s_main, *s_nyq;  // filtered emissivity spectrum
     const float2 *x_main, *x_nyq;  // filtered x_e spectrum (USE_TS_FLUCT; wave-level kernel only)
     unsigned char *first_cross;    // [lines][NZ]
+    // Crossing bits (zw_ionise_kernel<16, false, 16, false, true> only; first_cross is not touched then):
+    // this radius' own plane, [lines][16] words, one bit per cell, set where the barrier holds.  Every
+    // launch writes every word and reads none; resolve_crossings_kernel (ionize_kernels.hip) turns the
+    // planes of all radii into first_cross after the loop.  Bit order, private to the two kernels: word
+    // b of a line is what lane b of the line holds after wave_c2r<16, 16> -- bit q is cell 32 q + 2 b,
+    // bit 16 + q is cell 32 q + 2 b + 1 (q = 0..15).
+    unsigned *cross_bits;
     double *partials;              // one per workgroup (nx*ny/LZ_FUSED)
     double rhocrit_omb, ion_eff, f_limit;
     int mass_dep_zeta, r_index;
@@ -2280,7 +2287,8 @@ constexpr int zw_lines(int P) { return kBlock / P; }
 // Fused pass Z + f_coll sum + barrier, wave-level transform (A = 16 or 32, see wave_c2r).
 // TS: a third grid, the filtered x_e of the spin-temperature run, enters the barrier as
 // f_coll zeta > 1 - x_e (IonisationBox.c:1118, clip of :1091-1094).
-template <int A, bool TS, int P = 16, bool RC = false>
+// CB: the barrier's outcome goes to a.cross_bits (one bit per cell, write only) instead of the mask.
+template <int A, bool TS, int P = 16, bool RC = false, bool CB = false>
 __global__ void
 #if C21X_ZW_OCC
 __launch_bounds__(kBlock, (A == 16 && !TS) ? C21X_ZW_OCC : 1)
@@ -2310,6 +2318,7 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
     float2 *L = lines + lw * LINE_LDS;
     const float2 *dm = a.d_main + line * H, *sm = a.s_main + line * H;
     constexpr bool EARLY = (A == 16) && !C21X_ZW_LATE;
+    static_assert(!CB || (A == 16 && P == 16 && !TS && !RC), "crossing bits: the two-grid kernel on 512-point lines");
     float2 xd[A], xs[A];
 #pragma unroll
     for (int q = 0; q < A; q++) xd[q] = dm[P * q + b];
@@ -2319,19 +2328,20 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
     }
     const long lline = logical_line(line, a.ny, a.lb);
     const float dh = a.d_nyq[lline].x, sh = a.s_nyq[lline].x;
-    unsigned char *mrow = a.first_cross + lline * NZ;
+    unsigned char *mrow = nullptr;  // (crossing bits: there is no mask)
+    if constexpr (!CB) mrow = a.first_cross + lline * NZ;
     // MASK16: the line's mask row as 2 A contiguous bytes per lane (16-byte loads in flight with the
     // spectra); after the transforms the row goes through the line's LDS region, where the lanes pick
     // their (cell 2j, 2j + 1) pairs and leave the changes; changed 16-byte pieces go back to the grid.
     // Sixteen 2-byte loads and up to sixteen 2-byte stores per lane otherwise.
-    constexpr bool MASK16 = EARLY && (C21X_ZW_MASK16 || (TS && RC && C21X_ZW_TSRC_LEAN));
+    constexpr bool MASK16 = !CB && EARLY && (C21X_ZW_MASK16 || (TS && RC && C21X_ZW_TSRC_LEAN));
     constexpr int MV = MASK16 ? A / 8 : 1;
     uint4 mreg[MV];
     uchar2 old[(EARLY && !MASK16) ? A : 1];
     if constexpr (MASK16) {
 #pragma unroll
         for (int v = 0; v < MV; v++) mreg[v] = reinterpret_cast<const uint4 *>(mrow)[b * MV + v];
-    } else if (EARLY) {  // mask rows early too
+    } else if (EARLY && !CB) {  // mask rows early too
 #pragma unroll
         for (int q = 0; q < A; q++)
             old[q] = reinterpret_cast<const uchar2 *>(mrow)[(b + P * (q / P)) + A * (q % P)];
@@ -2426,6 +2436,7 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
     const bool floor_ionises = !TS && a.mass_dep_zeta && (floor_lhs > 1.);
     const float dmin = (float)(-1. + 1e-7);  // IonisationBox.c:803
     double acc = 0.;
+    unsigned cb = 0u;  // CB: this lane's word of the line's crossing bits
 #pragma unroll
     for (int q = 0; q < A; q++) {
         // x[P r + d] holds the cells (2j, 2j + 1), j = (b + P r) + A d
@@ -2475,6 +2486,10 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
         }
         const bool i0 = (!RC && floor_ionises) || f0 || ((double)s0 * a.ion_eff > D0);
         const bool i1 = (!RC && floor_ionises) || f1 || ((double)s1 * a.ion_eff > D1);
+        if constexpr (CB) {  // (A = P = 16: j = b + 16 q)
+            cb |= (i0 ? (1u << q) : 0u) | (i1 ? (0x10000u << q) : 0u);
+            continue;
+        }
         uchar2 m = MASK16 ? reinterpret_cast<const uchar2 *>(L)[j]
                           : (EARLY ? old[(EARLY && !MASK16) ? q : 0] : reinterpret_cast<const uchar2 *>(mrow)[j]);
         const bool n0 = i0 && m.x == 0, n1 = i1 && m.y == 0;
@@ -2506,6 +2521,8 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
                 reinterpret_cast<uint4 *>(mrow)[b * MV + v] = n;
         }
     }
+    // the line's 64 bytes, one word per lane: the four lines of a wave are four whole 64-byte pieces
+    if constexpr (CB) a.cross_bits[lline * (NZ / 32) + b] = cb;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     if (lane == 0) red[wave] = acc;
@@ -3193,6 +3210,10 @@ int launch_z_fused(const ZFusedArgs &a, long nlines, hipStream_t stream) {
 int dispatch_z_fused(int nz, const ZFusedArgs &a, long nlines, hipStream_t stream, int *n_partials) {
     KTimeScope kt(2, stream);
     *n_partials = (int)(nlines / LZ_FUSED);
+    if (a.cross_bits && !(nz == 512 && zw_lines_of(nz, nlines) && !a.rc && !a.x_main)) {
+        c21hip_set_error("fused pass Z: crossing bits need the two-grid wave kernel on 512-point z-lines");
+        return C21CM_VALUE_ERROR;
+    }
     if (a.rc && (zw3_selected(nz, nlines) || !zw_lines_of(nz, nlines))) {
         c21hip_set_error("fused pass Z with recombinations needs the 16-lane wave kernel (z-lines of 256 / 512 points)");
         return C21CM_VALUE_ERROR;
@@ -3247,6 +3268,8 @@ int dispatch_z_fused(int nz, const ZFusedArgs &a, long nlines, hipStream_t strea
                 ZW_FUSED(32, true, 16);
         } else if (nz == 256)
             ZW_FUSED(16, false, 8);
+        else if (nz == 512 && a.cross_bits)
+            hipLaunchKernelGGL((zw_ionise_kernel<16, false, 16, false, true>), grid, dim3(zblk), 0, stream, a, twH, twN);
         else if (nz == 512)
             ZW_FUSED(16, false, 16);
         else
@@ -4617,12 +4640,10 @@ extern "C" int c21hip_split_z_ionise_stars(const float *delta_work, const float 
 
 // The same with the filtered x_e spectrum of a spin-temperature run as a third grid
 // (xe_work == NULL: two grids).  512- and 1024-point z-lines only.
-extern "C" int c21hip_split_z_ionise_stars_xe(const float *delta_work, const float *stars_work,
-                                              const float *xe_work, unsigned char *first_cross,
-                                              double *partials, double *sum_out, int nx, int ny,
-                                              int nz, int r_index, double rhocrit_omb,
-                                              double ion_eff, int mass_dep_zeta, double f_limit,
-                                              void *stream) {
+static int z_ionise_stars(const float *delta_work, const float *stars_work, const float *xe_work,
+                          unsigned char *first_cross, unsigned *cross_bits, double *partials,
+                          double *sum_out, int nx, int ny, int nz, int r_index, double rhocrit_omb,
+                          double ion_eff, int mass_dep_zeta, double f_limit, void *stream) {
     const long nlines = (long)nx * ny;
     ZFusedArgs a{};
     a.ny = ny;
@@ -4636,6 +4657,7 @@ extern "C" int c21hip_split_z_ionise_stars_xe(const float *delta_work, const flo
         a.x_nyq = a.x_main + nlines * (nz / 2);
     }
     a.first_cross = first_cross;
+    a.cross_bits = cross_bits;
     a.partials = partials;
     a.rhocrit_omb = rhocrit_omb;
     a.ion_eff = ion_eff;
@@ -4657,6 +4679,42 @@ extern "C" int c21hip_split_z_ionise_stars_xe(const float *delta_work, const flo
     if (st) return st;
     if (!sum_out) return 0;  // deferred: the caller reduces the partials of all radii at once
     return c21hip_reduce_sum(partials, n_partials, sum_out, stream);
+}
+
+extern "C" int c21hip_split_z_ionise_stars_xe(const float *delta_work, const float *stars_work,
+                                              const float *xe_work, unsigned char *first_cross,
+                                              double *partials, double *sum_out, int nx, int ny,
+                                              int nz, int r_index, double rhocrit_omb,
+                                              double ion_eff, int mass_dep_zeta, double f_limit,
+                                              void *stream) {
+    return z_ionise_stars(delta_work, stars_work, xe_work, first_cross, nullptr, partials, sum_out, nx,
+                          ny, nz, r_index, rhocrit_omb, ion_eff, mass_dep_zeta, f_limit, stream);
+}
+
+// Does the two-grid fused pass Z of this grid write crossing bits (c21hip_split_z_ionise_stars_bits)?
+// 512-point z-lines on the wave-level kernel; C21CM_CROSS_BITS=0 keeps the uint8 mask.
+extern "C" int c21hip_z_cross_bits_supported(int nx, int ny, int nz) {
+    static const int on = [] {
+        const char *e = getenv("C21CM_CROSS_BITS");
+        return (e && e[0] == '0') ? 0 : 1;
+    }();
+    return on && nz == 512 && zw_lines_of(nz, (long)nx * ny) != 0;
+}
+
+// The two-grid fused pass Z with the barrier's outcome as this radius' plane of crossing bits
+// (cross_plane: nx*ny*nz/8 bytes, every word written, nothing read; ZFusedArgs::cross_bits) instead
+// of the read-modify-write of the uint8 mask.  c21hip_resolve_crossings turns the planes into the mask.
+extern "C" int c21hip_split_z_ionise_stars_bits(const float *delta_work, const float *stars_work,
+                                                unsigned *cross_plane, double *partials,
+                                                double *sum_out, int nx, int ny, int nz, int r_index,
+                                                double rhocrit_omb, double ion_eff,
+                                                int mass_dep_zeta, double f_limit, void *stream) {
+    if (!cross_plane || !c21hip_z_cross_bits_supported(nx, ny, nz)) {
+        c21hip_set_error("fused pass Z: crossing bits are not available for this grid");
+        return C21CM_VALUE_ERROR;
+    }
+    return z_ionise_stars(delta_work, stars_work, nullptr, nullptr, cross_plane, partials, sum_out, nx,
+                          ny, nz, r_index, rhocrit_omb, ion_eff, mass_dep_zeta, f_limit, stream);
 }
 
 // The same with a recombination model (CELL_RECOMB): sfr_work = passes X, Y of HaloBox.whalo_sfr;
@@ -5128,6 +5186,10 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
                                 stream_);
         else if (kind == 5)  // pass X without a window (diagnostic)
             st = filter_xy(src, work, 2, n, n, n, box_len, box_len, ft, R, rp, 0, stream_, 2);
+        else if (kind == 2 && c21hip_z_cross_bits_supported(n, n, n))  // what the loop launches: one plane
+            st = c21hip_split_z_ionise_stars_bits(a, b, reinterpret_cast<unsigned *>(mask), partials,
+                                                  partials + nlines / 4 + 40, n, n, n, 5, 6.2e9, 1.0, 1,
+                                                  1e-9, stream);
         else if (kind == 2)
             st = c21hip_split_z_ionise_stars(a, b, mask, partials, partials + nlines / 4 + 40,
                                              n, n, n, 5, 6.2e9, 1.0, 1, 1e-9, stream);

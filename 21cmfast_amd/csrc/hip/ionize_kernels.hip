@@ -1210,6 +1210,55 @@ final_sweep_kernel(IoniseParams p, float stored_z, const unsigned char *__restri
     block_sum_to(acc_x, partials_xh + chunk0);
 }
 
+// Crossing bits -> first-crossing mask.  The two-grid fused pass Z on 512-point lines writes one
+// plane of bits per radius (fft_native.hip, ZFusedArgs::cross_bits: [line][16] words, word b bit q =
+// cell 32 q + 2 b, bit 16 + q = cell 32 q + 2 b + 1); the first radius in visit order (largest index
+// first) whose bit is set is what the mask's "mask == 0 ? r : mask" would have kept, 0 where none is.
+// A thread owns four words of a line (one 16-byte load per plane) = 16 groups of 8 consecutive cells.
+// The answer is accumulated bit-sliced -- slice s holds bit s of the index of each cell's first
+// crossing -- so a plane costs a few word operations for 128 cells, and is expanded to bytes at the end.
+template <int NS>
+__global__ void __launch_bounds__(kBlock)
+resolve_crossings_kernel(const unsigned *__restrict__ bits, size_t plane_words, int r_hi, int r_lo,
+                         unsigned char *__restrict__ first_cross, size_t nquads) {
+    const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= nquads) return;
+    unsigned seen[4] = {0u, 0u, 0u, 0u}, sl[NS][4];
+#pragma unroll
+    for (int s = 0; s < NS; s++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) sl[s][i] = 0u;
+#pragma unroll 4
+    for (int r = r_hi; r >= r_lo; r--) {
+        const uint4 w = reinterpret_cast<const uint4 *>(bits + (size_t)(r - 1) * plane_words)[t];
+        const unsigned wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const unsigned fresh = wv[i] & ~seen[i];
+            seen[i] |= wv[i];
+#pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((r >> s) & 1) sl[s][i] |= fresh;  // (uniform)
+        }
+    }
+    // words 4 k .. 4 k + 3 of the line: cells 32 q + 8 k .. + 7 for every q
+    unsigned char *row = first_cross + (t >> 2) * 512 + 8 * (t & 3);
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        unsigned v[4];  // low half: the even cell's index, high half: the odd cell's
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            v[i] = 0u;
+#pragma unroll
+            for (int s = 0; s < NS; s++) v[i] |= ((sl[s][i] >> q) & 0x00010001u) << s;
+        }
+        uint2 o;
+        o.x = (v[0] & 0xffu) | ((v[0] >> 16) << 8) | ((v[1] & 0xffu) << 16) | ((v[1] >> 16) << 24);
+        o.y = (v[2] & 0xffu) | ((v[2] >> 16) << 8) | ((v[3] & 0xffu) << 16) | ((v[3] >> 16) << 24);
+        *reinterpret_cast<uint2 *>(row + 32 * q) = o;
+    }
+}
+
 __global__ void __launch_bounds__(kBlock)
 apply_first_cross_kernel(const unsigned char *__restrict__ fc,
                          const float *__restrict__ prev_z_reion, int first_snapshot, float z_now,
@@ -2005,6 +2054,26 @@ extern "C" int c21hip_brightness_temp(const float *density, const float *xH, con
     LAUNCH_CHECK();
     hipLaunchKernelGGL(finish_reduce_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream,
                        partials, blocks, 0, sum_out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// first_cross[nlines][512] from the crossing-bit planes of the radii r_hi, r_hi - 1, ... r_lo (>= 1);
+// the plane of radius r starts at bits + (r - 1) * nlines * 16 words.  Writes every byte of the mask.
+extern "C" int c21hip_resolve_crossings(const unsigned *bits, int r_hi, int r_lo,
+                                        unsigned char *first_cross, size_t nlines, void *stream) {
+    if (r_lo < 1 || r_hi > 255 || !nlines) {
+        c21hip_set_error("resolve_crossings: radius indices 1..255 and at least one line");
+        return C21CM_VALUE_ERROR;
+    }
+    const size_t nquads = nlines * 4;
+    const dim3 grid((unsigned)((nquads + kBlock - 1) / kBlock));
+    if (r_hi < 64)
+        hipLaunchKernelGGL(resolve_crossings_kernel<6>, grid, dim3(kBlock), 0, (hipStream_t)stream, bits,
+                           nlines * 16, r_hi, r_lo, first_cross, nquads);
+    else
+        hipLaunchKernelGGL(resolve_crossings_kernel<8>, grid, dim3(kBlock), 0, (hipStream_t)stream, bits,
+                           nlines * 16, r_hi, r_lo, first_cross, nquads);
     LAUNCH_CHECK();
     return 0;
 }

@@ -38,6 +38,7 @@ enum c21_ws_slot {
     WS_SCALARS,
     WS_TABLE,
     WS_FIRST_CROSS,
+    WS_CROSS_BITS, /* two-grid fused loop on 512-point lines: one plane of crossing bits per radius > 0 */
     WS_DELTA_WORK,
     WS_STARS_WORK,
     WS_XE_WORK,

@@ -279,6 +279,10 @@ typedef struct {
     int x4_on;
     float *x4_unf, *x4_work, *x4_work2;
     const float *cur_x4;
+    /* single pass, two-grid fused loop on 512-point lines: every radius writes its own plane of crossing
+     * bits (plane of radius r at cross_bits + (r - 1) * ntot / 32) and the mask is resolved from them after
+     * the loop (c21hip_resolve_crossings); NULL: the fused pass Z updates the uint8 mask */
+    unsigned *cross_bits;
     float *sfr_work2;
     double rec0;         /* homogeneous model: the one previous N_rec */
     int finalised;       /* the post-loop sweep already ran inside final_step() */
@@ -769,6 +773,8 @@ static int z_ionise_radius(ion_ctx *c, int R_ct, const float *dwork, const float
                            const float *xwork, unsigned char *first_cross) {
     int status = 0;
     const c21cm_ionize_spec *s = c->s;
+    /* crossing bits: this radius' plane instead of the mask (two grids only, see cross_bits_begin) */
+    unsigned *plane = c->cross_bits ? c->cross_bits + (size_t)(R_ct - 1) * (c->ntot / 32) : NULL;
     if (c->fused_rc) { /* xwork: the filtered whalo_sfr; sums always deferred or reduced below */
         double *part = c->def_partials ? c->def_partials + (long)R_ct * c->def_stride : c->partials;
         if (c->def_partials) {
@@ -815,6 +821,13 @@ static int z_ionise_radius(ion_ctx *c, int R_ct, const float *dwork, const float
             TRY(flush_deferred(c));
         if (c->def_count == 0) c->def_first = R_ct;
         c->def_count++;
+        if (plane)
+            TRY(c21hip_split_z_ionise_stars_bits(dwork, swork, plane,
+                                                 c->def_partials + (long)R_ct * c->def_stride, NULL,
+                                                 c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
+                                                 s->ion_eff_factor, s->mass_dep_zeta, s->f_limit_acg,
+                                                 c->stream));
+        else
         TRY(c21hip_split_z_ionise_stars_xe(dwork, swork, xwork, first_cross,
                                            c->def_partials + (long)R_ct * c->def_stride, NULL,
                                            c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
@@ -824,6 +837,11 @@ static int z_ionise_radius(ion_ctx *c, int R_ct, const float *dwork, const float
     }
     {
         double *sum_dev = c->scalars + SC_SUMS + R_ct;
+        if (plane)
+            TRY(c21hip_split_z_ionise_stars_bits(dwork, swork, plane, c->partials, sum_dev, c->nx, c->ny,
+                                                 c->nz, R_ct, s->rhocrit_omb, s->ion_eff_factor,
+                                                 s->mass_dep_zeta, s->f_limit_acg, c->stream));
+        else
         TRY(c21hip_split_z_ionise_stars_xe(dwork, swork, xwork, first_cross, c->partials, sum_dev,
                                            c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
                                            s->ion_eff_factor, s->mass_dep_zeta, s->f_limit_acg,
@@ -2227,6 +2245,20 @@ done:
     return status;
 }
 
+/* Crossing bits instead of the mask inside the loop?  Exactly where the loop dispatches the two-grid
+ * fused pass Z on 512-point lines: the fused Lagrangian loop without an x_e grid, a recombination model
+ * or IONISE_ENTIRE_SPHERE.  Single pass only -- the shard phases exchange the mask.
+ * C21CM_CROSS_BITS=0 keeps the mask (c21hip_z_cross_bits_supported), and so does a call whose planes
+ * cannot be allocated: the mask path needs no memory of its own, so such a call must not fail here. */
+static void cross_bits_begin(ion_ctx *c) {
+    const c21cm_ionize_spec *s = c->s;
+    c->cross_bits = NULL;
+    if (!c->fused || c->fused_rc || s->use_ts_fluct || c->sphere || s->n_radii < 2 ||
+        !c21hip_z_cross_bits_supported(c->nx, c->ny, c->nz))
+        return;
+    c->cross_bits = (unsigned *)c21hip_ws(WS_CROSS_BITS, (size_t)(s->n_radii - 1) * (c->ntot / 8));
+}
+
 /* The single pass: the whole ladder and the finish tail in one call -- what a world = 1 run of a radii
  * phase followed by its finish phase does too. */
 int c21cm_ionize_grids(const c21cm_ionize_spec *spec, const PerturbedField *perturbed_field,
@@ -2250,12 +2282,19 @@ int c21cm_ionize_grids(const c21cm_ionize_spec *spec, const PerturbedField *pert
             status = C21CM_MEMORY_ALLOC_ERROR;
             goto done;
         }
-        TRY(c21hip_memset(mask, 0, c.ntot, stream));
+        cross_bits_begin(&c);
+        if (!c.cross_bits) /* (the resolver writes every byte of the mask) */
+            TRY(c21hip_memset(mask, 0, c.ntot, stream));
     }
     /* (the fused Lagrangian loop prepares its own set; grids with other windows keep their tables) */
     TRY(native_wev_prepare(&c));
     if (mask) {
         TRY(radii_ladder(&c, spec->n_radii - 1, 1, mask, spec->r_lowest == 0 ? 0 : -1));
+        if (c.cross_bits) {
+            TRY(c21hip_resolve_crossings(c.cross_bits, spec->n_radii - 1, spec->r_lowest > 1 ? spec->r_lowest : 1,
+                                         mask, (size_t)c.nx * c.ny, stream));
+            c.cross_bits = NULL;
+        }
         TRY(flush_deferred(&c));
         TRY(c.fused_rc ? finish_first_cross_recomb(&c, mask) : finish_first_cross(&c, mask, 0));
     } else {
