@@ -141,6 +141,8 @@ int c21hip_wev_prepare(int filter_a, float R_param_a, int filter_b, float R_para
                        const float *R, int n_R, int nx, int ny, int nz, double box_len,
                        double box_len_z, int pair, int *enabled, void *stream);
 void c21hip_wev_release(void);
+/* -1: no set is active; 1: the node tables cover every kR of the set; 0: direct evaluation beyond them */
+int c21hip_wev_covers(void);
 int c21hip_wev_applicable(int filter_a, int filter_b, int n_grids, int nx, int ny, int nz);
 /* one grid, two radii per pass-X sweep, under window a or b of the prepared set (phases: 2 pass X,
  * 4 / 8 pass Y of the first / second radius) */

@@ -4233,6 +4233,9 @@ extern "C" int c21hip_wev_prepare(int filter_a, float R_param_a, int filter_b, f
     return 0;
 }
 extern "C" void c21hip_wev_release(void) { g_wev.active = false; }
+// -1: no set is active; else 1 when the node tables reach the largest kR of the set (FMODE 6 / 7), 0 when
+// the windows beyond them are evaluated directly (FMODE 8 / 9)
+extern "C" int c21hip_wev_covers(void) { return g_wev.active ? (g_wev.covers ? 1 : 0) : -1; }
 // 1: c21hip_wev_prepare would enable evaluated windows for these filters on this grid
 extern "C" int c21hip_wev_applicable(int filter_a, int filter_b, int n_grids, int nx, int ny, int nz) {
     const char *env = getenv("C21CM_WINDOWS");
