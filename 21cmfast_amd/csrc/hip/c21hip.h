@@ -740,6 +740,18 @@ int c21hip_lightcone_dvdr(float *bt, const float *vel, const float *tau, const d
 int c21hip_d2h_2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width,
                   size_t height, void *stream);
 
+/* ---- dvdr_periodic_kernels.hip : the dv/dr correction of a coeval box, periodic line of sight
+ * (rsds.py:16-103 with periodic = True) ----
+ * bt_out = bt_in corrected by g = irfft(i k rfft(vel)) along every line of n cells (float[n_cols][n], the
+ * line of sight fastest), k = 2 pi rfftfreq(n, dx); then the per-cell arithmetic of c21hip_lightcone_dvdr.
+ * bt_out may be bt_in.  hubble: H(z) [1/s] per slice, device; tau: USE_TS_FLUCT only.  method 0: automatic,
+ * 1: transform (n = 2^k, 8 <= n <= 1024), 2: direct circulant sum (2 <= n <= 1536).  Device pointers only;
+ * one launch.  An unsupported n, a method that does not fit n or a NULL array is C21CM_VALUE_ERROR, and
+ * nothing is launched. */
+int c21hip_dvdr_periodic(float *bt_out, const float *bt_in, const float *vel, const float *tau,
+                         const double *hubble, size_t n_cols, int n, double dx, double max_dvdr, int use_ts,
+                         int method, void *stream);
+
 /* ---- angular_lightcone_kernels.hip : angular lightcone sampling and the periodic B-spline prefilter
  * (lightconers.py AngularLightconer) ---- */
 #define C21HIP_ANG_MAX_BOXES (3 * C21HIP_LC_MAX_FIELDS) /* a vector field takes three boxes */

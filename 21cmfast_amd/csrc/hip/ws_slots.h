@@ -351,6 +351,12 @@ enum c21_ws_slot {
     WS_PH_IN,
     WS_PH_OUT,
     WS_PH_GRIDS,
+    /* ---- dvdr_periodic_driver.c ---- */
+    WS_DVP_HUBBLE,
+    WS_DVP_BT,
+    WS_DVP_VEL,
+    WS_DVP_TAU,
+    WS_DVP_OUT,
 
     WS_COUNT
 };

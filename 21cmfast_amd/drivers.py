@@ -455,6 +455,75 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
     return result
 
 
+class Coeval:
+    """A thin view of one snapshot of ``run_coeval`` (Coeval, drivers/coeval.py:44-377): ``inputs``, the
+    ``redshift`` and the snapshot's ``fields`` (name -> array, numpy or torch), each field reachable as an
+    attribute.  Its three methods are the reference's velocity corrections (:242-377), run on the device
+    where the arrays live.
+
+    As upstream, ``axis`` only selects WHICH velocity component enters (``velocity_x`` / ``_y`` / ``_z``):
+    the gradient and the shift always run along the LAST axis of the box, whatever ``axis`` says."""
+
+    def __init__(self, inputs: Inputs, redshift, fields: dict):
+        self.inputs, self.redshift, self.fields = inputs, float(redshift), dict(fields)
+
+    @classmethod
+    def from_result(cls, result: dict, redshift, inputs: Inputs) -> "Coeval":
+        """The snapshot of ``redshift`` out of what ``run_coeval(inputs, ...)`` returned."""
+        return cls(inputs, redshift, result[float(np.float32(redshift))])
+
+    def __getattr__(self, name):
+        fields = self.__dict__.get("fields", {})
+        if name in fields:
+            return fields[name]
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    def _los_velocity(self, axis):
+        if not hasattr(self, "velocity_" + str(axis)):
+            if axis not in ["x", "y", "z"]:
+                raise ValueError("`axis` can only be `x`, `y` or `z`.")
+            raise ValueError("You asked for axis = '" + axis + "', but the coeval doesn't have velocity_" + axis
+                             + "! Set matter_options.KEEP_3D_VELOCITIES=True next time you call run_coeval if "
+                             "you wish to set axis=`" + axis + "'.")
+        return getattr(self, "velocity_" + axis)
+
+    def _tau_21(self):
+        if not self.inputs.astro_options.USE_TS_FLUCT:
+            return None
+        if "tau_21" not in self.fields:
+            raise ValueError('USE_TS_FLUCT needs the tau_21 box of the snapshot: pass keep=(..., "tau_21") to '
+                             "run_coeval")
+        return self.fields["tau_21"]
+
+    def include_dvdr_in_tau21(self, axis: str = "z", periodic: bool = True):
+        """The brightness temperature with the velocity-gradient correction (coeval.py:242-278)."""
+        from . import rsds
+
+        vel = self._los_velocity(axis)
+        return rsds.include_dvdr_in_tau21(self.brightness_temp, vel, self.redshift, self.inputs,
+                                          periodic=periodic, tau_21=self._tau_21())
+
+    def apply_rsds(self, field: str = "brightness_temp", axis: str = "z", periodic: bool = True,
+                   n_rsd_subcells: int = 4):
+        """``field`` of the box with redshift-space distortions (coeval.py:280-326)."""
+        from . import rsds
+
+        vel = self._los_velocity(axis)
+        return rsds.apply_rsds(getattr(self, field), vel, self.redshift, self.inputs, periodic=periodic,
+                               n_rsd_subcells=n_rsd_subcells)
+
+    def apply_velocity_corrections(self, axis: str = "z", periodic: bool = True, n_rsd_subcells: int = 4):
+        """The brightness temperature with the velocity-gradient correction, then redshift-space
+        distortions (coeval.py:328-377)."""
+        from . import rsds
+
+        vel = self._los_velocity(axis)
+        tb = rsds.include_dvdr_in_tau21(self.brightness_temp, vel, self.redshift, self.inputs,
+                                        periodic=periodic, tau_21=self._tau_21())
+        return rsds.apply_rsds(tb, vel, self.redshift, self.inputs, periodic=periodic,
+                               n_rsd_subcells=n_rsd_subcells)
+
+
 def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, device, lib, progress,
                halo_catalogs, inspect, history, perturbed_halos=False):
     """The per-snapshot body shared by ``run_coeval`` and ``run_lightcone``: yields

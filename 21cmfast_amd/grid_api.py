@@ -881,6 +881,52 @@ def lightcone_dvdr(brightness_temp, los_velocity, hubble, dx: float, max_dvdr: f
               "c21cm_lightcone_dvdr_columns_grids")
 
 
+DVDR_PERIODIC_METHODS = {"auto": 0, "fft": 1, "direct": 2}
+
+
+def dvdr_periodic(brightness_temp, los_velocity, hubble, dx: float, max_dvdr: float, tau_21=None,
+                  method: str = "auto", out=None, lib=None, stream=None):
+    """The brightness temperature of a coeval box corrected for the line-of-sight velocity gradient, the line
+    of sight (the last axis) periodic (reference: rsds.py:16-103 with periodic = True).  The gradient is
+    ``irfft(1j k rfft(los_velocity))`` along the last axis, ``k = 2 pi rfftfreq(n, dx)``; ``hubble``: H(z)
+    [1/s], a scalar or one per slice; ``tau_21`` given: the USE_TS_FLUCT form, else the Taylor form clipped at
+    +-max_dvdr H.  ``method``: "auto" (the fp32 line transform for n = 2^k, 8 .. 1024, else the exact circulant
+    sum, n <= 1536), "fft" or "direct".  Arrays are float32, 2-D ``(n_cols, n)`` or 3-D, numpy or torch CUDA
+    tensors; returns ``out`` (default: a new array where ``brightness_temp`` lives), which may be
+    ``brightness_temp`` itself.  No other input is written."""
+    shape = tuple(int(x) for x in brightness_temp.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("brightness_temp must be a 2-D (n_cols, n) or 3-D (n, n, n_slices) array")
+    if method not in DVDR_PERIODIC_METHODS:
+        raise ValueError(f"method must be one of {sorted(DVDR_PERIODIC_METHODS)}")
+    n_slices = shape[-1]
+    # what the kernels take (csrc/hip/dvdr_periodic_kernels.hip); the library checks the same
+    pow2 = 8 <= n_slices <= 1024 and n_slices & (n_slices - 1) == 0
+    if n_slices < 2:
+        raise ValueError("a periodic line of sight needs at least 2 slices")
+    if method == "fft" and not pow2:
+        raise ValueError(f"method 'fft' takes a line of 2^k cells, 8 <= n <= 1024, not {n_slices}")
+    if (method == "direct" or not pow2) and n_slices > 1536:
+        raise ValueError(f"the direct sum takes a line of at most 1536 cells, not {n_slices}")
+    if out is None:
+        out = _new_like(brightness_temp, 0.0)
+    for a in (brightness_temp, los_velocity, tau_21, out):
+        if a is not None:
+            _f32_dense(a, "brightness_temp / los_velocity / tau_21 / out")
+        if a is not None and tuple(a.shape) != shape:
+            raise ValueError("los_velocity / tau_21 / out must have the shape of brightness_temp")
+    hubble = np.ascontiguousarray(np.broadcast_to(np.asarray(hubble, np.float64), (n_slices,)))
+    spec = S.DvdrPeriodicSpec(n_cols=int(np.prod(shape[:-1], dtype=np.int64)), n_slices=n_slices, dx=float(dx),
+                              max_dvdr=float(max_dvdr), use_ts_fluct=int(tau_21 is not None),
+                              method=DVDR_PERIODIC_METHODS[method], hubble=hubble.ctypes.data_as(S.c_double_p))
+    lib = lib or load()
+    lib.c21cm_dvdr_periodic_grids.restype = C.c_int
+    check(lib.c21cm_dvdr_periodic_grids(C.byref(spec), _vptr(brightness_temp), _vptr(los_velocity),
+                                        _vptr(tau_21), _vptr(out), _stream(stream)),
+          "c21cm_dvdr_periodic_grids")
+    return out
+
+
 def rsd_shift(fields, los_velocity, disp_scale, n_sub: int = 4, periodic: bool = False, out=None,
               stream=None):
     """Move every cell of each array in ``fields`` along the last axis by ``los_velocity *

@@ -1,6 +1,9 @@
-"""Redshift-space distortions on the MI355X (reference: src/py21cmfast/rsds.py:106-255).
+"""Velocity corrections on the MI355X (reference: src/py21cmfast/rsds.py:16-255).
 
-``rsds_shift`` and ``apply_rsds`` keep the reference's signatures, argument checks and messages; the
+``include_dvdr_in_tau21``, ``rsds_shift`` and ``apply_rsds`` keep the reference's signatures, argument
+checks and messages.  The dv/dr correction is the kernel of ``csrc/hip/dvdr_periodic_kernels.hip`` behind
+``grid_api.dvdr_periodic`` (a periodic line of sight: coeval boxes) or of ``lightcone_kernels.hip``
+behind ``grid_api.lightcone_dvdr`` (lightcones); the
 shift itself is the gfx950 kernel of ``csrc/hip/rsd_kernels.hip`` behind ``grid_api.rsd_shift``.
 Per line of sight the displacement ``v / H(z) / cell_size`` [pixels] is interpolated linearly onto
 ``n_rsd_subcells`` sub-cells per slice (extrapolated past the end slices, or wrapped when
@@ -40,6 +43,40 @@ def _like(result, ref):
     if _is_torch(ref):
         return result if result.dtype == ref.dtype else result.to(ref.dtype)
     return result.astype(np.asarray(ref).dtype, copy=False) if np.asarray(ref).dtype.kind == "f" else result
+
+
+def include_dvdr_in_tau21(brightness_temp, los_velocity, redshifts, inputs, periodic: bool, tau_21=None):
+    """The brightness temperature with the velocity-gradient correction (rsds.py:16-103):
+    ``brightness_temp`` (2-D ``(ncoords, nslices)`` or 3-D, the line of sight last) and the line-of-sight
+    velocity ``los_velocity`` [Mpc/s] of every cell; ``redshifts``: one per slice, or a float (a coeval
+    box); ``inputs``: a ``drivers.Inputs``; ``tau_21``: required with USE_TS_FLUCT.  ``periodic``: the
+    gradient is the spectral derivative along the last axis, whose length is the period (the reference's
+    ``irfftn(1j k_z rfftn(v))``); else ``np.gradient`` with second-order ends.  Returns a new array of the
+    kind of ``brightness_temp``; no input is written."""
+    if tau_21 is None and inputs.astro_options.USE_TS_FLUCT:
+        raise ValueError("tau_21 is not provided, but inputs.astro_options.USE_TS_FLUCT is True!")
+    if hasattr(redshifts, "__len__") and len(redshifts) != brightness_temp.shape[-1]:
+        raise ValueError("Redshifts must be a float or array with the same size as number of LoS slices")
+    if tuple(los_velocity.shape) != tuple(brightness_temp.shape):
+        raise ValueError("brightness_temp must be an array with the same shape as los_velocity")
+    if brightness_temp.ndim not in (2, 3):
+        raise ValueError("brightness_temp must be a 2-D (ncoords, nslices) or 3-D (n, n, nslices) array")
+    from .drivers import FlatCosmology
+
+    so, cp = inputs.simulation_options, inputs.cosmo_params
+    cosmo = FlatCosmology(cp.hlittle, cp.OMm)
+    z = np.broadcast_to(np.asarray(redshifts, np.float64), (brightness_temp.shape[-1],))
+    hubble = cosmo.H0_cgs * cosmo.efunc(z)  # 1/s
+    cell = float(so.BOX_LEN) / float(so.HII_DIM)  # Mpc
+    max_dvdr = float(inputs.astro_params.MAX_DVDR)
+    tau = _f32(tau_21) if inputs.astro_options.USE_TS_FLUCT else None
+    if periodic:
+        out = api.dvdr_periodic(_f32(brightness_temp), _f32(los_velocity), hubble, cell, max_dvdr, tau_21=tau)
+    else:  # in place in the library: on a copy
+        bt = _f32(brightness_temp)
+        out = bt.clone() if _is_torch(bt) else bt.copy()
+        api.lightcone_dvdr(out, _f32(los_velocity), hubble, cell, max_dvdr, tau_21=tau)
+    return _like(out, brightness_temp)
 
 
 def rsds_shift(field, los_displacement, n_rsd_subcells: int = 4, periodic: bool = False):

@@ -423,6 +423,21 @@ class DvdrSpec(_Base):
     ]
 
 
+class DvdrPeriodicSpec(_Base):
+    """``c21cm_dvdr_periodic_spec`` (include/c21cm_grid.h): the dv/dr correction of a coeval box whose line
+    of sight is periodic."""
+
+    _fields_ = [
+        ("n_cols", C.c_longlong),
+        ("n_slices", C.c_int),
+        ("dx", C.c_double),
+        ("max_dvdr", C.c_double),
+        ("use_ts_fluct", C.c_int),
+        ("method", C.c_int),
+        ("hubble", c_double_p),
+    ]
+
+
 class RsdSpec(_Base):
     """``c21cm_rsd_spec`` (include/c21cm_grid.h): the redshift-space shift of columns of slices."""
 

@@ -870,6 +870,29 @@ int c21cm_spline_prefilter_grids(int n0, int n1, int n2, int order, int n_fields
 int c21cm_lightcone_dvdr_columns_grids(const c21cm_dvdr_spec *spec, long long n_cols, float *brightness_temp,
                                        const float *los_velocity, const float *tau_21, void *stream);
 
+/* ---- The dv/dr correction of a coeval box: periodic line of sight (rsds.py:16-103, periodic = True;
+ * drivers/coeval.py:242-278) ----
+ * out = brightness_temp corrected by the line-of-sight velocity gradient g = irfft(i k rfft(los_velocity))
+ * along every column of n_slices cells (the line of sight is the fastest axis: float[n_cols][n_slices]),
+ * k = 2 pi rfftfreq(n_slices, dx) -- what irfftn(1j k_z rfftn(v)) gives, the transforms across the line of
+ * sight cancelling -- then 1/|1 + clip(g, +-max_dvdr H)/H| or, with use_ts_fluct, the fp64 tau_21 form of
+ * c21cm_dvdr_spec.  method 0 picks the path: an fp32 line transform in LDS for n_slices = 2^k, 8 .. 1024;
+ * the exact circulant sum in fp64 for every other n_slices from 2 to 1536 (1: the transform, 2: the sum,
+ * or C21CM_VALUE_ERROR where n_slices does not fit).  Each array may be host or device memory; out may be
+ * brightness_temp, and no other input is ever written. */
+typedef struct c21cm_dvdr_periodic_spec {
+    long long n_cols;      /* columns (HII_DIM^2 for a box) */
+    int n_slices;          /* cells per column = the period, >= 2 */
+    double dx;             /* BOX_LEN / HII_DIM [Mpc] */
+    double max_dvdr;       /* AstroParams.MAX_DVDR */
+    int use_ts_fluct;      /* tau_21 required */
+    int method;            /* 0: automatic, 1: transform, 2: direct */
+    const double *hubble;  /* host, n_slices: H(z) of every slice [1/s] */
+} c21cm_dvdr_periodic_spec;
+
+int c21cm_dvdr_periodic_grids(const c21cm_dvdr_periodic_spec *spec, const float *brightness_temp,
+                              const float *los_velocity, const float *tau_21, float *out, void *stream);
+
 /* Library management */
 const char *c21cm_version(void);
 int c21cm_device_synchronize(void);
