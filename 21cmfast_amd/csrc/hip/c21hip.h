@@ -336,6 +336,37 @@ int c21hip_copy_filter_star(const float *src_c, float *dst_c, int nx, int ny, in
                             double box_len, double box_len_z, int filter_type, float R,
                             float R_param, float R_star, int apply, void *stream);
 
+/* gsl_stream_kernels.hip: the same streams drawn on the device (layouts: gsl_stream.c).
+ *   draw    one launch over n_streams descriptors; every stream resumes from its saved state and stops after at
+ *           most max_pairs accepted pairs, at its count, or at the tile cap (tile_cap <= 0: derived from the pairs
+ *           asked for), which sets its error word and *flag_dev
+ *   accept  the compaction alone on words in device memory; result_dev[0] = pairs found, [1] = words used
+ *   raw     the first n raw outputs of one generator state */
+typedef struct c21_gsl_stream_desc {
+    unsigned long long out_offset; /* first pair of the stream in the output, grid order */
+    unsigned long long count;      /* pairs the stream owes: 2 rows ny nzc */
+    unsigned int kind;             /* 0 mt19937, 1 gfsr4, 2 cmrg, 3 mrg, 4 taus2 */
+    unsigned int state_offset;     /* of the stream's record in the state buffer, in 32-bit words */
+} c21_gsl_stream_desc;
+/* a stream's record: C21_GSL_HDR header words (0-1 accepted pairs, 2 carry present, 3 carry word, 4 error), then
+ * the generator state as c21_gsl_export_state writes it */
+#define C21_GSL_HDR 8
+/* cmrg, mrg, taus2: every thread owns C21_GSL_RUN consecutive outputs of a tile; jump matrix j of C21_GSL_JUMPS
+ * is A^(C21_GSL_RUN 2^j).  Tables back to back: cmrg (two 3x3), mrg (5x5), taus2 (three times 32 columns). */
+#define C21_GSL_RUN 8
+#define C21_GSL_JUMPS 9
+#define C21_GSL_JUMP_CMRG 0
+#define C21_GSL_JUMP_MRG (C21_GSL_JUMPS * 18)
+#define C21_GSL_JUMP_TAUS2 (C21_GSL_JUMP_MRG + C21_GSL_JUMPS * 25)
+#define C21_GSL_JUMP_WORDS (C21_GSL_JUMP_TAUS2 + C21_GSL_JUMPS * 96)
+int c21hip_gsl_tile_words(int kind); /* words per tile of generator `kind`; -1: words in memory */
+int c21hip_gsl_stream_draw(const void *desc_dev, int n_streams, unsigned int *state_dev, const unsigned int *jump_dev,
+                           unsigned long long *pairs_dev, unsigned long long max_pairs, long tile_cap, int *flag_dev,
+                           void *stream);
+int c21hip_gsl_accept_pairs(int kind, const unsigned int *words_dev, size_t n_words, size_t want,
+                            unsigned long long *pairs_dev, unsigned long long *result_dev, void *stream);
+int c21hip_gsl_raw_words(int kind, const unsigned int *state_dev, const unsigned int *jump_dev, size_t n,
+                         unsigned int *out_dev, void *stream);
 /* ics_kernels.hip: the raw word pairs of the reference's IC random stream (gsl_stream.c: two accepted
  * 32-bit outputs per deviate, generator kind per x-row) -> gsl_ran_ugaussian deviates, in place */
 int c21hip_gsl_words_to_deviates(void *buf, size_t n_deviates, const unsigned char *row_kind_dev,

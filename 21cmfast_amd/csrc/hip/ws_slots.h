@@ -357,6 +357,13 @@ enum c21_ws_slot {
     WS_DVP_VEL,
     WS_DVP_TAU,
     WS_DVP_OUT,
+    /* ---- gsl_stream.c: the reference's random streams drawn on the device ---- */
+    WS_GSL_DESC,  /* one descriptor per stream that owns rows */
+    WS_GSL_STATE, /* per stream: accepted count, carry word, error word, generator state (saved by every launch) */
+    WS_GSL_JUMP,  /* jump matrices of cmrg, mrg, taus2 */
+    WS_GSL_FLAG,  /* tile-cap flag of a draw; the two counts of c21cm_gsl_accept_pairs */
+    WS_GSL_IN,    /* staged host words of c21cm_gsl_accept_pairs */
+    WS_GSL_OUT,   /* outputs of the c21cm_gsl_* entries on their way to a host array */
 
     WS_COUNT
 };

@@ -128,7 +128,8 @@ int ComputeInitialConditions(unsigned long long random_seed, InitialConditions *
      * N_THREADS give the same universe as upstream (all five per-thread generators, gsl_stream.c);
      * it is drawn serially on the host, as upstream draws it.  With C21CM_IC_RNG=philox the
      * counter-based device generator is used (a different, equally valid realisation; ~100x faster
-     * at DIM = 512).  C21CM_IC_RNG=gsl insists on the former. */
+     * at DIM = 512).  C21CM_IC_RNG=gsl insists on the former; C21CM_IC_RNG=gsl-device draws the same
+     * streams on the device (same fields bit for bit). */
     {
         extern int c21_gsl_stream_supported(int n_threads);
         const char *e = getenv("C21CM_IC_RNG");
@@ -136,6 +137,8 @@ int ComputeInitialConditions(unsigned long long random_seed, InitialConditions *
         s.rng_threads = n_thr;
         if (e && e[0] == 'p')
             s.rng_stream = C21CM_RNG_PHILOX;
+        else if (e && !strcmp(e, "gsl-device") && c21_gsl_stream_supported(n_thr))
+            s.rng_stream = C21CM_RNG_GSL_DEVICE;
         else if (e && e[0] == 'g')
             s.rng_stream = C21CM_RNG_GSL;
         else

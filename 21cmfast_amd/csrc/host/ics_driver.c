@@ -33,20 +33,30 @@ _Static_assert(WS_IC_DIAG_LAST - WS_IC_DIAG0 == 2 && WS_IS_D_LAST - WS_IS_D0 == 
     } while (0)
 
 /* C21CM_RNG_GSL: the reference's random stream (gsl_stream.c) drawn on the host in the
- * reference's order and staged in HBM for sample_modes_kernel; NULL for the Philox stream. */
+ * reference's order and staged in HBM for sample_modes_kernel; C21CM_RNG_GSL_DEVICE: the same stream drawn
+ * on the device; NULL for the Philox stream. */
 int c21_gsl_mode_deviates(unsigned long long seed, int n_threads, int nx, int ny, int nzc,
                           double *ab);
 int c21_gsl_mode_deviates_device(unsigned long long seed, int n_threads, int nx, int ny, int nzc,
                                  double *dev_ab, void *stream);
+int c21_gsl_mode_deviates_ondevice(unsigned long long seed, int n_threads, int nx, int ny, int nzc, double *dev_ab,
+                                   long long max_pairs_per_launch, void *stream);
 static int stream_deviates(const c21cm_ics_spec *s, void *stream, const double **dev_ab) {
     *dev_ab = NULL;
     if (s->rng_stream == C21CM_RNG_PHILOX) return 0;
-    if (s->rng_stream != C21CM_RNG_GSL) {
+    if (s->rng_stream != C21CM_RNG_GSL && s->rng_stream != C21CM_RNG_GSL_DEVICE) {
         c21hip_set_error("ics: unknown rng_stream %d", s->rng_stream);
         return C21CM_VALUE_ERROR;
     }
     const int nzc = s->dim_z / 2 + 1;
     const size_t bytes = 2 * sizeof(double) * (size_t)s->dim * s->dim * nzc;
+    if (s->rng_stream == C21CM_RNG_GSL_DEVICE) { /* the same accepted pairs, drawn by the device */
+        double *dev = (double *)c21hip_ws(WS_IC_DEVIATES, bytes);
+        if (!dev) return C21CM_MEMORY_ALLOC_ERROR;
+        *dev_ab = dev;
+        return c21_gsl_mode_deviates_ondevice(s->seed, s->rng_threads > 0 ? s->rng_threads : 1, s->dim, s->dim, nzc,
+                                              dev, 0, stream);
+    }
     {
         /* default: raw words staged chunk by chunk while the streams are drawn, ln / sqrt on the
          * device (C21CM_GSL_DEVIATES=host: the deviates computed on the host, one blocking copy) */

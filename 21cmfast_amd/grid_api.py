@@ -617,6 +617,74 @@ def ics_grids(spec: S.IcsSpec, ics: dict | None = None, device=None, stream=None
     return ics
 
 
+def _int_array(a, itemsize: int, what: str):
+    """A caller's integer array of `itemsize` bytes per element, host or device, as it is."""
+    if _is_torch(a):
+        assert a.is_contiguous() and not a.dtype.is_floating_point and a.element_size() == itemsize, what
+    else:
+        assert a.dtype.kind in "iu" and a.dtype.itemsize == itemsize and a.flags["C_CONTIGUOUS"], what
+    return a
+
+
+def gsl_raw_words(kind: int, seed: int, n: int, on_device: bool = False, out=None):
+    """The first ``n`` raw outputs of generator ``kind`` (0 mt19937, 1 gfsr4, 2 cmrg, 3 mrg, 4 taus2) after
+    ``gsl_rng_set(seed)``, computed on the host or on the device (the same words).  ``out``: a host or device
+    array of 32-bit integers; default a new numpy uint32 array."""
+    if out is None:
+        out = np.zeros(n, np.uint32)
+    _int_array(out, 4, "out")
+    lib = load()
+    lib.c21cm_gsl_raw_words.restype = C.c_int
+    lib.c21cm_gsl_raw_words.argtypes = [C.c_int, C.c_ulonglong, C.c_size_t, C.c_int, C.c_void_p]
+    check(lib.c21cm_gsl_raw_words(kind, seed, n, int(on_device), _vptr(out)), "c21cm_gsl_raw_words")
+    return out
+
+
+def gsl_accept_pairs(kind: int, words, want: int, on_device: bool = False):
+    """The polar method's compaction on caller-supplied raw words of generator ``kind``: zero words dropped,
+    survivors paired, pairs with 0 < x^2 + y^2 <= 1 kept as ``a | c << 32`` until ``want`` are found.
+    ``words``: host or device array of 32-bit integers.  Returns (pairs as numpy uint64, words used)."""
+    _int_array(words, 4, "words")
+    n_words = words.numel() if _is_torch(words) else words.size
+    pairs = np.zeros(max(1, min(want, n_words // 2)), np.uint64)
+    n_pairs, n_used = C.c_size_t(), C.c_size_t()
+    lib = load()
+    lib.c21cm_gsl_accept_pairs.restype = C.c_int
+    lib.c21cm_gsl_accept_pairs.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    check(lib.c21cm_gsl_accept_pairs(kind, _vptr(words), n_words, want, int(on_device), _vptr(pairs),
+                                     C.byref(n_pairs), C.byref(n_used)), "c21cm_gsl_accept_pairs")
+    return pairs[: n_pairs.value], n_used.value
+
+
+def gsl_stream_pairs(seed: int, n_threads: int, shape, on_device: bool = False, max_pairs_per_launch: int = 0,
+                     tile_cap: int = 0, out=None, stream=None):
+    """The accepted raw pairs of the reference's IC draw -- ``seed_rng_threads(seed)`` with ``n_threads`` streams,
+    two pairs per mode of a grid of ``shape`` = (nx, ny, nz) -- in grid order: (nx, ny, nz // 2 + 1, 2) packed
+    ``a | c << 32``.  ``max_pairs_per_launch`` bounds one launch of the device draw (0: the default) and does not
+    change the result; ``tile_cap`` bounds the tiles one launch may work through per stream (0: derived from the
+    pairs asked for), and a launch that reaches it fails the call.  ``out``: a host or device array of 64-bit integers; default a new numpy uint64 array."""
+    nx, ny, nz = shape
+    nzc = nz // 2 + 1
+    if out is None:
+        out = np.zeros((nx, ny, nzc, 2), np.uint64)
+    _int_array(out, 8, "out")
+    assert (out.numel() if _is_torch(out) else out.size) == 2 * nx * ny * nzc
+    lib = load()
+    lib.c21cm_gsl_stream_pairs.restype = C.c_int
+    lib.c21cm_gsl_stream_pairs.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_longlong, C.c_long, C.c_void_p, C.c_void_p]
+    check(lib.c21cm_gsl_stream_pairs(seed, n_threads, nx, ny, nzc, int(on_device), max_pairs_per_launch, tile_cap,
+                                     _vptr(out), _stream(stream) if on_device else None),
+          "c21cm_gsl_stream_pairs")
+    return out
+
+
+def gsl_tile_words(kind: int = -1) -> int:
+    """Words per tile of the device draw of generator ``kind``; -1: of ``gsl_accept_pairs``."""
+    return int(load().c21cm_gsl_tile_words(kind))
+
+
 def brightness_grids(spec: S.BrightnessSpec, density, neutral_fraction, spin_temperature=None,
                      stream=None) -> dict:
     """ComputeBrightnessTemp sweep on the MI355X (reference:

@@ -437,7 +437,10 @@ typedef struct c21cm_ics_spec {
      *                         gsl_ran_ugaussian per mode from the generator of the OpenMP thread
      *                         that owns the mode's n_x (InitialConditions.c:103-139) -- for
      *                         N_THREADS = rng_threads (1 or 2): same seed, same universe as upstream.
-     *                         The stream is serial by construction and is drawn on the host. */
+     *                         The acceptance loop runs on the host, ln and sqrt on the device.
+     *   C21CM_RNG_GSL_DEVICE (2)  the same streams drawn on the device, one workgroup per stream
+     *                         (gsl_stream_kernels.hip): the same accepted pairs, so the same fields bit
+     *                         for bit as C21CM_RNG_GSL. */
     int rng_stream;
     int rng_threads;
     /* V_CB_MODEL = FLUCTS (compute_relative_velocities, InitialConditions.c:141-238), cubic grids:
@@ -445,9 +448,40 @@ typedef struct c21cm_ics_spec {
      * unused); NULL = no relative velocities.  Output: InitialConditions.lowres_vcb. */
     const double *vcb_by_m;
 } c21cm_ics_spec;
-enum { C21CM_RNG_PHILOX = 0, C21CM_RNG_GSL = 1 };
+enum { C21CM_RNG_PHILOX = 0, C21CM_RNG_GSL = 1, C21CM_RNG_GSL_DEVICE = 2 };
 
 int c21cm_ics_grids(const c21cm_ics_spec *spec, InitialConditions *ics, void *stream);
+
+/* ---- the reference's IC random streams, piece by piece (gsl_stream.c, gsl_stream_kernels.hip) ----
+ * kind: 0 mt19937, 1 gfsr4, 2 cmrg, 3 mrg, 4 taus2.  on_device = 0 computes on the host, 1 on the device; the
+ * two give the same bits.  Output (and `words`) may be host or device arrays.
+ *   raw_words     the first n raw outputs after gsl_rng_set(seed), before zero rejection
+ *   accept_pairs  the polar method's compaction alone on caller-supplied words: zero words dropped, survivors
+ *                 paired, a pair (a, c) kept iff 0 < x^2 + y^2 <= 1 and stored as a | c << 32; stops after `want`
+ *                 pairs.  pairs_out holds min(want, n_words / 2) entries.  *n_words_used: words consumed up to the
+ *                 last pair when `want` was reached, else n_words.
+ *   stream_pairs  the whole draw of seed_rng_threads(seed) with n_threads streams for nx x ny x nzc modes: two
+ *                 pairs per mode in grid order, 2 nx ny nzc entries.  max_pairs_per_launch bounds what one launch
+ *                 of the device draw accepts per stream (<= 0: the default); the result does not depend on it.
+ *                 tile_cap: the most tiles one launch of the device draw may work through per stream (<= 0:
+ *                 derived from the pairs the launch is asked for, several times what they need on average); a
+ *                 launch that gets there without its pairs makes the call fail with C21CM_VALUE_ERROR. */
+int c21cm_gsl_raw_words(int kind, unsigned long long seed, size_t n, int on_device, unsigned int *out_u32);
+int c21cm_gsl_accept_pairs(int kind, const unsigned int *words, size_t n_words, size_t want, int on_device,
+                           unsigned long long *pairs_out, size_t *n_pairs, size_t *n_words_used);
+int c21cm_gsl_stream_pairs(unsigned long long seed, int n_threads, int nx, int ny, int nzc, int on_device,
+                           long long max_pairs_per_launch, long tile_cap, unsigned long long *pairs_out,
+                           void *stream);
+long long c21cm_gsl_default_pairs_per_launch(void);
+/* words per tile of the device draw of generator `kind`; kind -1: of c21cm_gsl_accept_pairs */
+int c21cm_gsl_tile_words(int kind);
+/* host helpers.  export_state: the state after gsl_rng_set(seed) as 32-bit words, the form the device loads --
+ * kinds 2, 3, 4: 6, 5, 3 words (x1..x3 y1..y3 / x1..x5 / s1..s3); kinds 0, 1: a position word, then the 624 state /
+ * 16384 ring words.  step (kinds 2, 3, 4): one step, returning the output; jump (kinds 2, 3, 4): n steps at once
+ * by matrix powers */
+int c21_gsl_export_state(int kind, unsigned long seed, unsigned int *state);
+unsigned int c21_gsl_step(int kind, unsigned int *state);
+int c21_gsl_jump(int kind, unsigned int *state, unsigned long long n);
 
 /* ---- ComputeBrightnessTemp grid algorithm (BrightnessTemperatureBox.c:22-105) -----------
  * delta_T = const_factor * x_HI * (1 + delta) [mK]; with spin temperatures additionally the
