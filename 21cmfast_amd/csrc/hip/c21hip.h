@@ -918,6 +918,18 @@ int c21hip_ts_pack_slabs(const double *sums, size_t ntot, int world, int rank, i
 int c21hip_ts_combine_slab(const double *sums, size_t ntot, int world, int rank, int rows,
                            size_t maxlen, int as_float, const void *rowmax, const void *recv, double *out,
                            void *stream);
+/* What the last c21hip_ts_shell_loop / c21hip_ts_sfrd_means launched (0 before the first call); read-only,
+ * for the tests: shell-loop version (1, 2, 3), cells per thread (1, 2), source mode (0 Lagrangian grids,
+ * 1 ln SFRD tables, 2 dfcoll/dz tables) and the box-sum kernel of the table modes (0 with Lagrangian grids).
+ * Two process-wide ints without synchronisation: meaningful only when one host thread drives ComputeTsBox. */
+#define C21HIP_TS_ROUTE_LOOP_MASK 0x3
+#define C21HIP_TS_ROUTE_CELLS_SHIFT 2
+#define C21HIP_TS_ROUTE_MODE_SHIFT 4
+#define C21HIP_TS_ROUTE_SUM_SHIFT 6
+#define C21HIP_TS_SUM_SCALAR 1 /* sfrd_sum_kernel, one cell per load */
+#define C21HIP_TS_SUM_VEC4 2   /* sfrd_sum_kernel, 16-byte loads */
+#define C21HIP_TS_SUM_V2 3     /* sfrd_sum2_kernel */
+int c21hip_ts_last_route(void);
 struct c21cm_ts_first_spec;
 int c21hip_ts_first(const struct c21cm_ts_first_spec *s, const float *density, float *Ts_out,
                     float *Tk_out, float *xe_out, size_t ntot, void *stream);

@@ -56,6 +56,10 @@ inline bool ts_loop_v1() {
     return e && e[0] == 'v' && e[1] == '1';
 }
 
+// what the launchers below chose last (c21hip_ts_last_route): read by the tests, never by the library
+int g_route_loop = 0;  // C21HIP_TS_ROUTE_LOOP | CELLS | MODE fields
+int g_route_sum = 0;   // C21HIP_TS_ROUTE_SUM field
+
 __constant__ double kKappaHH[C21CM_KAPPA_NPTS] = C21CM_KAPPA_HH_VALUES;
 __constant__ double kKappaPH[C21CM_KAPPA_NPTS] = C21CM_KAPPA_PH_VALUES;
 __constant__ double kKappaEH[C21CM_KAPPA_NPTS] = C21CM_KAPPA_EH_VALUES;
@@ -171,7 +175,7 @@ static_assert(SH_COUNT == C21HIP_TS_SHELL_ROWS, "shell rows of the device table 
 // box sum of the SFRD table values of one shell (blockIdx.y)
 __global__ void __launch_bounds__(kBlock)
 sfrd_sum_kernel(const float *__restrict__ filtered_density, const float *__restrict__ tables,
-                int table_exp, const double *__restrict__ shell, int n_step, size_t ntot,
+                int table_exp, int vec4, const double *__restrict__ shell, int n_step, size_t ntot,
                 double *__restrict__ partials) {
     __shared__ double lds[kBlock];
     const int R = blockIdx.y;
@@ -180,7 +184,7 @@ sfrd_sum_kernel(const float *__restrict__ filtered_density, const float *__restr
     const double growth = shell[SH_GROWTH * n_step + R], tab_min = shell[SH_TABMIN * n_step + R],
                  tab_width = shell[SH_TABWIDTH * n_step + R], inv_w = shell[SH_TABINVW * n_step + R];
     double acc = 0.;
-    if ((ntot & 3) == 0) {  // four cells per 16-byte load
+    if (vec4) {  // four cells per 16-byte load: ntot % 4 == 0 and a 16-byte aligned array (launcher)
         const float4 *d4 = reinterpret_cast<const float4 *>(dens);
         for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < ntot / 4;
              i += (size_t)gridDim.x * kBlock) {
@@ -470,17 +474,50 @@ ts_accumulate_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
 //   lo = sum_R x_R W[R][k][m],  hi = sum_R x_R W[R][k][m+1]
 // so a cell and shell cost seven fp64 FMAs.  The source term itself is a float upstream
 // (del_fcoll_Rct, :1040-1079) and is evaluated to float accuracy in fp32: bin index and weight
-// from one FMA, the table difference times the weight added to an EXACT float knot inside a
+// from shell_bin(), the table difference times the weight added to an EXACT float knot inside a
 // two-term base-2 reduction (so the argument of the hardware exp2 carries ~5e-8, not the 1e-6 a
-// float holding ln SFRD ~ -20 would), (1 + delta) exp(.) in fp32.  Against the double evaluation
-// rounded to float once that is <= 3e-7 per term, random in sign; x_e and T_k move by a few 1e-8
-// (parity bound 2e-6, tests/test_gpu_ts.py).  ~45 slots per cell and shell: the sweep is within
-// reach of the 4 B it reads (19.2 -> see DESIGN for the measured figure).  C21CM_TS_LOOP=v1
-// selects the kernels above for A/B runs.
+// float holding ln SFRD ~ -20 would), (1 + delta) exp(.) in fp32.  Against the fp64 shell sums the
+// six sums stay within 4 float ulps of sum_R |term_R| for symmetric and for skewed table ranges
+// (tests/test_gpu_ts_shell_sums.py; the measured ratios are in DESIGN.md, Appendix C2); x_e and T_k
+// move by a few 1e-8 (parity bound 2e-6, tests/test_gpu_ts.py).  ~45 slots per cell and shell: the
+// sweep is within reach of the 4 B it reads (19.2 -> see DESIGN for the measured figure).
+// C21CM_TS_LOOP=v1 selects the kernels above for A/B runs.
 struct ShellLookup {
     float gw, off;  // t = delta * gw + off,  gw = growth / width, off = -tab_min / width
     float growth;
+    float gw_lo;             // what gw lost of its double
+    float off_int, off_frac;  // off = off_int + off_frac in double: an integer and a fraction in [0, 1)
 };
+
+__device__ __forceinline__ ShellLookup shell_lookup(double growth, double tab_min, double inv_w) {
+    const double gw = growth * inv_w, off = -tab_min * inv_w;
+    ShellLookup L;
+    L.growth = (float)growth;
+    L.gw = (float)gw;
+    L.off = (float)off;
+    L.gw_lo = (float)(gw - (double)L.gw);
+    const double fl = floor(off);
+    L.off_int = (float)fl;  // exact below 2^24 bins
+    L.off_frac = (float)(off - fl);
+    return L;
+}
+
+// Bin and weight of a cell.  t = delta gw + off reaches ~400 bins, so as a float it is only good to
+// ~2e-5 bins (its own rounding at ulp(256..512), those of gw and off); times the tables' relative slope
+// of a few % per bin that alone is several float ulps of the table value.  Hence t only chooses the bin,
+// and the weight is formed again around it: off_int - idx is a difference of two integers below 2^24,
+// exact whatever the table range; the FMA then rounds at the size of the weight itself (<= 3e-8), and
+// the fraction of off joins the low part of gw: ~1e-7 bins.  A bin chosen one off at a knot only moves
+// the weight to just below 0 or above 1 on the neighbour's line.
+__device__ __forceinline__ float shell_bin(float dens, const ShellLookup &L, int *idx) {
+    const float t = __fmaf_rn(dens, L.gw, L.off);
+    // the cells that define the table range sit on its first / last knot: keep the bin inside
+    // [0, NDELTA - 2] whatever the last bit of t says (upstream reads y[idx + 1] with weight 0 there)
+    const int i = min(max((int)floorf(t), 0), C21CM_NDELTA_TABLE - 2);
+    *idx = i;
+    return __fadd_rn(__fmaf_rn(dens, L.gw, __fsub_rn(L.off_int, (float)i)),
+                     __fmaf_rn(dens, L.gw_lo, L.off_frac));
+}
 
 // value of the per-shell table at the cell (E-INTEGRAL: exp of the ln SFRD table) in fp32
 template <bool EXP>
@@ -488,11 +525,8 @@ __device__ __forceinline__ float shell_table_f32(float dens, const ShellLookup &
                                                  const float *__restrict__ y, float *curr_dens) {
     const float x = __fmul_rn(dens, L.growth);
     *curr_dens = x;
-    const float t = __fmaf_rn(dens, L.gw, L.off);
-    // the cells that define the table range sit on its first / last knot: keep the bin inside
-    // [0, NDELTA - 2] whatever the last bit of t says (upstream reads y[idx + 1] with weight 0 there)
-    const int idx = min(max((int)floorf(t), 0), C21CM_NDELTA_TABLE - 2);
-    const float ip = t - (float)idx;
+    int idx;
+    const float ip = shell_bin(dens, L, &idx);
     const float y0 = y[idx], y1 = y[idx + 1];
     const float r = __fmul_rn(ip, y1 - y0);
     if (!EXP) return y0 + r;
@@ -515,11 +549,8 @@ sfrd_sum2_kernel(const float *__restrict__ filtered_density, const float *__rest
     const int R = blockIdx.y;
     for (int t = threadIdx.x; t < C21CM_NDELTA_TABLE; t += kBlock) tab[t] = tables[(size_t)R * C21CM_NDELTA_TABLE + t];
     __syncthreads();
-    const double inv_w = shell[SH_TABINVW * n_step + R];
-    ShellLookup L;
-    L.growth = (float)shell[SH_GROWTH * n_step + R];
-    L.gw = (float)(shell[SH_GROWTH * n_step + R] * inv_w);
-    L.off = (float)(-shell[SH_TABMIN * n_step + R] * inv_w);
+    const ShellLookup L = shell_lookup(shell[SH_GROWTH * n_step + R], shell[SH_TABMIN * n_step + R],
+                                       shell[SH_TABINVW * n_step + R]);
     const float4 *d4 = reinterpret_cast<const float4 *>(filtered_density + (size_t)R * ntot);
     double acc = 0.;
     const size_t n4 = ntot / 4;  // ntot % 4 == 0 (launcher)
@@ -577,12 +608,9 @@ ts_accumulate2_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
             }
             W[i] = v;
         }
-        for (int R = threadIdx.x; R < n; R += kBlock) {
-            const double inv_w = dev_tab[SH_TABINVW * n + R];
-            LK[R].growth = (float)dev_tab[SH_GROWTH * n + R];
-            LK[R].gw = (float)(dev_tab[SH_GROWTH * n + R] * inv_w);
-            LK[R].off = (float)(-dev_tab[SH_TABMIN * n + R] * inv_w);
-        }
+        for (int R = threadIdx.x; R < n; R += kBlock)
+            LK[R] = shell_lookup(dev_tab[SH_GROWTH * n + R], dev_tab[SH_TABMIN * n + R],
+                                 dev_tab[SH_TABINVW * n + R]);
     }
     __syncthreads();
     const size_t nitems = ntot / VEC;  // ntot % VEC == 0 (launcher)
@@ -703,12 +731,9 @@ ts_accumulate3_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
             const int row = j == 0 ? SH_STARLYA : (j == 1 ? SH_CONT : SH_INJ);
             SS[i] = c1 * dev_tab[row * n + R];
         }
-        for (int R = threadIdx.x; R < n; R += kAccBlock) {
-            const double inv_w = dev_tab[SH_TABINVW * n + R];
-            LK[R].growth = (float)dev_tab[SH_GROWTH * n + R];
-            LK[R].gw = (float)(dev_tab[SH_GROWTH * n + R] * inv_w);
-            LK[R].off = (float)(-dev_tab[SH_TABMIN * n + R] * inv_w);
-        }
+        for (int R = threadIdx.x; R < n; R += kAccBlock)
+            LK[R] = shell_lookup(dev_tab[SH_GROWTH * n + R], dev_tab[SH_TABMIN * n + R],
+                                 dev_tab[SH_TABINVW * n + R]);
         for (int i = threadIdx.x; i < n * TS; i += kAccBlock) {
             const int R = i / TS, j = i - R * TS;
             TAB[i] = j < C21CM_NDELTA_TABLE ? tables[(size_t)R * C21CM_NDELTA_TABLE + j] : 0.f;
@@ -750,10 +775,8 @@ ts_accumulate3_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
 #if C21X_TS_PACKED  // (the round-3 form: 2-vectors so that the compiler emits packed fp32 instructions)
             const v2f d = {c.x, c.y};
             const v2f x = d * L.growth;
-            const v2f t = __builtin_elementwise_fma(d, (v2f){L.gw, L.gw}, (v2f){L.off, L.off});
-            const int i0 = min(max((int)floorf(t.x), 0), C21CM_NDELTA_TABLE - 2);
-            const int i1 = min(max((int)floorf(t.y), 0), C21CM_NDELTA_TABLE - 2);
-            const v2f ip = t - (v2f){(float)i0, (float)i1};
+            int i0, i1;
+            const v2f ip = {shell_bin(c.x, L, &i0), shell_bin(c.y, L, &i1)};
             const v2f y0 = {y[i0], y[i1]}, y1 = {y[i0 + 1], y[i1 + 1]};
             const v2f r = ip * (y1 - y0);
             v2f tv;
@@ -781,9 +804,8 @@ ts_accumulate3_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
                 for (int e = 0; e < 2; e++) {
                     const float dd = cc[e];
                     const float xg = __fmul_rn(dd, L.growth);
-                    const float tt = __fmaf_rn(dd, L.gw, L.off);
-                    const int ii = min(max((int)floorf(tt), 0), C21CM_NDELTA_TABLE - 2);
-                    const float ipf = __fsub_rn(tt, (float)ii);
+                    int ii;
+                    const float ipf = shell_bin(dd, L, &ii);
                     const float ya = y[ii], yb = y[ii + 1];
                     const float rr = __fmul_rn(ipf, __fsub_rn(yb, ya));
                     float tvv;
@@ -917,7 +939,11 @@ extern "C" int c21hip_ts_sfrd_means(const float *filtered_density, const float *
                                     void *stream) {
     int bx = grid_for(ntot);
     if (bx > 512) bx = 512;  // n_step rows of blocks fill the chip
-    const bool v2 = !ts_loop_v1() && (ntot & 3) == 0 && ((size_t)filtered_density & 15) == 0;
+    // 16-byte loads need rows that start on 16 bytes: the array itself and ntot % 4 == 0
+    const bool vec4 = (ntot & 3) == 0 && ((size_t)filtered_density & 15) == 0;
+    const bool v2 = !ts_loop_v1() && vec4;
+    g_route_sum = (v2 ? C21HIP_TS_SUM_V2 : (vec4 ? C21HIP_TS_SUM_VEC4 : C21HIP_TS_SUM_SCALAR))
+                  << C21HIP_TS_ROUTE_SUM_SHIFT;
     if (v2 && table_exp)
         hipLaunchKernelGGL((sfrd_sum2_kernel<true>), dim3(bx, n_step), dim3(kBlock), 0,
                            (hipStream_t)stream, filtered_density, tables_dev, dev_tab, n_step, ntot,
@@ -928,7 +954,8 @@ extern "C" int c21hip_ts_sfrd_means(const float *filtered_density, const float *
                            partials);
     else
         hipLaunchKernelGGL(sfrd_sum_kernel, dim3(bx, n_step), dim3(kBlock), 0, (hipStream_t)stream,
-                           filtered_density, tables_dev, table_exp, dev_tab, n_step, ntot, partials);
+                           filtered_density, tables_dev, table_exp, vec4 ? 1 : 0, dev_tab, n_step, ntot,
+                           partials);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(sfrd_finish_kernel, dim3(n_step), dim3(kBlock), 0, (hipStream_t)stream,
                        partials, bx, mean_sfr_zpp_dev, (double)ntot, n_step, dev_tab, ave_out_dev);
@@ -981,6 +1008,9 @@ extern "C" int c21hip_ts_shell_loop(const c21hip_ts_args *a, const float *prev_x
         const char *loop_env = getenv("C21CM_TS_LOOP");
         const bool v3 = !ts_loop_v1() && !(loop_env && loop_env[0] == 'v' && loop_env[1] == '2') &&
                         vec2 && !a->lagrangian && ts_acc3_lds(a->n_step) <= 160 * 1024;
+        g_route_loop = (v3 ? 3 : (ts_loop_v1() ? 1 : 2)) | (vec2 ? 2 : 1) << C21HIP_TS_ROUTE_CELLS_SHIFT |
+                       (a->lagrangian ? 0 : (a->table_exp ? 1 : 2)) << C21HIP_TS_ROUTE_MODE_SHIFT;
+        if (a->lagrangian) g_route_sum = 0;  // no box sum belongs to this call
         if (v3) {
             const size_t lds3 = ts_acc3_lds(a->n_step);
             static size_t attr3 = 0;
@@ -1027,6 +1057,8 @@ extern "C" int c21hip_ts_shell_loop(const c21hip_ts_args *a, const float *prev_x
     }
     return 0;
 }
+
+extern "C" int c21hip_ts_last_route(void) { return g_route_loop | g_route_sum; }
 
 // host-side collision rates at the mean temperature (get_Ts: float z, TK, xe)
 static double host_kappa(const double *y, double width, double lnT_max, double lnT, int power_law) {

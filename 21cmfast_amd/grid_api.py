@@ -839,6 +839,41 @@ def ts_grids(spec: S.TsSpec, density, previous: dict, source: dict | None = None
     return out
 
 
+def ts_shell_sums(spec: S.TsSpec, density, previous: dict, source: dict | None = None,
+                  filtered_density=None, stream=None):
+    """The shell loop of ``ts_grids`` alone (``c21cm_ts_shell_sums``): the six per-cell sums over the
+    spec's shells as a device float64 tensor [6, N] (heat, ion, lya, starlya, cont, inj).  The tensor
+    starts as NaN, so rows the loop does not write stay visible: row 0 is written as zero without
+    ``use_xray_heating``, rows 4 and 5 are untouched without ``use_lya_heating``.  Arrays may be numpy
+    or CUDA tensors; no mini-halos, and not before the first sources (``no_light``)."""
+    import torch
+
+    dev = density.device if _is_torch(density) else "cuda"
+    sums = torch.full((6, int(np.prod(density.shape))), float("nan"), dtype=torch.float64, device=dev)
+    prev = S.TsBoxStruct(**{k: _fptr(previous[k]) for k in TS_FIELDS})
+    src = S.XraySourceBoxStruct(**{k: _fptr(v) for k, v in (source or {}).items()})
+    lib = load()
+    lib.c21cm_ts_shell_sums.restype = C.c_int
+    lib.c21cm_ts_shell_sums.argtypes = [C.c_void_p] * 7
+    check(lib.c21cm_ts_shell_sums(C.byref(spec), _vptr(density), C.byref(prev), C.byref(src),
+                                  _vptr(filtered_density), C.c_void_p(sums.data_ptr()),
+                                  _stream(stream)), "c21cm_ts_shell_sums")
+    return sums
+
+
+def ts_last_route() -> dict:
+    """What the spin-temperature launchers chose in the last call (``c21hip_ts_last_route``): ``loop``
+    (shell-loop version 1, 2, 3), ``cells`` per thread (1, 2), ``mode`` (0 Lagrangian grids, 1 ln SFRD
+    tables, 2 dfcoll/dz tables) and ``box_sum`` (None with Lagrangian grids, else "scalar", "float4" or
+    "sfrd_sum2")."""
+    lib = load()
+    lib.c21hip_ts_last_route.restype = C.c_int
+    lib.c21hip_ts_last_route.argtypes = []
+    r = lib.c21hip_ts_last_route()
+    return {"loop": r & 3, "cells": (r >> 2) & 3, "mode": (r >> 4) & 3,
+            "box_sum": (None, "scalar", "float4", "sfrd_sum2")[(r >> 6) & 3]}
+
+
 def ts_mcrit_grid(spec: S.MturnSpec, m_turn: float, J_21_LW, vcb=None, stream=None):
     """log10 of the Lyman-Werner turnover mass per cell from the previous TsBox's J_21_LW
     (prepare_filter_boxes, SpinTemperatureBox.c:535-565); allocated like ``J_21_LW``."""

@@ -121,6 +121,11 @@ int oracle_ts_mcrit_grid(const c21cm_mturn_spec *spec, double m_turn, const floa
 int oracle_ts_grids(const c21cm_ts_spec *spec, const float *density, const TsBox *previous,
                     const XraySourceBox *source_box, const float *filtered_density, TsBox *out,
                     c21cm_ts_report *report);
+/* the same run; sums_out / abs_out: [6][N] doubles each, the per-cell shell sums (heat, ion, lya, starlya,
+ * cont, inj) and the sums of the absolute values of their addends */
+int oracle_ts_shell_sums(const c21cm_ts_spec *spec, const float *density, const TsBox *previous,
+                         const XraySourceBox *source_box, const float *filtered_density, TsBox *out,
+                         c21cm_ts_report *report, double *sums_out, double *abs_out);
 int oracle_ts_first_grids(const c21cm_ts_first_spec *spec, const float *density, TsBox *out);
 double oracle_kappa_10(double TK);
 double oracle_kappa_10_elec(double T);

@@ -382,6 +382,35 @@ def ts_grids(spec, density, previous: dict, source: dict | None = None, filtered
     return out
 
 
+def ts_shell_sums(spec, density, previous: dict, source: dict | None = None, filtered_density=None):
+    """ts_grids, and what its shell loop accumulated: ``sums`` [6, N] doubles in the order of the
+    device's CellSums (heat, ion, lya, starlya, cont, inj) and ``abs_sums`` [6, N], the same loop with
+    the absolute value of every addend (the scale of a rounding-error bound on ``sums``)."""
+    shape = density.shape
+    out = {k: np.zeros(shape, np.float32) for k in TS_FIELDS}
+    prev = S.TsBoxStruct(**{k: fptr(previous[k]) for k in TS_FIELDS})
+    box = S.TsBoxStruct(**{k: fptr(out[k]) for k in TS_FIELDS})
+    if spec.use_mini_halos:
+        out["J_21_LW"] = np.zeros(shape, np.float32)
+        box.J_21_LW = fptr(out["J_21_LW"])
+    src = S.XraySourceBoxStruct(**{k: fptr(v) for k, v in (source or {}).items()})
+    rep = S.TsReport()
+    sums = np.zeros((6, density.size), np.float64)
+    abs_sums = np.zeros((6, density.size), np.float64)
+    lib = load()
+    lib.oracle_ts_shell_sums.restype = C.c_int
+    lib.oracle_ts_shell_sums.argtypes = [C.c_void_p] * 9
+    st = lib.oracle_ts_shell_sums(C.byref(spec), fptr(density), C.byref(prev), C.byref(src),
+                                  fptr(filtered_density), C.byref(box), C.byref(rep),
+                                  sums.ctypes.data_as(C.c_void_p), abs_sums.ctypes.data_as(C.c_void_p))
+    if st:
+        raise RuntimeError(f"oracle_ts_shell_sums status {st}")
+    out["report"] = rep
+    out["sums"] = sums
+    out["abs_sums"] = abs_sums
+    return out
+
+
 def ts_mcrit_grid(spec, m_turn, J_21_LW, vcb=None):
     """log10 of the Lyman-Werner turnover mass per cell (prepare_filter_boxes)."""
     lib = load()

@@ -291,9 +291,12 @@ int oracle_ts_mcrit_grid(const c21cm_mturn_spec *m, double m_turn, const float *
     return C21CM_OK;
 }
 
-int oracle_ts_grids(const c21cm_ts_spec *s, const float *density, const TsBox *previous,
-                    const XraySourceBox *source_box, const float *filtered_density, TsBox *out,
-                    c21cm_ts_report *report) {
+/* sums_out / abs_out (either may be NULL): the six per-cell shell sums in the order of the device's
+ * CellSums (heat, ion, lya, starlya, cont, inj), [6][N] doubles, and the same loop with fabs on every
+ * addend (the scale of a rounding-error bound on the sums) */
+static int ts_grids_impl(const c21cm_ts_spec *s, const float *density, const TsBox *previous,
+                         const XraySourceBox *source_box, const float *filtered_density, TsBox *out,
+                         c21cm_ts_report *report, double *sums_out, double *abs_out) {
     int status = ts_check(s);
     if (status) return status;
     if (!density || !previous || !previous->spin_temperature || !previous->kinetic_temp_neutral ||
@@ -348,6 +351,7 @@ int oracle_ts_grids(const c21cm_ts_spec *s, const float *density, const TsBox *p
         inverse_val_box[ct] = (xHII_call - X[m]) * inverse_diff[m];
     }
 
+    if (abs_out) memset(abs_out, 0, 6 * ntot * sizeof(double));
     if (!s->no_light) {
         for (int R_ct = nR; R_ct--;) {
             const double z_edge_factor = s->z_edge_factor[R_ct];
@@ -440,6 +444,19 @@ int oracle_ts_grids(const c21cm_ts_spec *s, const float *density, const TsBox *p
                 if (s->use_xray_heating) dxheat_dt_box[ct] += xray_sfr * FREQ(freq_int_heat);
                 dxion_source_dt_box[ct] += xray_sfr * FREQ(freq_int_ion);
                 dxlya_dt_box[ct] += xray_sfr * FREQ(freq_int_lya);
+                if (abs_out) {
+                    if (s->use_xray_heating) abs_out[ct] += fabs(xray_sfr * FREQ(freq_int_heat));
+                    abs_out[ntot + ct] += fabs(xray_sfr * FREQ(freq_int_ion));
+                    abs_out[2 * ntot + ct] += fabs(xray_sfr * FREQ(freq_int_lya));
+                    abs_out[3 * ntot + ct] += fabs(sfr_term * s->starlya_prefactor[R_ct] +
+                                                   sfr_term_mini * starlya_factor_mini);
+                    if (s->use_lya_heating) {
+                        abs_out[4 * ntot + ct] += fabs(sfr_term * s->lya_cont_prefactor[R_ct] +
+                                                       sfr_term_mini * lyacont_factor_mini);
+                        abs_out[5 * ntot + ct] += fabs(sfr_term * s->lya_inj_prefactor[R_ct] +
+                                                       sfr_term_mini * lyainj_factor_mini);
+                    }
+                }
 #undef FREQ
                 dstarlya_dt_box[ct] +=
                     sfr_term * s->starlya_prefactor[R_ct] + sfr_term_mini * starlya_factor_mini;
@@ -452,6 +469,8 @@ int oracle_ts_grids(const c21cm_ts_spec *s, const float *density, const TsBox *p
             }
         }
     }
+
+    if (sums_out) memcpy(sums_out, acc, 6 * ntot * sizeof(double));
 
     double J_alpha_ave = 0, xheat_ave = 0, xion_ave = 0, Ts_ave = 0, Tk_ave = 0, x_e_ave = 0;
     int bad = 0;
@@ -506,6 +525,21 @@ done:
     free(del_fcoll_Rct);
     free(del_fcoll_Rct_MINI);
     return status;
+}
+
+int oracle_ts_grids(const c21cm_ts_spec *s, const float *density, const TsBox *previous,
+                    const XraySourceBox *source_box, const float *filtered_density, TsBox *out,
+                    c21cm_ts_report *report) {
+    return ts_grids_impl(s, density, previous, source_box, filtered_density, out, report, NULL, NULL);
+}
+
+/* oracle_ts_grids, and the six shell sums of every cell with their absolute-value sums copied out */
+int oracle_ts_shell_sums(const c21cm_ts_spec *s, const float *density, const TsBox *previous,
+                         const XraySourceBox *source_box, const float *filtered_density, TsBox *out,
+                         c21cm_ts_report *report, double *sums_out, double *abs_out) {
+    if (!sums_out || !abs_out) return C21CM_VALUE_ERROR;
+    return ts_grids_impl(s, density, previous, source_box, filtered_density, out, report, sums_out,
+                         abs_out);
 }
 
 /* init_first_Ts (:892-927) with get_Ts's collisions-only branch (heating_helper_progs.c:736-760);

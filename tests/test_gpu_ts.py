@@ -74,6 +74,58 @@ def test_cell_sweep_matches_oracle(api, oracle, lagrangian, n, n_step, nz, devic
     assert to_host(got["kinetic_temp_neutral"]).flat[13] == np.float32(6e4)  # frozen above MAX_TK
 
 
+# 11 x 11 x 13 = 1573 cells (odd: one cell per thread, the scalar box sum) and 81^3 = 531441 cells (odd, and
+# past the 2048 x 256 = 524288 items of one trip of ts_cell_kernel / ts_first_kernel / ts_mcrit_kernel and of
+# the one-cell shell loops: a second trip of 7153 cells, 241 in its last workgroup; ts_finish_kernel then
+# sums 2048 partials per row)
+ODD_BOX, SECOND_TRIP_BOX = (11, 13), (81, 81)
+
+
+def keep_x_e_well_conditioned(spec):
+    """compare() takes x_e at 2e-6 RELATIVE, which presumes x_e is not a difference of nearly equal
+    numbers.  With the workload's clumping factor of 2, recombination drives 6 % of the cells through
+    x_e = 0 in one step; among 5e5 cells one lands within 1e-6 of zero, where the 1e-7 float accuracy of
+    the table modes' source term (2.5e-4 of x_e per step) is several 1e-5 of what is left.  Both boxes of
+    these cases therefore recombine twenty times slower, so that they differ in size only;
+    well_conditioned() then checks on the oracle's result that no cell lost more than 60 % of its x_e."""
+    spec.clumping_factor = 0.1
+
+
+def well_conditioned(ref, d):
+    assert (ref["xray_ionised_fraction"] >= 0.4 * d["previous"]["xray_ionised_fraction"]).all()
+
+
+@pytest.mark.parametrize("box", [ODD_BOX, SECOND_TRIP_BOX], ids=["1573", "531441"])
+@pytest.mark.parametrize("mode", [dict(lagrangian=True), dict(lagrangian=False),
+                                  dict(lagrangian=False, fcoll_tables=True)],
+                         ids=["grids", "sfrd", "fcoll"])
+def test_cell_sweep_odd_box_and_second_trip(api, oracle, monkeypatch, mode, box):
+    monkeypatch.delenv("C21CM_TS_LOOP", raising=False)  # the route asserted below is the default one
+    spec, d = H.make(n=box[0], hii_dim_z=box[1], n_step=4, **mode)
+    keep_x_e_well_conditioned(spec)
+    got, ref = run_both(api, oracle, spec, d, True)
+    well_conditioned(ref, d)
+    compare(got, ref, spec)
+    if not mode["lagrangian"]:
+        np.testing.assert_allclose(np.array(got["report"].ave_sfrd[:4]),
+                                   np.array(ref["report"].ave_sfrd[:4]), rtol=1e-6)
+    assert to_host(got["kinetic_temp_neutral"]).flat[13] == np.float32(6e4)
+    route = api.ts_last_route()
+    assert route["cells"] == 1 and route["loop"] == 2
+    assert route["box_sum"] == (None if mode["lagrangian"] else "scalar")
+
+
+@pytest.mark.parametrize("box", [ODD_BOX, SECOND_TRIP_BOX], ids=["1573", "531441"])
+def test_first_box_odd_box_and_second_trip(api, oracle, box):
+    shape = (box[0], box[0], box[1])
+    fs = H.first_spec(n=box[0], hii_dim_z=box[1])
+    dens = H.smooth_field(shape, np.random.default_rng(2), 0.06)
+    ref = oracle.ts_first_grids(fs, dens)
+    got = api.ts_first_grids(fs, to_device(dens, True))
+    for k in ref:
+        np.testing.assert_allclose(to_host(got[k]), ref[k], rtol=2e-6, err_msg=k)
+
+
 def test_fcoll_table_mode_matches_oracle(api, oracle):
     """C21CM_TS_SRC_FCOLL_TABLES (CONST-ION-EFF): the source is the dfcoll/dz table, the box mean that
     normalises it is the f_coll table's; the densest cell sits exactly on the last knot."""

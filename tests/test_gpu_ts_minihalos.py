@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import ts_helpers as H
-from test_gpu_ts import api, compare, to_device, to_host  # noqa: F401  (fixture)
+from test_gpu_ts import (api, compare, keep_x_e_well_conditioned, to_device, to_host,  # noqa: F401  (fixture)
+                         well_conditioned)
 
 pytestmark = pytest.mark.gpu
 S = importlib.import_module("21cmfast_amd.structs")
@@ -77,6 +78,51 @@ def test_source_grids_with_mini_halos(api, oracle, device, lw_copies):
     compare(got, ref, spec)
     np.testing.assert_allclose(to_host(got["J_21_LW"]), ref["J_21_LW"], rtol=2e-6, atol=1e-30)
     assert ref["J_21_LW"].mean() > 1e-3
+
+
+# 1573 cells (odd) and 531441 cells (past the 2048 x 256 = 524288 cells of one trip of the two mini-halo
+# shell loops, of ts_mcrit_kernel and of the cell sweep: a second trip of 7153 cells; sfrd_sum_mini_kernel
+# takes 5 trips of 131072)
+from test_gpu_ts import ODD_BOX, SECOND_TRIP_BOX  # noqa: E402
+
+
+@pytest.mark.parametrize("box", [ODD_BOX, SECOND_TRIP_BOX], ids=["1573", "531441"])
+def test_two_population_odd_box_and_second_trip(api, oracle, box):
+    spec, d = H.make(n=box[0], hii_dim_z=box[1], n_step=4, lagrangian=False)
+    H.add_minis(spec, d)
+    keep_x_e_well_conditioned(spec)
+    got, ref = run_both(api, oracle, spec, d, True)
+    well_conditioned(ref, d)
+    compare_mini(got, ref, spec)
+    assert to_host(got["J_21_LW"]).mean() > 1e-3
+
+
+@pytest.mark.parametrize("box", [ODD_BOX, SECOND_TRIP_BOX], ids=["1573", "531441"])
+def test_source_grids_with_mini_halos_odd_box_and_second_trip(api, oracle, box):
+    spec, d = H.make(n=box[0], hii_dim_z=box[1], n_step=4, lagrangian=True)
+    H.add_minis_grids(spec, d, lw_copies=True)
+    keep_x_e_well_conditioned(spec)
+    ref = oracle.ts_grids(spec, d["density"], d["previous"], d["source"], None)
+    well_conditioned(ref, d)
+    got = api.ts_grids(spec, to_device(d["density"], True), to_device(d["previous"], True),
+                       to_device(d["source"], True), None)
+    compare(got, ref, spec)
+    np.testing.assert_allclose(to_host(got["J_21_LW"]), ref["J_21_LW"], rtol=2e-6, atol=1e-30)
+    assert ref["J_21_LW"].mean() > 1e-3
+
+
+@pytest.mark.parametrize("box", [ODD_BOX, SECOND_TRIP_BOX], ids=["1573", "531441"])
+def test_mcrit_grid_odd_box_and_second_trip(api, oracle, box):
+    import torch
+
+    shape = (box[0], box[0], box[1])
+    rng = np.random.default_rng(3)
+    ms = S.MturnSpec(hii_dim=box[0], hii_dim_z=box[1], redshift=15.0, vcb_const=20.0, A_LW=2.0,
+                     BETA_LW=0.6, A_VCB=1.0, BETA_VCB=1.8, sigma_vcb=25.86 * math.sqrt(3 * math.pi / 8))
+    j21 = (2.0 * rng.random(shape) ** 3).astype(np.float32)
+    vcb = (40 * rng.random(shape)).astype(np.float32)
+    got = api.ts_mcrit_grid(ms, 1e5, torch.from_numpy(j21).cuda(), torch.from_numpy(vcb).cuda())
+    np.testing.assert_allclose(got.cpu().numpy(), oracle.ts_mcrit_grid(ms, 1e5, j21, vcb), rtol=3e-7)
 
 
 def test_no_light(api, oracle):

@@ -146,3 +146,35 @@ def test_bad_requests_are_refused(oracle):
     spec.lya_dEC = None
     with pytest.raises(RuntimeError):
         oracle.ts_grids(spec, d["density"], d["previous"], d["source"], None)
+
+
+@pytest.mark.parametrize("mode", [dict(lagrangian=True), dict(lagrangian=False),
+                                  dict(lagrangian=False, fcoll_tables=True)],
+                         ids=["grids", "sfrd", "fcoll"])
+def test_exported_shell_sums_are_the_ones_the_report_is_built_from(oracle, mode):
+    """oracle_ts_shell_sums hands out the `acc` array of the run: the box means of the report follow from
+    its rows with the prefactors of ts_cell (:1794-1848).  Same doubles in another summation order over
+    <= 2e4 cells: 1e-12 relative."""
+    spec, d = H.make(n=24, n_step=12, hii_dim_z=28, **mode)
+    plain = oracle.ts_grids(spec, d["density"], d["previous"], d["source"], d["filtered_density"])
+    out = oracle.ts_shell_sums(spec, d["density"], d["previous"], d["source"], d["filtered_density"])
+    sums, abs_sums, rep = out["sums"], out["abs_sums"], out["report"]
+    assert sums.shape == abs_sums.shape == (6, d["density"].size) and d["density"].size <= 20000
+    # the same run (threaded reductions: the box means may differ in their last bits between two runs)
+    for k in ("kinetic_temp_neutral", "xray_ionised_fraction"):
+        np.testing.assert_allclose(out[k], plain[k], rtol=3e-7)
+    for f in ("xion_ave", "xheat_ave", "J_alpha_ave"):
+        assert getattr(rep, f) == pytest.approx(getattr(plain["report"], f), rel=1e-12)
+    scale = spec.xray_prefactor * spec.volunit_inv
+    assert rep.xion_ave == pytest.approx(sums[1].mean() * scale, rel=1e-12)
+    assert rep.xheat_ave == pytest.approx(sums[0].mean() * scale, rel=1e-12)
+    delta = d["density"].astype(np.float64).ravel() * spec.growth_ratio
+    delta[delta <= -1] = -1 + 1e-7
+    j_alpha = sums[2] * scale * spec.Nb_zp * (1 + delta) + sums[3] * spec.lya_star_prefactor * spec.volunit_inv
+    assert rep.J_alpha_ave == pytest.approx(j_alpha.mean(), rel=1e-12)
+    # the workload's weights are positive: the absolute-value sums are the sums themselves; rows 4 and
+    # 5 are the Lyman-alpha heating split of row 3 (0.6 / 0.4 in ts_helpers.make)
+    np.testing.assert_array_equal(abs_sums, sums)
+    assert (sums[:4].max(axis=1) > 0).all()
+    np.testing.assert_allclose(sums[4] + sums[5], sums[3], rtol=1e-14)
+    assert sums[3, 5] == 0 or not mode["lagrangian"]  # the cell no shell reaches (ts_helpers.make)

@@ -13,6 +13,7 @@ import importlib
 import math
 
 import numpy as np
+from scipy.special import ndtr
 
 S = importlib.import_module("21cmfast_amd.structs")
 
@@ -44,9 +45,13 @@ def lya_tables(rng):
 
 
 def make(n=24, n_step=12, lagrangian=True, seed=5, zp=12.0, dzp=-0.3, lya_heating=True,
-         xray_heating=True, cmb_heating=True, no_light=False, hii_dim_z=None, fcoll_tables=False):
+         xray_heating=True, cmb_heating=True, no_light=False, hii_dim_z=None, fcoll_tables=False,
+         dark_shells=2, skew=False):
     """Returns (spec, inputs dict).  inputs: density, previous (dict of three boxes), source
-    (dict) or filtered_density."""
+    (dict) or filtered_density.  The outermost ``dark_shells`` shells carry no Lyman-alpha starlight
+    (n_step <= 2 needs 0: some shell has to shine for the Lyman-alpha normalisation).  ``skew`` (table
+    modes): filtered densities like a real box's, delta g from -0.9 to ~8 with 9 % of the cells in the top
+    quarter of the table, instead of the symmetric Gaussian range."""
     rng = np.random.default_rng(seed)
     nz = hii_dim_z or n
     shape = (n, n, nz)
@@ -85,7 +90,7 @@ def make(n=24, n_step=12, lagrangian=True, seed=5, zp=12.0, dzp=-0.3, lya_heatin
         else:
             spec.z_edge_factor[i] = abs(ze["dzpp"][i] * ze["dtdz"][i]) * c.hubble(zpp) / 0.5
         spec.xray_R_factor[i] = (1 + zpp) ** -1.0
-        spec.starlya_prefactor[i] = 1e-7 * (1 + 0.3 * math.cos(i)) * (i < n_step - 2)
+        spec.starlya_prefactor[i] = 1e-7 * (1 + 0.3 * math.cos(i)) * (i < n_step - dark_shells)
         spec.lya_cont_prefactor[i] = 0.6 * spec.starlya_prefactor[i]
         spec.lya_inj_prefactor[i] = 0.4 * spec.starlya_prefactor[i]
         spec.zpp_growth[i] = ze["growth"][i]
@@ -126,8 +131,12 @@ def make(n=24, n_step=12, lagrangian=True, seed=5, zp=12.0, dzp=-0.3, lya_heatin
         spec.sfr_scale = 0.05
         spec.xray_scale = 1e40 * RH.PC["s_per_yr"]
         for i in range(n_step):
-            fd[i] = smooth_field(shape, rng, 2.5 / (1 + 0.25 * i))  # extrapolated to z = 0
             g = spec.zpp_growth[i]
+            if skew:  # the cube of a uniform variate: median delta g = 0.2, tail to 8 / (1 + 0.1 i)
+                u = ndtr(smooth_field(shape, rng, 1.0).astype(np.float64))
+                fd[i] = ((-0.9 + 8.9 * u ** 3 / (1 + 0.1 * i)) / g).astype(np.float32)
+            else:
+                fd[i] = smooth_field(shape, rng, 2.5 / (1 + 0.25 * i))  # extrapolated to z = 0
             lo, hi = float(fd[i].min()) * g, float(fd[i].max()) * g * 1.001
             spec.tab_min[i] = lo
             spec.tab_width[i] = (hi - lo) / (S.NDELTA_TABLE - 1.0)
