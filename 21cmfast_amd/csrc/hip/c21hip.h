@@ -80,6 +80,10 @@ void c21hip_fft_release(void);
 /* 1 when the hand-written power-of-two transform is used, 0 for rocFFT */
 int c21hip_fft_is_native(int nx, int ny, int nz);
 int c21hip_pair_sweep_supported(int nx); /* two line tiles of nx points fit in LDS */
+/* Pass Y's epilogue over the Nyquist plane: 1 unless the process runs with C21CM_YNYQ_SPLIT=0 (one (tile, grid)
+ * per workgroup, moved in 16-byte vectors along y, against two grids per workgroup and 8-byte accesses).  Read
+ * once per process; results do not depend on it. */
+int c21hip_ynyq_split_enabled(void);
 
 /* ---- fft_native.hip : power-of-two transform on the split k-space layout ----
  * split layout: complex main[nx][ny][nz/2] followed by the Nyquist plane nyq[nx][ny]. */

@@ -639,6 +639,9 @@ struct LinePassArgs {
     // written last first), the rest outer-major as before (so that the fused pass Z still finds the
     // planes written last).
     int item_order;
+    // Strided g1 (the Nyquist plane of pass Y): 1 = the epilogue deals (tile, grid) pairs, one per workgroup,
+    // and moves the tile along y -- contiguous in nyq[x][y] -- in 16-byte vectors
+    int epi_split;
 };
 
 static inline int geo_items(const LineGeo &g) {
@@ -1557,9 +1560,58 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
         }
     }
 main_done:
-    if (!(a.n_geo > 1 && a.g1_strided)) return;
+    if (FMODE != 0 || !(a.n_geo > 1 && a.g1_strided)) return;  // (only pass Y has a strided geometry)
     // ---- epilogue: the strided tiles of g1 (no window, not pipelined: 2 * nx/16 tiles in
     // all), taken by the workgroups at the end of the grid, which have the fewest main items
+    if (a.epi_split) {
+        // One (tile, grid) pair per workgroup.  The plane is nyq[x][y] and the lines run along y, so a tile's
+        // columns are 4 KB apart but its rows are adjacent: a thread moves two rows of one column as one
+        // 16-byte vector (4 lanes cover 64 bytes of a column) and the transposition into tile[row][col] is
+        // done on the LDS side.  All loads of the tile are in flight before the first LDS write.
+        // (host: line_bstride == 1 and an even col_stride; a plane is 16-byte aligned like the main block it follows)
+        const unsigned cs = (unsigned)a.g1.col_stride;
+        const int nct = a.g1.n_ctiles;
+        for (int w = (int)(gridDim.x - 1 - blockIdx.x); w < n_work1 * a.n_grids; w += (int)gridDim.x) {
+            const int g = w / n_work1, wt = w - g * n_work1;
+            const int og = wt / nct, ct = wt - og * nct;
+            const long base = (long)og * a.g1.outer_bstride + (long)ct * TZ * a.g1.col_stride;
+            const float2 *src = (g ? a.g1.src[1] : a.g1.src[0]) + base;
+            float2 *dst = (g ? a.g1.dst[1] : a.g1.dst[0]) + base;
+            float4 v[2 * NP];
+#pragma unroll
+            for (int u = 0; u < 2 * NP; u++) {
+                const int i = (int)threadIdx.x + kBlock * u;
+                const int col = i % TZ, rp = i / TZ;  // rows 2 rp, 2 rp + 1
+                v[u] = *reinterpret_cast<const float4 *>(src + ((unsigned)col * cs + 2u * (unsigned)rp));
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 2 * NP; u++) {
+                const int i = (int)threadIdx.x + kBlock * u;
+                const int col = i % TZ, rp = i / TZ;
+                tile[(2 * rp) * TZ + col] = make_float2(v[u].x, v[u].y);
+                tile[(2 * rp + 1) * TZ + col] = make_float2(v[u].z, v[u].w);
+            }
+            __syncthreads();
+            line_fft<N, TZ, SIGN, kBlock>(tile, tw, tw_half);
+#pragma unroll
+            for (int u = 0; u < 2 * NP; u++) {
+                const int i = (int)threadIdx.x + kBlock * u;
+                const int col = i % TZ, rp = i / TZ;
+                const float2 e0 = tile[fft_out_row<N>(2 * rp) * TZ + col];
+                const float2 e1 = tile[fft_out_row<N>(2 * rp + 1) * TZ + col];
+                float4 o = make_float4(e0.x, e0.y, e1.x, e1.y);
+                if (a.out_scale != 1.0f) {
+                    o.x *= a.out_scale;
+                    o.y *= a.out_scale;
+                    o.z *= a.out_scale;
+                    o.w *= a.out_scale;
+                }
+                *reinterpret_cast<float4 *>(dst + ((unsigned)col * cs + 2u * (unsigned)rp)) = o;
+            }
+        }
+        return;
+    }
     for (int w = (int)(gridDim.x - 1 - blockIdx.x); w < n_work1; w += (int)gridDim.x) {
         // (the strided geometry is the unblocked Nyquist plane: offsets are i * bstride)
         const unsigned ls = (unsigned)a.g1.line_bstride, cs = (unsigned)a.g1.col_stride;
@@ -2158,6 +2210,17 @@ constexpr int ktime_kind(int sign, int fmode) {
                                                               : (fmode == 7 || fmode == 9) ? 8 : 10);
 }
 
+// Pass Y's Nyquist epilogue: C21CM_YNYQ_SPLIT=0 restores two grids per workgroup with 8-byte accesses; read once
+// per process
+static bool ynyq_split_on() {
+    static int on = -1;
+    if (on < 0) {
+        const char *e = getenv("C21CM_YNYQ_SPLIT");
+        on = (e && atoi(e) == 0) ? 0 : 1;
+    }
+    return on != 0;
+}
+
 #ifndef C21X_XORDER_DEFAULT
 #define C21X_XORDER_DEFAULT 3
 #endif
@@ -2175,6 +2238,12 @@ int launch_line_pass_mode(const LinePassArgs &a, hipStream_t stream) {
         c21hip_set_error("native FFT: %zu bytes of LDS for a %d-point line pass (mode %d)", lds, N, FMODE);
         return C21CM_VALUE_ERROR;
     }
+    if (FMODE != 0 && a.n_geo > 1 && a.g1_strided) {  // the epilogue is compiled into the windowless passes only
+        c21hip_set_error("native FFT: a strided second geometry in a line pass of mode %d", FMODE);
+        return C21CM_VALUE_ERROR;
+    }
+    const bool epi_split = ynyq_split_on() && a.n_geo > 1 && a.g1_strided && a.g1.line_bstride == 1 &&
+                           a.g1.line_lb == 0 && a.g1.col_stride % 2 == 0;
     const int n_work = geo_items(a.g0) + (a.n_geo > 1 ? geo_items(a.g1) : 0);
     // persistent grid: as many workgroups as fit (LDS-limited), each striding over the work
     int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;
@@ -2203,6 +2272,7 @@ int launch_line_pass_mode(const LinePassArgs &a, hipStream_t stream) {
         }
         ao.item_order = (FMODE == 0) ? yo : xo;
     }
+    ao.epi_split = epi_split ? 1 : 0;
     KTimeScope kt(ktime_kind(SIGN, FMODE), stream);
     hipLaunchKernelGGL((line_pass_kernel<N, SIGN, FMODE>), dim3((unsigned)nblocks),
                        dim3(LineThreads<N, FMODE>::value), lds, stream, ao, tw);
@@ -3462,6 +3532,8 @@ extern "C" int c21hip_native_fft_supported(int nx, int ny, int nz) {
 }
 // two radii per pass-X sweep need two line tiles in LDS
 extern "C" int c21hip_pair_sweep_supported(int nx) { return nx <= 512; }
+// 1 unless C21CM_YNYQ_SPLIT is 0 in this process
+extern "C" int c21hip_ynyq_split_enabled(void) { return ynyq_split_on() ? 1 : 0; }
 
 // ---- the timing hook of this file for launches issued elsewhere (bench.py: c21hip_ktime_*)
 extern "C" const void *c21hip_twiddles_dev(int n) { return twiddles(n); }
