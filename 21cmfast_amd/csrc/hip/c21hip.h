@@ -940,6 +940,35 @@ int c21hip_ts_first(const struct c21cm_ts_first_spec *s, const float *density, f
 /* spin-exchange rate coefficients kappa_10 (H-H, e-H, p-H) at temperature T [K] */
 void c21hip_kappa_rates(double T, double *k_HH, double *k_eH, double *k_pH);
 
+/* ---- halo_sampler_kernels.hip: c21cm_sample_halos_grids (include/c21cm_grid.h) on device arrays ----
+ * pass A: one condition per thread (block 256) or per wave64 (wave_threshold: expected halos from which a
+ * wave takes the condition; both give the same words); words[4 n], FOUR per condition: halos kept, draws made, draws removed |
+ * C21HIP_HS_DROP_LAST, the row of its first halo inside its block of 256 conditions; block_sums[ceil(n / 256)]: kept halos per 256 conditions; *bad (preset to ~0):
+ * min over failing conditions of (index << 3 | code), codes C21HIP_HS_BAD_*.  scan: exclusive, in place,
+ * the total to *total.  pass B writes the halos of condition i from row first_row + its offset. */
+struct c21cm_sample_halos_spec;
+#define C21HIP_HS_BLOCK 256
+#define C21HIP_HS_DROP_LAST 0x80000000u
+enum { C21HIP_HS_BAD_DRAWS = 1, C21HIP_HS_BAD_MASS = 2, C21HIP_HS_BAD_WALK = 3 };
+typedef struct c21hip_hs_arrays {
+    const double *tables;      /* device copy of spec->tables */
+    const float *cond_masses;  /* descendants: masses, coordinates [3 n], the three deviates */
+    const float *cond_coords, *cond_star, *cond_sfr, *cond_xray;
+    const float *density, *overlap; /* cells; overlap may be NULL */
+    unsigned long long n_cond;
+    double wave_threshold;
+    /* single_test_sample's cells: `density` holds overdensities at the redshift itself and cond_coords a
+     * position inside the cell each one stands for (Stochasticity.c:1216-1222) */
+    int cells_listed;
+} c21hip_hs_arrays;
+int c21hip_hs_pass_a(const struct c21cm_sample_halos_spec *s, const c21hip_hs_arrays *a, unsigned int *words,
+                     unsigned long long *block_sums, unsigned long long *bad, void *stream);
+int c21hip_hs_scan(unsigned long long *block_sums, unsigned long long n_blocks, unsigned long long *total,
+                   void *stream);
+int c21hip_hs_pass_b(const struct c21cm_sample_halos_spec *s, const c21hip_hs_arrays *a, const unsigned int *words,
+                     const unsigned long long *block_bases, unsigned long long first_row, float *masses,
+                     float *coords, float *star, float *sfr, float *xray, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

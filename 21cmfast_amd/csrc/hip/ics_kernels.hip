@@ -23,6 +23,7 @@
 
 #include "c21hip.h"
 #include "c21cm_abi.h"
+#include "philox.h"
 #include "split_layout.h"
 
 namespace {
@@ -46,32 +47,11 @@ inline int grid_for(size_t work_items) {
         }                                                                               \
     } while (0)
 
-__device__ __forceinline__ void philox4x32_10(uint64_t counter, uint64_t key, uint32_t (&out)[4]) {
-    uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32), c2 = 0, c3 = 0;
-    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __device__ __forceinline__ void gaussian_pair(uint64_t counter, uint64_t seed, double *a,
                                               double *b) {
     uint32_t x[4];
     philox4x32_10(counter, seed, x);
-    const double u1 = ((double)(((uint64_t)(x[0] >> 5) << 26) | (x[2] >> 6)) + 0.5) * 0x1p-53;
-    const double u2 = ((double)(((uint64_t)(x[1] >> 5) << 26) | (x[3] >> 6)) + 0.5) * 0x1p-53;
-    const double r = sqrt(-2.0 * log(u1));
-    double s, c;
-    sincos(2.0 * M_PI * u2, &s, &c);
-    *a = r * c;
-    *b = r * s;
+    philox_gaussian_pair(x, a, b);
 }
 
 // which element (conjugated) a constrained element of the k_z = 0 / Nyquist planes copies

@@ -364,6 +364,14 @@ enum c21_ws_slot {
     WS_GSL_FLAG,  /* tile-cap flag of a draw; the two counts of c21cm_gsl_accept_pairs */
     WS_GSL_IN,    /* staged host words of c21cm_gsl_accept_pairs */
     WS_GSL_OUT,   /* outputs of the c21cm_gsl_* entries on their way to a host array */
+    /* ---- halo_sampler_driver.c ---- */
+    WS_HS_TABLES, /* the snapshot's tables (doubles) */
+    WS_HS_IN0,    /* staged conditions: five catalogue arrays, or density and overlap */
+    WS_HS_IN_LAST = WS_HS_IN0 + 4,
+    WS_HS_WORDS, /* four words per condition between pass A and pass B */
+    WS_HS_SUMS,  /* kept halos per block of conditions, then their exclusive scan; total and status word */
+    WS_HS_OUT0,  /* staged outputs: masses, coordinates, three deviates */
+    WS_HS_OUT_LAST = WS_HS_OUT0 + 4,
 
     WS_COUNT
 };

@@ -1559,3 +1559,58 @@ int ComputePerturbedHaloCatalog(float redshift, InitialConditions *boxes, TsBox 
     if (!st) halos_perturbed->n_halos = o.n_halos;
     return st;
 }
+
+/* ------------------------------------------------------------------------------------
+ * ComputeHaloCatalog (HaloCatalog.c:38-54, Stochasticity.c:1116-1170) for SOURCE_MODEL = CHMF-SAMPLER.
+ * Descendants given: their progenitors.  Else the cells of the low-resolution density; DexM's large
+ * halos and their overlap box enter only where the radius ladder finds a scale that is not too rare, and
+ * then the finder would be needed, which this backend does not have. */
+int ComputeHaloCatalog(float redshift_desc, float redshift, InitialConditions *boxes,
+                       unsigned long long int random_seed, HaloCatalog *halos_desc, HaloCatalog *halos) {
+    int st = require_globals("ComputeHaloCatalog", 1);
+    if (st) return st;
+    if (!halos) return C21CM_VALUE_ERROR;
+    const int src = matter_options_global->SOURCE_MODEL;
+    if (src == C21CM_SOURCE_DEXM_ESF) {
+        c21hip_set_error("ComputeHaloCatalog: SOURCE_MODEL = DEXM-ESF needs the DexM halo finder, which is not "
+                         "implemented in this backend yet");
+        return C21CM_VALUE_ERROR;
+    }
+    if (src != C21CM_SOURCE_CHMF_SAMPLER) {
+        c21hip_set_error("ComputeHaloCatalog: SOURCE_MODEL has no halo catalogues");
+        return C21CM_VALUE_ERROR;
+    }
+    if ((st = ensure_ps())) return st;
+    c21cm_sample_halos_spec s;
+    if (redshift_desc > 0) {
+        if (!halos_desc) return C21CM_VALUE_ERROR;
+        if (redshift < redshift_desc) {
+            c21hip_set_error("ComputeHaloCatalog: the descendant redshift %g lies above the progenitor redshift %g",
+                             (double)redshift_desc, (double)redshift);
+            return C21CM_VALUE_ERROR;
+        }
+        if (!halos_desc->n_halos) { /* Stochasticity.c:1118-1122 */
+            halos->n_halos = 0;
+            return 0;
+        }
+        if ((st = c21cm_sampler_setup(redshift, redshift_desc, random_seed, &s))) return st;
+        return c21cm_sample_halos_grids(&s, NULL, NULL, NULL, halos_desc, halos, NULL);
+    }
+    const char *why = c21_sampler_unsupported_options(); /* the options first, the tables last */
+    if (why) {
+        c21hip_set_error("halo sampler: %s is not implemented in this backend yet", why);
+        return C21CM_VALUE_ERROR;
+    }
+    if (!c21cm_dexm_is_empty(redshift)) {
+        c21hip_set_error("ComputeHaloCatalog: at z = %g this box has scales on which DexM halos are not too rare; "
+                         "the DexM halo finder is not implemented in this backend yet (pass large halos through "
+                         "c21cm_sample_halos_grids)", (double)redshift);
+        return C21CM_VALUE_ERROR;
+    }
+    if (!boxes || !boxes->lowres_density) {
+        c21hip_set_error("ComputeHaloCatalog: InitialConditions.lowres_density is missing");
+        return C21CM_VALUE_ERROR;
+    }
+    if ((st = c21cm_sampler_setup(redshift, -1., random_seed, &s))) return st;
+    return c21cm_sample_halos_grids(&s, boxes->lowres_density, NULL, NULL, NULL, halos, NULL);
+}

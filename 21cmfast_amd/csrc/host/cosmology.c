@@ -678,6 +678,20 @@ static double mf_integral(integrand_fn f, void *ctx, double lnM_min, double lnM_
     return c21_integrate(f, ctx, lnM_min, lnM_max, 1e-6);
 }
 
+static double mf_number_integrand(double lnM, void *ctx) { /* hmf.c:582-589 */
+    const struct mf_ctx *p = (const struct mf_ctx *)ctx;
+    return unconditional_mf(p->growthf, lnM, p->hmf);
+}
+
+/* Nhalo_General (hmf.c:935-943): halos per unit mass of the mean universe between the two masses */
+double c21_Nhalo_General(double z, double lnM_min, double lnM_max) {
+    struct mf_ctx c;
+    memset(&c, 0, sizeof(c));
+    c.growthf = dicke(z);
+    c.hmf = matter_options_global->HMF == C21CM_HMF_ST ? C21CM_HMF_ST : C21CM_HMF_PS;
+    return mf_integral(mf_number_integrand, &c, lnM_min, lnM_max);
+}
+
 static int supported_hmf(void) {
     const int h = matter_options_global->HMF;
     return h == C21CM_HMF_PS || h == C21CM_HMF_ST;
@@ -792,8 +806,8 @@ static double sheth_delc_fixed(double del, double sig) {
     return sqrt(JENKINS_a) * del * (1. + JENKINS_b * pow(sig * sig / (JENKINS_a * del * del), JENKINS_c));
 }
 
-/* hmf.c:166-171 (Delos not supported here) */
-static double get_delta_crit(int hmf, double sigma, double growthf) {
+/* hmf.c:166-171 (Delos not supported here); exported with the reference's name */
+double get_delta_crit(int hmf, double sigma, double growthf) {
     if (hmf == C21CM_HMF_ST) return sheth_delc_fixed(DELTA_C_SPH / growthf, sigma) * growthf;
     return DELTA_C_SPH;
 }
@@ -836,6 +850,11 @@ static double conditional_mf(double growthf, double lnM, double delta_cond, doub
     const double del = (DELTA_C_SPH - delta_cond) / growthf;
     return -del * dsigmasqdm * pow(sigdiff_inv, 1.5) * exp(-del * del * 0.5 * sigdiff_inv) /
            sqrt(2. * M_PI);
+}
+
+/* hmf.c:511-525, exported with the reference's name: PS and ST as above, anything else the EPS form */
+double conditional_hmf(double growthf, double lnM, double delta, double sigma, int HMF) {
+    return conditional_mf(growthf, lnM, delta, sigma, HMF == C21CM_HMF_ST ? C21CM_HMF_ST : C21CM_HMF_PS);
 }
 
 /* hmf.c:664-700 (gauleg, Numerical-Recipes form, 1-based) */

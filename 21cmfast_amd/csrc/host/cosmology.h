@@ -47,6 +47,13 @@ double c21_dtdz(float z);
 double c21_ddickedt(double z);
 double c21_sigma_fast(double M); /* spline over a cached ln M table */
 double c21_Fcoll_General(double z, double lnM_min, double lnM_max);
+/* halo_sampler_tables.c: why the broadcast options cannot be sampled, or NULL */
+const char *c21_sampler_unsupported_options(void);
+/* ... expected N and M of one condition above exp(lnM_lo), by the integrals themselves */
+struct c21cm_sample_halos_spec;
+void c21_sampler_expected(const struct c21cm_sample_halos_spec *s, double cond_val, double lnM_lo, double *n_exp,
+                          double *m_exp);
+double c21_Nhalo_General(double z, double lnM_min, double lnM_max);
 double c21_FgtrM_bias_fast(float growthf, float del_bias, float sig_small, float sig_large);
 float c21_dfcoll_dz(float z, float sigma_min, float del_bias, float sig_bias);
 double c21_Nion_General(double z, double lnM_min, double lnM_max, double Mturn,

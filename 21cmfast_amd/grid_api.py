@@ -741,6 +741,68 @@ def grid_minmax(values, stream=None):
     return mm[0], mm[1]
 
 
+def sampler_spec(redshift, redshift_desc=-1.0, seed=0) -> S.SampleHalosSpec:
+    """The halo sampler's constants and tables of one snapshot from the broadcast globals
+    (stoc_set_consts_z, Stochasticity.c:77-155): ``redshift_desc > 0`` for the progenitors of a catalogue at
+    that redshift, else for the cells of the density grid.  ``spec.tables`` points at library-owned host
+    tables that stay valid until the next call."""
+    lib = load()
+    lib.c21cm_sampler_setup.restype = C.c_int
+    lib.c21cm_sampler_setup.argtypes = [C.c_double, C.c_double, C.c_ulonglong, C.c_void_p]
+    spec = S.SampleHalosSpec()
+    check(lib.c21cm_sampler_setup(float(redshift), float(redshift_desc), int(seed), C.byref(spec)),
+          "c21cm_sampler_setup")
+    return spec
+
+
+def _catalog_of(cat):
+    """HaloCatalogStruct of a struct, or of a dict of arrays (numpy or torch CUDA) with the reference's
+    field names; None stays None"""
+    if cat is None or isinstance(cat, S.HaloCatalogStruct):
+        return cat
+    n = int(cat["halo_masses"].shape[0])
+    out = S.HaloCatalogStruct(n_halos=n, buffer_size=n)
+    for name in ("halo_masses", "halo_coords", "star_rng", "sfr_rng", "xray_rng"):
+        setattr(out, name, _fptr(cat[name]) if n else None)
+    out._keep = cat
+    return out
+
+
+def sample_halos(spec: S.SampleHalosSpec, out: S.HaloCatalogStruct, density=None, overlap=None, large=None,
+                 desc=None, stream=None):
+    """The halo sampler on the MI355X (reference: Stochasticity.c:761-1113): the halos of every condition
+    -- the descendant halos ``desc`` with ``spec.from_catalog``, else the cells of ``density`` [HII_DIM^3]
+    (times D(z)), optionally after the ``large`` halos and with ``overlap`` taken off every cell -- appended
+    to ``out`` (structs.empty_halo_catalog) in condition order, then draw order.  Arrays are numpy or torch
+    CUDA tensors; catalogues are HaloCatalogStructs or dicts of such arrays.
+
+    The random numbers are NOT the reference's GSL streams: every draw is a word of a Philox-4x32-10 block
+    keyed by ``seed + int(1000 z)`` and counted by (condition, purpose, draw), another equally valid
+    realisation that depends on nothing but the inputs.  Returns ``out`` (``n_halos`` set, arrays zero
+    beyond it)."""
+    lib = load()
+    lib.c21cm_sample_halos_grids.restype = C.c_int
+    lib.c21cm_sample_halos_grids.argtypes = [C.c_void_p, S.c_float_p, S.c_float_p] + [C.c_void_p] * 4
+    large_s, desc_s = _catalog_of(large), _catalog_of(desc)
+    check(lib.c21cm_sample_halos_grids(C.byref(spec), _fptr(density), _fptr(overlap),
+                                       C.byref(large_s) if large_s is not None else None,
+                                       C.byref(desc_s) if desc_s is not None else None, C.byref(out),
+                                       _stream(stream)), "c21cm_sample_halos_grids")
+    return out
+
+
+def sample_halos_counts(n_conditions: int):
+    """Halos kept per condition by the last ``sample_halos`` call (int32 numpy array): cuts its catalogue,
+    which is in condition order, into the conditions."""
+    lib = load()
+    lib.c21cm_sample_halos_last_counts.restype = C.c_int
+    lib.c21cm_sample_halos_last_counts.argtypes = [C.c_ulonglong, C.c_void_p]
+    counts = np.zeros(int(n_conditions), np.int32)
+    check(lib.c21cm_sample_halos_last_counts(int(n_conditions), counts.ctypes.data_as(C.c_void_p)),
+          "c21cm_sample_halos_last_counts")
+    return counts
+
+
 def perturb_halos_grids(spec: S.PerturbHalosSpec, consts: S.HaloConsts, ics: dict,
                         catalog: S.HaloCatalogStruct, out: S.PerturbedHaloCatalogStruct,
                         log10_mturn_acg=None, log10_mturn_mcg=None, stream=None):

@@ -337,6 +337,41 @@ class PerturbHalosSpec(_Base):
     ]
 
 
+class SampleHalosSpec(_Base):
+    """``c21cm_sample_halos_spec`` (include/c21cm_grid.h)."""
+
+    _fields_ = [(k, C.c_int) for k in (
+        "from_catalog", "sample_method", "hmf", "hii_dim", "hii_dim_z", "n_cond", "n_prob", "max_halo_cell", "path")] + [
+        ("seed", C.c_ulonglong)] + [(k, C.c_double) for k in (
+            "redshift", "redshift_desc", "box_len", "box_len_z", "growth_out", "growth_in", "m_min",
+            "m_max_tables", "sampler_min_mass", "halomass_correction", "corr_star", "corr_sfr", "corr_xray",
+            "m_cell", "sigma_cell", "rtom_unit", "x_min", "x_width", "p_min", "p_width")] + [
+        ("tables", c_double_p)]
+
+
+def empty_halo_catalog(n, device=None) -> "HaloCatalogStruct":
+    """A zeroed HaloCatalog of ``n`` rows: float32 numpy arrays, or torch tensors on ``device``, kept on
+    the struct as ``arrays`` {field: array}; ``halo_coords`` is [n, 3]."""
+    import numpy as np
+
+    n = int(n)
+    cat = HaloCatalogStruct(n_halos=0, buffer_size=n)
+    cat.arrays = {}
+    for name in ("halo_masses", "halo_coords", "star_rng", "sfr_rng", "xray_rng"):
+        shape = (n, 3) if name == "halo_coords" else (n,)
+        if device is not None:
+            import torch
+
+            a = torch.zeros(shape, dtype=torch.float32, device=device)
+            ptr = C.cast(a.data_ptr(), c_float_p) if n else None
+        else:
+            a = np.zeros(shape, np.float32)
+            ptr = a.ctypes.data_as(c_float_p)
+        cat.arrays[name] = a
+        setattr(cat, name, ptr)
+    return cat
+
+
 class HaloConsts(_Base):
     """``c21cm_halo_consts`` (include/c21cm_grid.h)."""
 

@@ -416,6 +416,39 @@ int test_halo_props(double redshift, float *vcb_grid, float *J21_LW_grid, float 
                     float *halo_coords, float *star_rng, float *sfr_rng, float *xray_rng,
                     float *halo_props_out);
 
+/* reference: src/py21cmfast/src/HaloCatalog.c:38-54 + Stochasticity.c:1116-1170, SOURCE_MODEL =
+ * CHMF-SAMPLER.  redshift_desc > 0: the progenitors of halos_desc; else the cells of
+ * boxes->lowres_density, provided the DexM ladder finds nothing at this redshift (c21cm_dexm_is_empty in
+ * c21cm_grid.h) -- the DexM finder itself is not built, and DEXM-ESF returns ValueError.  The random
+ * numbers are counter-based (c21cm_sample_halos_grids), not the reference's GSL streams.  Arrays host
+ * or device.  ValueError (3) with a message for redshift < redshift_desc, a halo buffer too small,
+ * SAMPLE_METHOD = PARTITION / BINARY-SPLIT, an HMF other than PS / ST, USE_INTERPOLATION_TABLES other than
+ * hmf-interpolation and PHOTON_CONS_TYPE != none. */
+int ComputeHaloCatalog(float redshift_desc, float redshift, InitialConditions *boxes,
+                       unsigned long long int random_seed, HaloCatalog *halos_desc, HaloCatalog *halos);
+
+/* reference: src/py21cmfast/src/integral_wrappers.c:26-97, Stochasticity.c:43-62, hmf.c:166-171,511-525
+ * (_functionprototypes_wrapper.h:93-98,144-148; bound by py21cmfast's cfuncs layer).  The conditions are
+ * overdensities of a cell (z_prev <= 0) or descendant masses; -1 marks a condition or probability outside
+ * the tables. */
+void get_condition_integrals(double redshift, double z_prev, int n_conditions, double *cond_values,
+                             double *out_n_exp, double *out_m_exp);
+void get_halo_chmf_interval(double redshift, double z_prev, int n_conditions, double *cond_values,
+                            int n_masslim, double *lnM_lo, double *lnM_hi, double *out_n);
+void get_halomass_at_probability(double redshift, double z_prev, int n_conditions, double *cond_values,
+                                 double *probabilities, double *out_mass);
+double get_delta_crit(int HMF, double sigma, double growthf);
+double conditional_hmf(double growthf, double lnM, double delta, double sigma, int HMF);
+double expected_nhalo(double redshift);
+/* reference: Stochasticity.c:1164-1306 (_functionprototypes_wrapper.h:121-124; cfuncs.sample_halos_from_conditions):
+ * n_condition conditions (descendant masses with z_in > 0, else cell overdensities at z_out; cond_crd a
+ * position of each) sampled by the kernels of ComputeHaloCatalog; per condition the halos above
+ * SAMPLER_MIN_MASS and their mass, and the expectation above SAMPLER_MIN_MASS; masses and coordinates of all
+ * halos in condition order.  Host arrays; the last two must hold every halo. */
+int single_test_sample(unsigned long long int seed, int n_condition, float *conditions, float *cond_crd,
+                       double z_out, double z_in, int *out_n_tot, int *out_n_cell, double *out_n_exp,
+                       double *out_m_cell, double *out_m_exp, float *out_halo_masses, float *out_halo_coords);
+
 /* reference: src/py21cmfast/src/BrightnessTemperatureBox.c:22 (_functionprototypes_wrapper.h:28-29) */
 int ComputeBrightnessTemp(float redshift, TsBox *spin_temp, IonizedBox *ionized_box,
                           PerturbedField *perturb_field, BrightnessTemp *box);

@@ -604,6 +604,78 @@ int c21cm_perturb_halos_grids(const c21cm_perturb_halos_spec *spec, const c21cm_
                               const float *log10_mturn_mcg, const HaloCatalog *halos,
                               PerturbedHaloCatalog *out, void *stream);
 
+/* ---- the halo sampler (SOURCE_MODEL = CHMF-SAMPLER): Stochasticity.c:663-1113 with explicit scalars.
+ * Every condition -- a descendant halo (from_catalog) or a cell of the low-resolution density field --
+ * samples the conditional mass function of its tables and appends its halos to `out` in condition order,
+ * then draw order (the reference's order at N_THREADS = 1; grid mode copies `large` to the front first).
+ *
+ * Random numbers.  NOT the reference's GSL streams: every uniform and Gaussian deviate is word(s) of one
+ * Philox-4x32-10 block with key = seed + (uint64)(redshift * 1000) and counter = {draw index, purpose,
+ * condition index low, high}; the purposes are the C21CM_HS_DRAW_* below.  A catalogue therefore depends
+ * on nothing but the inputs: not on launch geometry, and not on which condition ran first.  It is another,
+ * equally valid realisation than the reference's.
+ *
+ * Two passes: pass A samples every condition and keeps four words of it (halos kept, draws made, its row in its block, draws
+ * removed + flags); an exclusive scan gives the offsets and the total; pass B repeats the same draws and
+ * writes.  total > out->buffer_size: ValueError, nothing written.  A condition that needs more than
+ * max_halo_cell draws (or a descendant mass outside [m_min, m_max_tables]): ValueError naming the
+ * condition.  On success out->n_halos is set and the five arrays are zero from n_halos to buffer_size.
+ *
+ * tables (doubles, host or device): [nhalo n_cond][mcoll n_cond][sigma n_cond][inverse n_cond * n_prob]:
+ * expected N / M_cond and M / M_cond per unit condition mass on the nodes x_min + i x_width (delta for
+ * cells, ln M for descendants), sigma(M) on the same nodes (descendants only, else zeros), and the inverse
+ * CDF M / M_cond on those rows times the columns ln p = p_min + k p_width.  c21cm_sampler_setup builds
+ * them from the broadcast globals.  Sums that decide control flow (the mass-limited loop and its
+ * removals) are kept as 64-bit integers of the float-rounded masses in units of 1 Msun: a float >= 2^24
+ * is an integer, so the sums are exact and do not depend on the order of the additions. */
+enum { C21CM_HS_DRAW_MASS = 0, C21CM_HS_DRAW_SELECT = 1, C21CM_HS_DRAW_PERMUTE = 2, C21CM_HS_DRAW_POISSON = 3,
+       C21CM_HS_DRAW_POSITION = 4, C21CM_HS_DRAW_POSITION2 = 5, C21CM_HS_DRAW_PROPS = 6, C21CM_HS_DRAW_PROPS2 = 7 };
+#define C21CM_MAX_HALO_CELL 100000 /* Stochasticity.h MAX_HALO_CELL */
+typedef struct c21cm_sample_halos_spec {
+    int from_catalog;  /* 1: conditions are the halos of `desc`; 0: the cells of `density` */
+    int sample_method; /* 0 MASS-LIMITED, 1 NUMBER-LIMITED; cells are always number-limited */
+    int hmf;           /* C21CM_HMF_PS or C21CM_HMF_ST */
+    int hii_dim, hii_dim_z;
+    int n_cond, n_prob;
+    int max_halo_cell; /* draws per condition before ValueError; <= 0: C21CM_MAX_HALO_CELL */
+    int path;          /* 0: a wave takes the conditions that expect >= 64 halos (not tuned); 1 / 2: every
+                        * condition on the thread / the wave path.  The catalogue does not depend on it. */
+    unsigned long long seed;
+    double redshift, redshift_desc;
+    double box_len, box_len_z;
+    double growth_out, growth_in;
+    double m_min, m_max_tables;          /* SAMPLER_MIN_MASS / SAMPLER_BUFFER_FACTOR, M_MAX_INTEGRAL */
+    double sampler_min_mass;             /* halos below it are drawn but not stored (compared as floats) */
+    double halomass_correction;
+    double corr_star, corr_sfr, corr_xray; /* exp(-dz / CORR_*), 0 where CORR_* <= 0 */
+    double m_cell, sigma_cell;           /* cells: the condition mass and sigma(m_cell) */
+    double rtom_unit;                    /* mass of a sphere of radius 1 Mpc: R(M) = cbrt(M / rtom_unit) */
+    double x_min, x_width, p_min, p_width;
+    const double *tables;
+} c21cm_sample_halos_spec;
+
+/* stoc_set_consts_z (Stochasticity.c:77-155) from the broadcast globals: every scalar of the spec, and
+ * `tables` pointing at library-owned host tables that stay valid until the next call.  redshift_desc > 0:
+ * descendants.  The tables of one snapshot are cached under the exact values of the two redshifts: a caller
+ * that names one snapshot once as a float widened to double (ComputeHaloCatalog does) and once as a double
+ * builds them twice, so use one spelling per snapshot.  c21cm_sample_halos_last_counts below reads state of
+ * the last call and is not for concurrent callers.  ValueError for redshift < redshift_desc and for options outside HMF = PS / ST,
+ * SAMPLE_METHOD = MASS-LIMITED / NUMBER-LIMITED, USE_INTERPOLATION_TABLES = hmf-interpolation. */
+int c21cm_sampler_setup(double redshift, double redshift_desc, unsigned long long seed,
+                        c21cm_sample_halos_spec *spec);
+/* density: float[hii_dim^2 hii_dim_z], the z = 0 field (multiplied by growth_out); overlap (may be NULL):
+ * the fraction of each cell inside `large` halos; large (may be NULL); desc: read with from_catalog only.
+ * Arrays host or device. */
+int c21cm_sample_halos_grids(const c21cm_sample_halos_spec *spec, const float *density, const float *overlap,
+                             const HaloCatalog *large, const HaloCatalog *desc, HaloCatalog *out,
+                             void *stream);
+/* halos kept per condition by the last c21cm_sample_halos_grids call, into a host array.  ValueError unless
+ * that call succeeded, sampled exactly n conditions and the workspace has not been released since. */
+int c21cm_sample_halos_last_counts(unsigned long long n, int *counts);
+/* the reference's DexM radius ladder (HaloCatalog.c:156-200) without a field: 1 when every scale is
+ * skipped as rarer than 7 sigma, i.e. DexM would find nothing at this redshift in this box */
+int c21cm_dexm_is_empty(double redshift);
+
 /* min and max of n floats (host or device array), e.g. the table range of the above */
 int c21cm_grid_minmax(const float *values, size_t n, double out_minmax[2], void *stream);
 
