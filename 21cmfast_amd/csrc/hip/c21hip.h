@@ -961,6 +961,35 @@ typedef struct c21hip_hs_arrays {
      * position inside the cell each one stands for (Stochasticity.c:1216-1222) */
     int cells_listed;
 } c21hip_hs_arrays;
+/* ---- dexm_kernels.hip: the DexM halo finder ---- */
+struct c21cm_find_halos_spec;
+typedef struct c21hip_dexm_arrays {
+    unsigned char *in_halo, *forbidden, *state; /* [N] bytes; forbidden only with DEXM_OPTIMIZE */
+    unsigned short *rung_grid;                  /* [N]: rung + 1 of the halo centred on the cell, else 0 */
+    unsigned int *list, *found;                 /* [N]: the rung's candidates in raster order; halo cells as found */
+    unsigned int *counters;                     /* decided, accepted (this rung), found (all rungs), last round */
+} c21hip_dexm_arrays;
+unsigned long long c21hip_dexm_blocks(size_t n); /* workgroups (= partial counts) of the compaction kernels */
+int c21hip_dexm_count(int halos, const float *delta, float crit, const unsigned char *mask,
+                      const unsigned short *rung_grid, size_t n, unsigned long long *counts, void *stream);
+int c21hip_dexm_list(const float *delta, float crit, const unsigned char *mask, size_t n,
+                     const unsigned long long *offsets, unsigned int *list, unsigned char *state, void *stream);
+/* one round: decide marks the undecided candidates of rung r (rejected / accepted in this round), paint adds the
+ * accepted spheres and settles the marks */
+int c21hip_dexm_decide(const struct c21cm_find_halos_spec *s, int r, const c21hip_dexm_arrays *a, unsigned int n_cand,
+                       void *stream);
+int c21hip_dexm_paint(const struct c21cm_find_halos_spec *s, int r, const c21hip_dexm_arrays *a, unsigned int n_cand,
+                      unsigned int round, void *stream);
+int c21hip_dexm_serial(const struct c21cm_find_halos_spec *s, int r, const c21hip_dexm_arrays *a, unsigned int n_cand,
+                       void *stream);
+int c21hip_dexm_forbid(const struct c21cm_find_halos_spec *s, int r, const c21hip_dexm_arrays *a, unsigned int n_found,
+                       const float *r_of_rung, void *stream);
+int c21hip_dexm_extract(const struct c21cm_find_halos_spec *s, const c21hip_dexm_arrays *a, size_t n,
+                        const unsigned long long *offsets, const float *mass_of_rung, float *masses, float *coords,
+                        float *star, float *sfr, float *xray, void *stream);
+int c21hip_dexm_mask_float(const unsigned char *mask, float *out, size_t n, void *stream);
+int c21hip_dexm_downsample(const float *smooth, int dim, int dim_z, int hii_dim, int hii_dim_z, float *out, void *stream);
+
 int c21hip_hs_pass_a(const struct c21cm_sample_halos_spec *s, const c21hip_hs_arrays *a, unsigned int *words,
                      unsigned long long *block_sums, unsigned long long *bad, void *stream);
 int c21hip_hs_scan(unsigned long long *block_sums, unsigned long long n_blocks, unsigned long long *total,

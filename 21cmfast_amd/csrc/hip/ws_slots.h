@@ -372,6 +372,25 @@ enum c21_ws_slot {
     WS_HS_SUMS,  /* kept halos per block of conditions, then their exclusive scan; total and status word */
     WS_HS_OUT0,  /* staged outputs: masses, coordinates, three deviates */
     WS_HS_OUT_LAST = WS_HS_OUT0 + 4,
+    /* ---- dexm_driver.c: the DexM halo finder (its transforms run in tsfilter_driver.c's WS_TF_* slots) ---- */
+    WS_DX_IN,       /* staged hi-res density */
+    WS_DX_DELTA,    /* delta_m of the running rung (dense); then the 0 / 1 mask and its smoothed form */
+    WS_DX_MASK,     /* in_halo, bytes */
+    WS_DX_FORBID,   /* DEXM_OPTIMIZE: forbidden, bytes */
+    WS_DX_STATE,    /* per cell: the candidate's state on the running rung */
+    WS_DX_RUNG,     /* per cell: rung + 1 of the halo centred there (16 bits) */
+    WS_DX_LIST,     /* the rung's candidates in raster order */
+    WS_DX_FOUND,    /* halo cells in the order they were found */
+    WS_DX_COUNTS,   /* total, then candidates / halos per compaction workgroup and their exclusive scan */
+    WS_DX_COUNTERS, /* decided, accepted, found, last round */
+    WS_DX_TABLES,   /* per rung: mass, MtoR(mass) */
+    WS_DX_OVERLAP,  /* staged overlap box */
+    WS_DX_OUT0,     /* staged outputs: masses, coordinates, three deviates */
+    WS_DX_OUT_LAST = WS_DX_OUT0 + 4,
+    /* ---- abi_compute.c: ComputeHaloCatalog for CHMF-SAMPLER, between the finder and the sampler ---- */
+    WS_ABI_DX_LARGE0, /* the catalogue of large halos: masses, coordinates, three deviates */
+    WS_ABI_DX_LARGE_LAST = WS_ABI_DX_LARGE0 + 4,
+    WS_ABI_DX_OVERLAP, /* the overlap box */
 
     WS_COUNT
 };

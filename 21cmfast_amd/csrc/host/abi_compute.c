@@ -1561,20 +1561,29 @@ int ComputePerturbedHaloCatalog(float redshift, InitialConditions *boxes, TsBox 
 }
 
 /* ------------------------------------------------------------------------------------
- * ComputeHaloCatalog (HaloCatalog.c:38-54, Stochasticity.c:1116-1170) for SOURCE_MODEL = CHMF-SAMPLER.
- * Descendants given: their progenitors.  Else the cells of the low-resolution density; DexM's large
- * halos and their overlap box enter only where the radius ladder finds a scale that is not too rare, and
- * then the finder would be needed, which this backend does not have. */
+ * ComputeHaloCatalog (HaloCatalog.c:38-456, Stochasticity.c:1116-1170).
+ * DEXM-ESF: the radius ladder and the DexM finder into `halos`.
+ * CHMF-SAMPLER with descendants: their progenitors.  Without: the cells of the low-resolution density; where
+ * the ladder is not empty, first the finder into a library-owned catalogue of large halos with its overlap
+ * box, which the sampler then takes in front of and off its cells.  An empty ladder needs no hi-res field. */
+static int missing_hires(void) {
+    c21hip_set_error("ComputeHaloCatalog: the DexM halo finder needs InitialConditions.hires_density");
+    return C21CM_VALUE_ERROR;
+}
+
 int ComputeHaloCatalog(float redshift_desc, float redshift, InitialConditions *boxes,
                        unsigned long long int random_seed, HaloCatalog *halos_desc, HaloCatalog *halos) {
     int st = require_globals("ComputeHaloCatalog", 1);
     if (st) return st;
     if (!halos) return C21CM_VALUE_ERROR;
     const int src = matter_options_global->SOURCE_MODEL;
+    c21cm_find_halos_spec f;
     if (src == C21CM_SOURCE_DEXM_ESF) {
-        c21hip_set_error("ComputeHaloCatalog: SOURCE_MODEL = DEXM-ESF needs the DexM halo finder, which is not "
-                         "implemented in this backend yet");
-        return C21CM_VALUE_ERROR;
+        if ((st = ensure_ps())) return st;
+        if ((st = c21cm_dexm_ladder(redshift, &f))) return st;
+        f.seed = random_seed;
+        if (f.n_R && (!boxes || !boxes->hires_density)) return missing_hires();
+        return c21cm_find_halos_grids(&f, boxes ? boxes->hires_density : NULL, NULL, halos, NULL, NULL, NULL);
     }
     if (src != C21CM_SOURCE_CHMF_SAMPLER) {
         c21hip_set_error("ComputeHaloCatalog: SOURCE_MODEL has no halo catalogues");
@@ -1601,16 +1610,31 @@ int ComputeHaloCatalog(float redshift_desc, float redshift, InitialConditions *b
         c21hip_set_error("halo sampler: %s is not implemented in this backend yet", why);
         return C21CM_VALUE_ERROR;
     }
-    if (!c21cm_dexm_is_empty(redshift)) {
-        c21hip_set_error("ComputeHaloCatalog: at z = %g this box has scales on which DexM halos are not too rare; "
-                         "the DexM halo finder is not implemented in this backend yet (pass large halos through "
-                         "c21cm_sample_halos_grids)", (double)redshift);
-        return C21CM_VALUE_ERROR;
-    }
+    if ((st = c21cm_dexm_ladder(redshift, &f))) return st;
+    if (f.n_R && (!boxes || !boxes->hires_density)) return missing_hires();
     if (!boxes || !boxes->lowres_density) {
         c21hip_set_error("ComputeHaloCatalog: InitialConditions.lowres_density is missing");
         return C21CM_VALUE_ERROR;
     }
+    if (!f.n_R) {
+        if ((st = c21cm_sampler_setup(redshift, -1., random_seed, &s))) return st;
+        return c21cm_sample_halos_grids(&s, boxes->lowres_density, NULL, NULL, NULL, halos, NULL);
+    }
+    f.seed = random_seed;
+    /* the large halos: at most one per hi-res cell, and never more than the output holds (HaloCatalog.c:310) */
+    const unsigned long long n_hi = (unsigned long long)f.dim * f.dim * f.dim_z;
+    const size_t n_lo = (size_t)f.hii_dim * f.hii_dim * f.hii_dim_z;
+    HaloCatalog large;
+    memset(&large, 0, sizeof(large));
+    large.buffer_size = halos->buffer_size < n_hi ? halos->buffer_size : n_hi;
+    const size_t rows = large.buffer_size ? (size_t)large.buffer_size : 1;
+    float **arr[5] = {&large.halo_masses, &large.halo_coords, &large.star_rng, &large.sfr_rng, &large.xray_rng};
+    for (int k = 0; k < 5; k++)
+        if (!(*arr[k] = (float *)c21hip_ws(WS_ABI_DX_LARGE0 + k, rows * (k == 1 ? 3 : 1) * sizeof(float))))
+            return C21CM_MEMORY_ALLOC_ERROR;
+    float *overlap = (float *)c21hip_ws(WS_ABI_DX_OVERLAP, n_lo * sizeof(float));
+    if (!overlap) return C21CM_MEMORY_ALLOC_ERROR;
+    if ((st = c21cm_find_halos_grids(&f, boxes->hires_density, NULL, &large, NULL, overlap, NULL))) return st;
     if ((st = c21cm_sampler_setup(redshift, -1., random_seed, &s))) return st;
-    return c21cm_sample_halos_grids(&s, boxes->lowres_density, NULL, NULL, NULL, halos, NULL);
+    return c21cm_sample_halos_grids(&s, boxes->lowres_density, overlap, &large, NULL, halos, NULL);
 }

@@ -454,11 +454,12 @@ double expected_nhalo(double redshift) {
     return c21_Nhalo_General(redshift, log(M_min), log(M_max)) * volume * rho_m;
 }
 
-/* HaloCatalog.c:156-200: the radii DexM would filter at, each skipped when a halo of its mass is rarer
- * than 7 sigma under the DexM barrier (sheth_delc_dexm, hmf.c:143-146) */
-int c21cm_dexm_is_empty(double redshift) {
-    if (!simulation_options_global || !matter_options_global || !cosmo_params_global) return 0;
-    if (!c21_ps_ready()) init_ps();
+/* HaloCatalog.c:81-200: the radii DexM filters at, each skipped when a halo of its mass is rarer than
+ * 7 sigma under the DexM barrier (sheth_delc_dexm, hmf.c:143-146).  One walk serves both callers: with
+ * spec == NULL it stops at the first kept rung (c21cm_dexm_is_empty), else it stores every kept rung.
+ * Returns the number of kept rungs (1 for "at least one" without a spec), -1 for parameters that describe
+ * no box, -2 for more rungs than the spec holds. */
+static int dexm_walk(double redshift, c21cm_find_halos_spec *spec) {
     const SimulationOptions *so = simulation_options_global;
     const double l_factor = 0.620350491;
     const float growth = dicke(redshift);
@@ -467,26 +468,78 @@ int c21cm_dexm_is_empty(double redshift) {
     const float Delta_R = l_factor * 2. * so->BOX_LEN / (so->DIM + 0.0);
     /* Nothing non-finite may reach sigma_z0: its adaptive quadrature does not return for a mass that is
      * not a finite positive number.  Parameters that cannot describe a box (a non-finite or absurd box
-     * length, a step factor next to 1, a mass that overflows a float) answer "not empty", which makes
-     * ComputeHaloCatalog refuse.  Both walks are bounded. */
+     * length, a step factor next to 1, a mass that overflows a float) answer "no box", which makes
+     * c21cm_dexm_is_empty say "not empty" and ComputeHaloCatalog refuse.  Both walks are bounded. */
     if (!(so->DELTA_R_FACTOR >= 1.0001) || !(so->DELTA_R_FACTOR <= 1e3) || !(so->BOX_LEN > 0) ||
         !(so->BOX_LEN <= 1e6) || dim < 1 || so->DIM < 1 || !(growth > 0) || !isfinite(growth) ||
         !(M_MIN > 0) || !isfinite(M_MIN))
-        return 0;
+        return -1;
     float R = c21_MtoR(M_MIN * 1.01);
-    if (!(R > 0) || !isfinite(R)) return 0;
-    int steps = 0;
+    if (!(R > 0) || !isfinite(R)) return -1;
+    int steps = 0, kept = 0;
     while (R < l_factor * so->BOX_LEN && steps++ < 4096) R *= so->DELTA_R_FACTOR;
-    if (!(R >= l_factor * so->BOX_LEN) || !isfinite(R)) return 0;
+    if (!(R >= l_factor * so->BOX_LEN) || !isfinite(R)) return -1;
     steps = 0;
     while (R > 0.5 * Delta_R && c21_RtoM(R) >= M_MIN) {
-        if (steps++ >= 4096) return 0;
+        if (steps++ >= 4096) return -1;
         const float M = c21_RtoM(R);
-        if (!(M > 0) || !isfinite(M)) return 0;
+        if (!(M > 0) || !isfinite(M)) return -1;
         const double sig = sigma_z0(M), del = 1.686 / growth;
         const float delta_crit = growth * (sqrt(0.73) * del * (1. + 0.15 * pow(sig * sig / (0.73 * del * del), 0.05)));
-        if (!(sig * growth * 7. < delta_crit)) return 0;
+        if (!(sig * growth * 7. < delta_crit)) {
+            if (!spec) return 1;
+            if (kept >= C21CM_MAX_DEXM_RADII) return -2;
+            spec->R[kept] = R;
+            spec->mass[kept] = M;
+            spec->delta_crit[kept] = delta_crit;
+            kept++;
+        }
         R /= so->DELTA_R_FACTOR;
     }
-    return 1;
+    return kept;
+}
+
+int c21cm_dexm_is_empty(double redshift) {
+    if (!simulation_options_global || !matter_options_global || !cosmo_params_global) return 0;
+    if (!c21_ps_ready()) init_ps();
+    return dexm_walk(redshift, NULL) == 0;
+}
+
+int c21cm_dexm_ladder(double redshift, c21cm_find_halos_spec *spec) {
+    if (!spec) return C21CM_VALUE_ERROR;
+    if (!simulation_options_global || !matter_options_global || !cosmo_params_global) {
+        c21hip_set_error("DexM ladder: Broadcast_struct_global_all has not been called");
+        return C21CM_VALUE_ERROR;
+    }
+    if (!c21_ps_ready()) init_ps();
+    if (!c21_ps_ready()) return C21CM_VALUE_ERROR;
+    const SimulationOptions *so = simulation_options_global;
+    const MatterOptions *mo = matter_options_global;
+    memset(spec, 0, sizeof(*spec));
+    const int n = dexm_walk(redshift, spec);
+    if (n == -1) {
+        c21hip_set_error("DexM ladder: BOX_LEN, DIM, HII_DIM, DELTA_R_FACTOR and the cosmology describe no box");
+        return C21CM_VALUE_ERROR;
+    }
+    if (n == -2) {
+        c21hip_set_error("DexM ladder: more than %d radii; raise DELTA_R_FACTOR", C21CM_MAX_DEXM_RADII);
+        return C21CM_VALUE_ERROR;
+    }
+    spec->n_R = n;
+    spec->dim = so->DIM;
+    spec->dim_z = (int)(so->NON_CUBIC_FACTOR * so->DIM);
+    if (mo->SOURCE_MODEL == C21CM_SOURCE_CHMF_SAMPLER) {
+        spec->hii_dim = so->HII_DIM;
+        spec->hii_dim_z = (int)(so->NON_CUBIC_FACTOR * so->HII_DIM);
+    }
+    spec->halo_filter = mo->HALO_FILTER;
+    spec->optimize = mo->DEXM_OPTIMIZE ? 1 : 0;
+    spec->redshift = redshift;
+    spec->box_len = (double)so->BOX_LEN;
+    spec->box_len_z = (double)(so->BOX_LEN * so->NON_CUBIC_FACTOR);
+    spec->growth = (double)(float)dicke(redshift);
+    spec->r_overlap = so->DEXM_R_OVERLAP;
+    spec->optimize_minmass = so->DEXM_OPTIMIZE_MINMASS;
+    spec->rtom_unit = c21_RtoM(1.0);
+    return 0;
 }

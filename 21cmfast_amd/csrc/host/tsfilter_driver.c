@@ -15,6 +15,7 @@
 
 #include "../hip/c21hip.h"
 #include "c21cm_grid.h"
+#include "tsfilter.h"
 
 #define TRY(expr)         \
     do {                  \
@@ -25,17 +26,8 @@
         }                 \
     } while (0)
 
-typedef struct {
-    int nx, ny, nz, native;
-    size_t ntot, npad;
-    double box_len, box_len_z;
-    float *unf, *work;
-    double *partials, *stats; /* stats: 3 doubles per window, device */
-    void *stream;
-} tf_ctx;
-
-static int tf_setup(tf_ctx *c, int hii_dim, int hii_dim_z, double box_len, double box_len_z,
-                    int n_stats, void *stream) {
+int tf_setup(tf_ctx *c, int hii_dim, int hii_dim_z, double box_len, double box_len_z,
+             int n_stats, void *stream) {
     memset(c, 0, sizeof(*c));
     if (hii_dim < 2 || hii_dim_z < 2 || !(box_len > 0) || !(box_len_z > 0)) {
         c21hip_set_error("ts filter: bad grid geometry %d x %d x %d", hii_dim, hii_dim, hii_dim_z);
@@ -62,7 +54,7 @@ static int tf_setup(tf_ctx *c, int hii_dim, int hii_dim_z, double box_len, doubl
 }
 
 /* dense real input -> unfiltered spectrum / N   (prepare_filter_boxes, :511-530) */
-static int tf_forward(tf_ctx *c, const float *d_in) {
+int tf_forward(tf_ctx *c, const float *d_in) {
     int st;
     if (c->native)
         /* 1 / N is exact for the power-of-two sizes of the native transform */
@@ -76,8 +68,8 @@ static int tf_forward(tf_ctx *c, const float *d_in) {
 
 /* one window: spectrum x W -> real space -> max(v, min_value) * const_factor -> d_out,
  * statistics {min, max, sum} to stats3 (device) */
-static int tf_window(tf_ctx *c, int filter_type, float R, float R_param, int apply,
-                     double min_value, double const_factor, float *d_out, double *stats3) {
+int tf_window(tf_ctx *c, int filter_type, float R, float R_param, int apply,
+              double min_value, double const_factor, float *d_out, double *stats3) {
     int st;
     if (c->native) {
         if ((st = c21hip_split_filter_xy(c->unf, c->work, c->nx, c->ny, c->nz, c->box_len,

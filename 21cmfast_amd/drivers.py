@@ -404,6 +404,83 @@ def perturb_halo_catalog(inputs: Inputs, redshift, ics, catalog, prev_ts=None, p
                           _box_struct(S.IonizedBoxStruct, prev_ion), device)
 
 
+HALO_CATALOG_MEM_FACTOR = 1.2  # the reference's default (py21cmfast config)
+HALO_CATALOG_MIN_ROWS = 1000000  # get_halo_catalog_buffer_size (wrapper/cfuncs.py:57-79)
+
+
+def _halo_catalog(lib, redshift, icss, desc, seed, mem_factor, device):
+    """ComputeHaloCatalog with the globals already broadcast: the buffer holds (expected_nhalo + 1) times
+    ``mem_factor`` rows, at least HALO_CATALOG_MIN_ROWS."""
+    lib.expected_nhalo.restype = C.c_double
+    lib.expected_nhalo.argtypes = [C.c_double]
+    lib.ComputeHaloCatalog.restype = C.c_int
+    lib.ComputeHaloCatalog.argtypes = [C.c_float, C.c_float, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_void_p]
+    factor = HALO_CATALOG_MEM_FACTOR if mem_factor is None else float(mem_factor)
+    S.ConfigSettings.in_dll(lib, "config_settings").HALO_CATALOG_MEM_FACTOR = factor  # named by the overflow error
+    expected = lib.expected_nhalo(float(redshift))
+    if not np.isfinite(expected):
+        raise ValueError(f"expected_nhalo({redshift}) is not finite: the inputs describe no box")
+    rows = max(int((expected + 1.0) * factor), HALO_CATALOG_MIN_ROWS)
+    out = S.empty_halo_catalog(rows, device=device)
+    z_desc = -1.0 if desc is None else float(desc.redshift)
+    check(lib.ComputeHaloCatalog(z_desc, float(redshift), C.byref(icss), int(seed),
+                                 C.byref(desc) if desc is not None else None, C.byref(out)), "ComputeHaloCatalog")
+    out.redshift = float(redshift)
+    return out
+
+
+def _evolve_halos(lib, inputs, all_redshifts, is_node, icss, mem_factor, device):
+    """evolve_halos with the globals already broadcast"""
+    cats, desc = {}, None
+    for z in sorted(all_redshifts):  # lowest first: every node is the descendant of the next one up
+        cats[z] = _halo_catalog(lib, z, icss, desc, inputs.random_seed, mem_factor, device)
+        if z in is_node:
+            desc = cats[z]
+    return cats
+
+
+def determine_halo_catalog(inputs: Inputs, redshift, ics, descendant_halos=None, mem_factor=None, lib=None,
+                           device=None, data_path=None):
+    """The halo catalogue of one snapshot (reference: ``determine_halo_catalog``, drivers/single_field.py; C:
+    ComputeHaloCatalog).  SOURCE_MODEL = DEXM-ESF: the DexM finder on ``ics["hires_density"]``.
+    CHMF-SAMPLER: with ``descendant_halos`` (a catalogue this function returned for a LOWER redshift) the
+    progenitors of its halos; without, the DexM halos of the snapshot followed by the halos sampled in
+    every cell of ``ics["lowres_density"]``.
+
+    ``ics``: the initial conditions (a dict of arrays as ``run_coeval`` returns them under
+    ``"initial_conditions"``, or an InitialConditionsStruct).  The buffer holds ``(expected_nhalo(z) + 1) *
+    mem_factor`` rows (default: the reference's HALO_CATALOG_MEM_FACTOR of 1.2), at least a million.
+    Returns a ``structs.HaloCatalogStruct`` with ``n_halos`` set, its arrays under ``.arrays`` (numpy, or
+    torch tensors on ``device``) and its ``.redshift``."""
+    from . import grid_api as api
+
+    lib = lib or load(require_gpu=True)
+    if inputs.matter_options.SOURCE_MODEL not in (3, 4):
+        raise ValueError("SOURCE_MODEL has no halo catalogues")
+    _initialise(lib, inputs, data_path)
+    icss = ics if isinstance(ics, S.InitialConditionsStruct) else api.ics_struct(ics)
+    return _halo_catalog(lib, float(np.float32(redshift)), icss, descendant_halos, inputs.random_seed, mem_factor,
+                         device)
+
+
+def evolve_halos(inputs: Inputs, all_redshifts, ics, *, nodes=None, mem_factor=None, lib=None, device=None,
+                 data_path=None):
+    """The halo catalogues of a run (reference: ``evolve_halos``, drivers/coeval.py:435-517): the redshifts
+    are walked lowest first; the lowest gets the DexM halos and the sampled cells, every other one the
+    progenitors of the last NODE below it (``nodes``: the redshifts that are nodes; default: all of them).
+    Returns ``{z: HaloCatalogStruct}`` keyed by the float32 redshifts."""
+    from . import grid_api as api
+
+    lib = lib or load(require_gpu=True)
+    if inputs.matter_options.SOURCE_MODEL not in (3, 4):
+        return {}
+    _initialise(lib, inputs, data_path)
+    icss = ics if isinstance(ics, S.InitialConditionsStruct) else api.ics_struct(ics)
+    zs = [float(np.float32(z)) for z in all_redshifts]
+    is_node = set(zs) if nodes is None else {float(np.float32(z)) for z in nodes}
+    return _evolve_halos(lib, inputs, zs, is_node, icss, mem_factor, device)
+
+
 def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, lib=None,
                keep=("density", "velocity_z", "neutral_fraction", "z_reion", "brightness_temp") + TS_FIELDS,
                progress=None, halo_catalogs=None, inspect=None, keep_perturbed_halos=False):
@@ -413,7 +490,8 @@ def run_coeval(inputs: Inputs, out_redshifts, *, data_path=None, device=None, li
     previous one's boxes.  Supported source models: CONST-ION-EFF, E-INTEGRAL, L-INTEGRAL and,
     with catalogues from the caller, DEXM-ESF / CHMF-SAMPLER: ``halo_catalogs(z)`` returns the
     catalogue of node redshift z as ``structs.HaloCatalogStruct`` (``structs.halo_catalog``; numpy or
-    device arrays) -- finding and sampling halos is not part of this backend.
+    device arrays), or ``halo_catalogs="sample"`` finds and samples them from the initial conditions first
+    (``evolve_halos``).
 
     ``device``: a torch device string ("cuda") keeps every array in HBM (zero-copy entry points);
     None uses numpy arrays that the library stages.  ``data_path``: directory of the reference's
@@ -538,8 +616,8 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
     so, mo, ao, ap = (inputs.simulation_options, inputs.matter_options, inputs.astro_options,
                       inputs.astro_params)
     if mo.SOURCE_MODEL in (3, 4) and halo_catalogs is None:
-        raise NotImplementedError("SOURCE_MODEL = DEXM-ESF / CHMF-SAMPLER needs halo_catalogs(z): the halo "
-                                  "finder and sampler are not part of this backend")
+        raise NotImplementedError("SOURCE_MODEL = DEXM-ESF / CHMF-SAMPLER needs halo_catalogs: a function of "
+                                  "the redshift, or \"sample\" to find and sample them (evolve_halos)")
     mini = bool(ao.USE_MINI_HALOS)
     if mini and not (mo.SOURCE_MODEL in (1, 2, 3, 4) and ao.USE_TS_FLUCT):
         raise NotImplementedError("USE_MINI_HALOS runs with SOURCE_MODEL = E-INTEGRAL or L-INTEGRAL "
@@ -572,6 +650,10 @@ def _snapshots(inputs: Inputs, all_redshifts, is_node, chain, *, data_path, devi
         ics["lowres_vcb"] = new()
     icss = api.ics_struct(ics)
     check(lib.ComputeInitialConditions(inputs.random_seed, C.byref(icss)), "ComputeInitialConditions")
+    if isinstance(halo_catalogs, str):
+        if halo_catalogs != "sample":
+            raise ValueError('halo_catalogs is a function of the redshift, or "sample"')
+        halo_catalogs = _evolve_halos(lib, inputs, all_redshifts, is_node, icss, None, device).__getitem__
 
     lib.ComputeTsBox.restype = C.c_int
     lib.ComputeTsBox.argtypes = [C.c_float, C.c_float, C.c_float, C.c_short] + [C.c_void_p] * 5
@@ -1007,7 +1089,9 @@ def run_lightcone(inputs: Inputs, lightconer, node_redshifts, *, data_path=None,
     (n_pix, n_slices)}, ``lightcone_distances`` [Mpc], ``lightcone_redshifts``, ``node_redshifts``
     (descending), ``global_quantities`` {quantity: per-node box means (fp64)} and ``history`` as
     run_coeval's; an angular run adds ``latitude`` and ``longitude``.  ``keep_perturbed_halos`` with a
-    catalogue source model adds ``perturbed_halos`` {node redshift: PerturbedHalos}."""
+    catalogue source model adds ``perturbed_halos`` {node redshift: PerturbedHalos}.  ``halo_catalogs``: as
+    in ``run_coeval`` -- a function of the node redshift, or ``"sample"`` to find and sample the catalogues
+    from the initial conditions (``evolve_halos``: every node is the descendant of the next one up)."""
     so, ao, cp = inputs.simulation_options, inputs.astro_options, inputs.cosmo_params
     angular = isinstance(lightconer, AngularLightconer)
     if not (angular or isinstance(lightconer, RectilinearLightconer)):

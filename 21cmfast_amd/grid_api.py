@@ -803,6 +803,56 @@ def sample_halos_counts(n_conditions: int):
     return counts
 
 
+def dexm_spec(redshift, seed=0) -> S.FindHalosSpec:
+    """The DexM radius ladder of one snapshot from the broadcast globals (HaloCatalog.c:81-200): the kept
+    rungs (R, M, delta_crit), the growth factor and the options.  ``n_R == 0`` where the finder would find
+    nothing (``c21cm_dexm_is_empty``)."""
+    lib = load()
+    lib.c21cm_dexm_ladder.restype = C.c_int
+    lib.c21cm_dexm_ladder.argtypes = [C.c_double, C.c_void_p]
+    spec = S.FindHalosSpec()
+    check(lib.c21cm_dexm_ladder(float(redshift), C.byref(spec)), "c21cm_dexm_ladder")
+    spec.seed = int(seed)
+    return spec
+
+
+def find_halos(spec: S.FindHalosSpec, hires_density, out: S.HaloCatalogStruct, filtered=None, in_halo=None,
+               overlap=None, stream=None):
+    """The DexM halo finder on the MI355X (reference: HaloCatalog.c:38-456): ``hires_density`` [DIM^3] (the
+    z = 0 field) filtered on the ladder of ``spec``, every rung's candidates decided as the reference's
+    serial raster scan decides them, the halos appended to ``out`` (structs.empty_halo_catalog) in raster
+    order.  ``in_halo`` [DIM^3] uint8 receives the mask, ``overlap`` [HII_DIM^3] (needed when
+    ``spec.hii_dim > 0``) the covered fraction of every low-resolution cell; ``filtered`` [n_R, DIM^3] is the
+    test hook of ``spec.filtered_mode``.  Arrays are numpy or torch CUDA tensors.  Returns ``out``."""
+    lib = load()
+    lib.c21cm_find_halos_grids.restype = C.c_int
+    lib.c21cm_find_halos_grids.argtypes = [C.c_void_p] * 7
+    n = spec.dim * spec.dim * spec.dim_z
+    for name, a, size, width in (("hires_density", hires_density, n, 4), ("filtered", filtered, spec.n_R * n, 4),
+                                 ("in_halo", in_halo, n, 1),
+                                 ("overlap", overlap, spec.hii_dim * spec.hii_dim * spec.hii_dim_z, 4)):
+        if a is None:
+            continue
+        count = a.numel() if _is_torch(a) else a.size
+        itemsize = a.element_size() if _is_torch(a) else a.itemsize
+        contiguous = a.is_contiguous() if _is_torch(a) else a.flags["C_CONTIGUOUS"]
+        if count != size or itemsize != width or not contiguous:
+            raise ValueError(f"find_halos: {name} must be contiguous, {size} elements of {width} byte(s)")
+    check(lib.c21cm_find_halos_grids(C.byref(spec), _vptr(hires_density), _vptr(filtered), C.byref(out),
+                                     _vptr(in_halo), _vptr(overlap), _stream(stream)), "c21cm_find_halos_grids")
+    return out
+
+
+def find_halos_report() -> S.FindHalosReport:
+    """Per rung of the last ``find_halos`` call: candidates, accepted halos, rounds, serial tail."""
+    lib = load()
+    lib.c21cm_find_halos_last_report.restype = None
+    lib.c21cm_find_halos_last_report.argtypes = [C.c_void_p]
+    rep = S.FindHalosReport()
+    lib.c21cm_find_halos_last_report(C.byref(rep))
+    return rep
+
+
 def perturb_halos_grids(spec: S.PerturbHalosSpec, consts: S.HaloConsts, ics: dict,
                         catalog: S.HaloCatalogStruct, out: S.PerturbedHaloCatalogStruct,
                         log10_mturn_acg=None, log10_mturn_mcg=None, stream=None):

@@ -349,6 +349,29 @@ class SampleHalosSpec(_Base):
         ("tables", c_double_p)]
 
 
+MAX_DEXM_RADII = 256  # C21CM_MAX_DEXM_RADII
+
+
+class FindHalosSpec(_Base):
+    """``c21cm_find_halos_spec`` (include/c21cm_grid.h): the DexM halo finder's scalars and radius ladder."""
+
+    _fields_ = [(k, C.c_int) for k in (
+        "dim", "dim_z", "hii_dim", "hii_dim_z", "halo_filter", "n_R", "optimize", "filtered_mode", "path")] + [
+        ("seed", C.c_ulonglong)] + [(k, C.c_double) for k in (
+            "redshift", "box_len", "box_len_z", "growth", "r_overlap", "optimize_minmass", "rtom_unit")] + [
+        (k, C.c_float * MAX_DEXM_RADII) for k in ("R", "mass", "delta_crit")]
+
+
+class FindHalosReport(_Base):
+    """``c21cm_find_halos_report``: per rung the candidates, the accepted halos, the rounds and whether the
+    serial workgroup ran."""
+
+    _fields_ = [("n_R", C.c_int), ("n_halos", C.c_ulonglong),
+                ("candidates", C.c_uint * MAX_DEXM_RADII), ("accepted", C.c_uint * MAX_DEXM_RADII),
+                ("rounds", C.c_int * MAX_DEXM_RADII), ("tail", C.c_int * MAX_DEXM_RADII),
+                ("ms", C.c_double * 5)]  # transforms, compaction, decide, paint, serial (C21CM_DEXM_TIMING=1)
+
+
 def empty_halo_catalog(n, device=None) -> "HaloCatalogStruct":
     """A zeroed HaloCatalog of ``n`` rows: float32 numpy arrays, or torch tensors on ``device``, kept on
     the struct as ``arrays`` {field: array}; ``halo_coords`` is [n, 3]."""

@@ -629,7 +629,8 @@ int c21cm_perturb_halos_grids(const c21cm_perturb_halos_spec *spec, const c21cm_
  * removals) are kept as 64-bit integers of the float-rounded masses in units of 1 Msun: a float >= 2^24
  * is an integer, so the sums are exact and do not depend on the order of the additions. */
 enum { C21CM_HS_DRAW_MASS = 0, C21CM_HS_DRAW_SELECT = 1, C21CM_HS_DRAW_PERMUTE = 2, C21CM_HS_DRAW_POISSON = 3,
-       C21CM_HS_DRAW_POSITION = 4, C21CM_HS_DRAW_POSITION2 = 5, C21CM_HS_DRAW_PROPS = 6, C21CM_HS_DRAW_PROPS2 = 7 };
+       C21CM_HS_DRAW_POSITION = 4, C21CM_HS_DRAW_POSITION2 = 5, C21CM_HS_DRAW_PROPS = 6, C21CM_HS_DRAW_PROPS2 = 7,
+       C21CM_HS_DRAW_DEXM = 8 /* the deviates of a DexM halo: counter {0, 8, hi-res cell index low, high} */ };
 #define C21CM_MAX_HALO_CELL 100000 /* Stochasticity.h MAX_HALO_CELL */
 typedef struct c21cm_sample_halos_spec {
     int from_catalog;  /* 1: conditions are the halos of `desc`; 0: the cells of `density` */
@@ -675,6 +676,68 @@ int c21cm_sample_halos_last_counts(unsigned long long n, int *counts);
 /* the reference's DexM radius ladder (HaloCatalog.c:156-200) without a field: 1 when every scale is
  * skipped as rarer than 7 sigma, i.e. DexM would find nothing at this redshift in this box */
 int c21cm_dexm_is_empty(double redshift);
+
+/* ---- the DexM halo finder (HaloCatalog.c:38-456, check_halo, pixel_in_halo) with explicit scalars.
+ * The hi-res density is filtered on a descending ladder of radii; on each rung the reference walks the box
+ * serially in raster order and a cell with delta_m > delta_crit becomes a halo unless its own cell is in
+ * a halo already or a cell in a halo lies within r_overlap * R of it; an accepted halo paints its sphere.
+ * The result depends on the scan order.  Here the rung's candidates are compacted in raster order and
+ * decided in rounds that give the serial result exactly: a candidate that fails the mask
+ * test is rejected for good; one that passes and has no undecided earlier candidate within the range in
+ * which a halo of this rung can change its test is accepted; the accepted spheres are painted; repeat.
+ * A rung that is not finished after C21CM_DEXM_ROUND_CAP rounds is finished by one workgroup that walks
+ * the undecided candidates serially.
+ *
+ * Rows of `out` are in raster order of the hi-res cell: mass = the rung's M, coordinates = index *
+ * (BOX_LEN / DIM), the three deviates standard normals from one Philox block per halo (key as the sampler's,
+ * purpose C21CM_HS_DRAW_DEXM, counter the cell index).  total > out->buffer_size: ValueError, nothing written.
+ * On success the five arrays are zero from n_halos to buffer_size. */
+#define C21CM_MAX_DEXM_RADII 256
+#define C21CM_DEXM_ROUND_CAP 64  /* rounds per rung before the serial tail takes the rest (not tuned) */
+#define C21CM_DEXM_ROUND_BATCH 8 /* rounds between two readbacks of the undecided count */
+typedef struct c21cm_find_halos_spec {
+    int dim, dim_z;         /* the hi-res grid [dim][dim][dim_z] */
+    int hii_dim, hii_dim_z; /* the overlap box; 0: none */
+    int halo_filter;        /* 0 real-space top-hat, 1 sharp-k, 2 Gaussian */
+    int n_R;
+    int optimize;      /* DEXM_OPTIMIZE */
+    int filtered_mode; /* 0: `filtered` unused; 1: read (no transform runs); 2: written */
+    int path;          /* 0: rounds, then the serial tail; 1: serial only; 2: rounds only */
+    unsigned long long seed;
+    double redshift;
+    double box_len, box_len_z;
+    double growth;           /* dicke(z) as the reference's float */
+    double r_overlap;        /* DEXM_R_OVERLAP */
+    double optimize_minmass; /* DEXM_OPTIMIZE_MINMASS */
+    double rtom_unit;        /* mass of a sphere of radius 1 Mpc: MtoR(M) = cbrt(M / rtom_unit) */
+    float R[C21CM_MAX_DEXM_RADII], mass[C21CM_MAX_DEXM_RADII], delta_crit[C21CM_MAX_DEXM_RADII];
+} c21cm_find_halos_spec;
+
+typedef struct c21cm_find_halos_report {
+    int n_R;
+    unsigned long long n_halos;
+    /* per rung: candidates (cells over the threshold whose own cell is free), accepted halos, rounds run,
+     * 1 where the serial workgroup ran (path 1, or the tail after the round cap) */
+    unsigned int candidates[C21CM_MAX_DEXM_RADII], accepted[C21CM_MAX_DEXM_RADII];
+    int rounds[C21CM_MAX_DEXM_RADII], tail[C21CM_MAX_DEXM_RADII];
+    /* wall-clock milliseconds per phase, filled only when C21CM_DEXM_TIMING=1 drains the stream around each */
+    double ms[5];
+} c21cm_find_halos_report;
+enum { C21CM_DEXM_MS_TRANSFORMS = 0, C21CM_DEXM_MS_COMPACTION = 1, C21CM_DEXM_MS_DECIDE = 2, C21CM_DEXM_MS_PAINT = 3,
+       C21CM_DEXM_MS_SERIAL = 4 };
+
+/* HaloCatalog.c:81-200 from the broadcast globals: the kept rungs (R, M, delta_crit; those rarer than
+ * 7 sigma skipped), the growth factor and the options.  n_R == 0 exactly where c21cm_dexm_is_empty.
+ * Parameters that describe no box: ValueError at once; more than C21CM_MAX_DEXM_RADII rungs: ValueError. */
+int c21cm_dexm_ladder(double redshift, c21cm_find_halos_spec *spec);
+/* hires_density [dim^2 dim_z] (the z = 0 field; unused with filtered_mode 1); filtered [n_R][N] (test hook,
+ * see filtered_mode: the values are delta_m, already times growth); in_halo (may be NULL) [N] bytes, 1 inside
+ * a halo; overlap (NULL unless hii_dim > 0) [hii_dim^2 hii_dim_z]: the fraction of each low-res cell inside
+ * halos (HaloCatalog.c:361-420).  Arrays host or device. */
+int c21cm_find_halos_grids(const c21cm_find_halos_spec *spec, const float *hires_density, float *filtered,
+                           HaloCatalog *out, unsigned char *in_halo, float *overlap, void *stream);
+/* the report of the last c21cm_find_halos_grids call (also of one that stopped at the buffer check) */
+void c21cm_find_halos_last_report(c21cm_find_halos_report *report);
 
 /* min and max of n floats (host or device array), e.g. the table range of the above */
 int c21cm_grid_minmax(const float *values, size_t n, double out_minmax[2], void *stream);
