@@ -830,22 +830,47 @@ typedef struct c21hip_power_tabs { /* device pointers the driver fills (power_dr
     const int *group_wg;        /* n_groups + 1: the workgroups of group g (its bins g n_local ..) */
     int n_wg, n_groups, n_local;
     int ignore_zero_mode, ignore_kpar_zero;
+    /* cuts of the spherical average (read by the instantiations with cuts only): mu_min^2, mu_max^2, the wedge's
+     * slope^2 and its buffer */
+    int use_mu, use_wedge;
+    double mu_min_sq, mu_max_sq, wedge_slope_sq, wedge_buffer;
 } c21hip_power_tabs;
-size_t c21hip_power_lds_bytes(int n_local, int cylindrical);
-/* in[offsets[b] + (i ny + j) row_pitch + l] - mean[b] -> padded[b][i][j][l] for l < nz; *bad |= 1 on a non-finite
- * value.  mean[n_batch] (written here: each box's mean rounded to fp32) goes on to c21hip_power_bin; rowsum:
- * n_batch nx ny doubles of scratch */
+/* accumulators per bin: sum w P, sum w k, [sum w k_par (cylindrical)], [sum w P^2 (variance)], sum w */
+#define C21HIP_POWER_NV(cylindrical, variance) (3 + ((cylindrical) ? 1 : 0) + ((variance) ? 1 : 0))
+size_t c21hip_power_lds_bytes(int n_local, int cylindrical, int variance);
+/* (in[offsets[b] + (i ny + j) row_pitch + l] - mean[b]) [* wrow[i ny + j] * wz[l]] -> padded[b][i][j][l] for
+ * l < nz; *bad |= 1 on a non-finite value.  mean[n_batch] is written here and goes on to c21hip_power_bin: without
+ * a window each box's mean rounded to fp32 (a plain fp32 subtraction); with one (wrow and wz not NULL, device,
+ * nx ny and nz floats) the fp64 mean, subtracted in fp64.  rowsum: n_batch nx ny doubles of scratch */
 int c21hip_power_pack(const float *in, float *padded, int nx, int ny, int nz, long long row_pitch,
-                      const long long *offsets, int n_batch, double *rowsum, double *mean, int *bad, void *stream);
+                      const long long *offsets, int n_batch, double *rowsum, double *mean, const float *wrow,
+                      const float *wz, int *bad, void *stream);
 /* one pass over the half spectra complex[n_batch][nx][ny][nz/2+1] (spec2: cross power, or NULL) into
- * partials[n_batch][n_wg][n_local][3 or 4]; mean1 / mean2: the means the pack took out of each box */
+ * partials[n_batch][n_wg][n_local][NV]; mean1 / mean2: what goes back onto the k = 0 mode (the means the pack took
+ * out of each box; zeros with a window) */
 int c21hip_power_bin(const float *spec1, const float *spec2, int nx, int ny, int nz, int n_batch,
-                     int cylindrical, const c21hip_power_tabs *t, const double *mean1, const double *mean2,
-                     double *partials, int *bad, void *stream);
-/* partials -> totals[n_batch][n_groups n_local][3 or 4] -> means (device outputs) */
-int c21hip_power_finish(const double *partials, double *totals, int n_batch, int cylindrical,
-                        const c21hip_power_tabs *t, double scale, double *power, double *kmean,
+                     int cylindrical, int variance, const c21hip_power_tabs *t, const double *mean1,
+                     const double *mean2, double *partials, int *bad, void *stream);
+/* partials -> totals[n_batch][n_groups n_local][NV] -> means (device outputs); var (variance only): the population
+ * variance of the per-mode power, scale^2 (sum w P^2 / sum w - (sum w P / sum w)^2) */
+int c21hip_power_finish(const double *partials, double *totals, int n_batch, int cylindrical, int variance,
+                        const c21hip_power_tabs *t, double scale, double *power, double *kmean, double *var,
                         long long *counts, void *stream);
+
+/* ---- moments_kernels.hip : one-point statistics of boxes and lightcone chunks ---- */
+#define C21HIP_MOMENTS_MAX_BINS 4096 /* edges (fp64) and counts (32 bits) of one workgroup: 48 KiB of LDS and 8 bytes */
+/* pass 1: mean[b] = the fp64 mean of box b (row sums with lanes strided, then a fixed tree); *bad |= 1 on a
+ * non-finite value.  rowsum: n_batch nx ny doubles of scratch; part: c21hip_moments_part_doubles of scratch (the
+ * first level of a box's sum over its rows) */
+size_t c21hip_moments_part_doubles(int nx, int ny, int n_batch);
+int c21hip_moments_mean(const float *in, int nx, int ny, int nz, long long row_pitch, const long long *offsets,
+                        int n_batch, double *rowsum, double *part, double *mean, int *bad, void *stream);
+/* pass 2: moments[b] = {mean, sum d^2 / N, sum d^3 / N, sum d^4 / N}, d = (double)v - mean[b], in a fixed order;
+ * hist[b][n_bins] (zeroed here; skipped when n_bins = 0) counts np.digitize((double)v, edges) - 1 where it lies in
+ * [0, n_bins).  edges: device, n_bins + 1; rowsum: 3 n_batch nx ny doubles of scratch */
+int c21hip_moments_central(const float *in, int nx, int ny, int nz, long long row_pitch, const long long *offsets,
+                           int n_batch, const double *mean, int n_bins, const double *edges, double *rowsum,
+                           double *part, double *moments, unsigned long long *hist, void *stream);
 
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */

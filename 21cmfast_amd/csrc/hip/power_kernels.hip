@@ -26,6 +26,9 @@
 // Cylindrical spectra bin k_perp per row on the host (the rows are grouped by k_perp bin, each workgroup
 // holds rows of one group) and k_par = |kz| here.
 // HBM: 8 B per half-spectrum mode and field, read once; the partials are a few per cent of that.
+// Options (c21cm_power_opts; conventions: tests/power_stats_reference.py), each a template parameter so that the
+// instantiations without them stay the code they were: a taper in the pack (WIN), mu / wedge cuts in the bin step
+// (CUT), and the per-bin variance (VAR), one more accumulator sum(w P^2) through the same scan, rows and finish.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,24 +50,39 @@ int launch_status(const char *what) {
     return 0;
 }
 
-// one wave per row (b, i, j): in[offsets[b] + (i ny + j) row_pitch + l] - mean[b] -> padded[b][i][j][l], l < nz
+// one wave per row (b, i, j): in[offsets[b] + (i ny + j) row_pitch + l] - mean[b] -> padded[b][i][j][l], l < nz.
+// WIN: times the taper, (v - m) wrow[i ny + j] wz[l] with m the fp64 mean and the difference taken in fp64 (the
+// mean does not go back onto k = 0 here, so its fp32 rounding would stay in the modes the window couples to it)
+template <bool WIN>
 __global__ __launch_bounds__(kBlock) void power_pack_kernel(const float *__restrict__ in, float *__restrict__ padded,
                                                             long long rows_per_batch, long long n_rows, int nz,
                                                             long long row_pitch,
                                                             const long long *__restrict__ offsets,
-                                                            const double *__restrict__ mean, int *bad) {
+                                                            const double *__restrict__ mean,
+                                                            const float *__restrict__ wrow,
+                                                            const float *__restrict__ wz, int *bad) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (row >= n_rows) return;
     const long long b = row / rows_per_batch, r = row - b * rows_per_batch;
     const float *src = in + offsets[b] + r * row_pitch;
-    const float m = (float)mean[b];
     float *dst = padded + row * (2 * ((long long)nz / 2 + 1));
     int nonfinite = 0;
-    for (int l = lane; l < nz; l += 64) {
-        const float v = src[l];
-        nonfinite |= !isfinite(v);
-        dst[l] = v - m;
+    if (WIN) {
+        const double m = mean[b];
+        const float wr = wrow[r];
+        for (int l = lane; l < nz; l += 64) {
+            const float v = src[l];
+            nonfinite |= !isfinite(v);
+            dst[l] = ((float)((double)v - m) * wr) * wz[l];
+        }
+    } else {
+        const float m = (float)mean[b];
+        for (int l = lane; l < nz; l += 64) {
+            const float v = src[l];
+            nonfinite |= !isfinite(v);
+            dst[l] = v - m;
+        }
     }
     if (nonfinite) atomicOr(bad, 1);
 }
@@ -85,11 +103,11 @@ __global__ __launch_bounds__(kBlock) void power_rowsum_kernel(const float *__res
     if (lane == 0) rowsum[row] = s;
 }
 
-// mean[b] = the mean of box b rounded to fp32 (held as a double): one workgroup per box, thread t sums rows t,
-// t + 256, .. in order, then a fixed tree
+// mean[b] = the mean of box b rounded to fp32 (held as a double; round32 = 0: as it is): one workgroup per box,
+// thread t sums rows t, t + 256, .. in order, then a fixed tree
 __global__ __launch_bounds__(kBlock) void power_boxmean_kernel(const double *__restrict__ rowsum,
                                                                double *__restrict__ mean, long long rows_per_batch,
-                                                               double inv_cells) {
+                                                               double inv_cells, int round32) {
     __shared__ double red[kBlock];
     const double *src = rowsum + (long long)blockIdx.x * rows_per_batch;
     double s = 0.0;
@@ -101,20 +119,23 @@ __global__ __launch_bounds__(kBlock) void power_boxmean_kernel(const double *__r
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const float m = (float)(red[0] * inv_cells);
-        mean[blockIdx.x] = isfinite(m) ? (double)m : 0.0;  // a non-finite box is reported by the pack
+        const double md = red[0] * inv_cells;
+        const float m = (float)md;
+        mean[blockIdx.x] = isfinite(m) ? (round32 ? (double)m : md) : 0.0;  // a non-finite box is reported by the pack
     }
 }
 
-// NV accumulators per bin: sum w P, sum w k (|k| or k_perp), [sum w k_par], sum w
-template <bool CYL, bool CROSS>
+// NV accumulators per bin: sum w P, sum w k (|k| or k_perp), [sum w k_par], [sum w P^2], sum w.  VAR adds the
+// fourth through the same scan, rows and partials; CUT (spherical) applies the mu / wedge predicates of t: a mode
+// they drop stays in its run with weight 0, as one an ignore flag drops
+template <bool CYL, bool CROSS, bool VAR, bool CUT>
 __global__ __launch_bounds__(kBlock) void power_bin_kernel(const float2 *__restrict__ s1,
                                                            const float2 *__restrict__ s2, long long batch_c,
                                                            int ny, int nz, c21hip_power_tabs t,
                                                            const double *__restrict__ mean1,
                                                            const double *__restrict__ mean2, double n_cells,
                                                            double *__restrict__ partials, int *bad) {
-    constexpr int NV = CYL ? 4 : 3;
+    constexpr int NV = C21HIP_POWER_NV(CYL, VAR);
     extern __shared__ double lds[];
     const int nl = t.n_local, nh = nz / 2 + 1;
     double *edges = lds;             // nl + 1 (|k|^2 thresholds, or k_par edges when cylindrical)
@@ -138,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void power_bin_kernel(const float2 *__restr
         const bool active = e < n_el;
         const int rl = active ? (int)(e / nh) : nr;
         const int l = active ? (int)(e - (long long)rl * nh) : 0;
-        double p = 0.0, k1 = 0.0, k2 = 0.0;
+        double p = 0.0, k1 = 0.0, k2 = 0.0, pp = 0.0;
         int wt = 0, key = -1;
         if (active) {
             const int row = t.rows[r0 + rl];
@@ -179,11 +200,21 @@ __global__ __launch_bounds__(kBlock) void power_bin_kernel(const float2 *__restr
             bool use = bin >= 0 && bin < nl;
             if (t.ignore_zero_mode && row == 0 && l == 0) use = false;
             if (t.ignore_kpar_zero && l == 0) use = false;
+            if (CUT && !CYL) {
+                // fp64 + - x only, in the order the restatement (tests/power_stats_reference.py) writes them
+                const double kz2 = kz * kz;
+                if (t.use_mu && !(kz2 >= t.mu_min_sq * x && kz2 <= t.mu_max_sq * x)) use = false;
+                if (t.use_wedge) {
+                    const double a = fabs(kz) - t.wedge_buffer;
+                    if (!(a >= 0.0 && a * a >= t.wedge_slope_sq * (kx * kx + ky * ky))) use = false;
+                }
+            }
             // out-of-range modes join the nearest bin's run with nothing to add: keys stay monotone along a row
             key = bin < 0 ? 0 : (bin >= nl ? nl - 1 : bin);
             if (use) {
                 wt = (l == 0 || 2 * l == nz) ? 1 : 2;
                 p = q * wt;
+                if (VAR) pp = (q * q) * wt;
                 k1 *= wt;
                 k2 *= wt;
             } else {
@@ -199,12 +230,14 @@ __global__ __launch_bounds__(kBlock) void power_bin_kernel(const float2 *__restr
         for (int d = 1; d < 64; d <<= 1) {
             const double po = __shfl_up(p, d, 64), k1o = __shfl_up(k1, d, 64);
             const double k2o = CYL ? __shfl_up(k2, d, 64) : 0.0;
+            const double ppo = VAR ? __shfl_up(pp, d, 64) : 0.0;
             const int wo = __shfl_up(wt, d, 64), so = __shfl_up(seg, d, 64);
             if (lane >= d) {
                 if (!seg) {
                     p = po + p;
                     k1 = k1o + k1;
                     if (CYL) k2 = k2o + k2;
+                    if (VAR) pp = ppo + pp;
                     wt = wo + wt;
                 }
                 seg |= so;
@@ -218,6 +251,7 @@ __global__ __launch_bounds__(kBlock) void power_bin_kernel(const float2 *__restr
                 c[0] += p;
                 c[1] += k1;
                 if (CYL) c[2] += k2;
+                if (VAR) c[NV - 2] += pp;
                 c[NV - 1] += (double)wt;
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -262,13 +296,15 @@ __global__ __launch_bounds__(kBlock) void power_sum_kernel(const double *__restr
 }
 
 // means: power[b][d] = scale sum(w P) / sum(w), counts[b][d]; kmean[b][.] = |k| per bin, or k_perp per
-// k_perp bin followed by k_par per k_par bin (cylindrical).  Empty bins are NaN.
-template <bool CYL>
+// k_perp bin followed by k_par per k_par bin (cylindrical).  Empty bins are NaN.  VAR: var[b][d] = scale^2 (sum(w
+// P^2) / sum(w) - (sum(w P) / sum(w))^2), the population variance of the per-mode power.
+template <bool CYL, bool VAR>
 __global__ __launch_bounds__(kBlock) void power_mean_kernel(const double *__restrict__ totals, double scale,
                                                             int n_groups, int nl, long long n_batch,
                                                             double *__restrict__ power, double *__restrict__ kmean,
+                                                            double *__restrict__ var,
                                                             long long *__restrict__ counts) {
-    constexpr int NV = CYL ? 4 : 3;
+    constexpr int NV = C21HIP_POWER_NV(CYL, VAR);
     const long long n_dest = (long long)n_groups * nl, n_k = CYL ? n_groups + nl : nl;
     const long long per = n_dest + (CYL ? n_k : 0);
     const long long id = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -280,6 +316,10 @@ __global__ __launch_bounds__(kBlock) void power_mean_kernel(const double *__rest
         const double c = tb[o * NV + NV - 1];
         power[b * n_dest + o] = c > 0.0 ? tb[o * NV] / c * scale : nan;
         counts[b * n_dest + o] = (long long)c;
+        if (VAR) {
+            const double m1 = tb[o * NV] / c, m2 = tb[o * NV + NV - 2] / c;
+            var[b * n_dest + o] = c > 0.0 ? (m2 - m1 * m1) * (scale * scale) : nan;
+        }
         if (!CYL) kmean[b * n_k + o] = c > 0.0 ? tb[o * NV + 1] / c : nan;
         return;
     }
@@ -302,14 +342,16 @@ __global__ __launch_bounds__(kBlock) void power_mean_kernel(const double *__rest
 }
 }  // namespace
 
-extern "C" size_t c21hip_power_lds_bytes(int n_local, int cylindrical) {
-    return sizeof(double) * ((size_t)n_local + 1 + (size_t)kWaves * (size_t)n_local * (cylindrical ? 4 : 3));
+
+extern "C" size_t c21hip_power_lds_bytes(int n_local, int cylindrical, int variance) {
+    return sizeof(double) *
+           ((size_t)n_local + 1 + (size_t)kWaves * (size_t)n_local * C21HIP_POWER_NV(cylindrical, variance));
 }
 
 extern "C" int c21hip_power_pack(const float *in, float *padded, int nx, int ny, int nz, long long row_pitch,
-                                 const long long *offsets, int n_batch, double *rowsum, double *mean, int *bad,
-                                 void *stream) {
-    if (nx < 1 || ny < 1 || nz < 1 || n_batch < 1 || row_pitch < nz) {
+                                 const long long *offsets, int n_batch, double *rowsum, double *mean,
+                                 const float *wrow, const float *wz, int *bad, void *stream) {
+    if (nx < 1 || ny < 1 || nz < 1 || n_batch < 1 || row_pitch < nz || (wrow == nullptr) != (wz == nullptr)) {
         c21hip_set_error("power pack: bad launch shape");
         return C21CM_VALUE_ERROR;
     }
@@ -318,67 +360,120 @@ extern "C" int c21hip_power_pack(const float *in, float *padded, int nx, int ny,
     hipLaunchKernelGGL(power_rowsum_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, in, rowsum,
                        per, rows, nz, row_pitch, offsets);
     hipLaunchKernelGGL(power_boxmean_kernel, dim3((unsigned)n_batch), dim3(kBlock), 0, (hipStream_t)stream, rowsum,
-                       mean, per, 1.0 / ((double)per * (double)nz));
-    hipLaunchKernelGGL(power_pack_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, in, padded,
-                       per, rows, nz, row_pitch, offsets, mean, bad);
+                       mean, per, 1.0 / ((double)per * (double)nz), wrow ? 0 : 1);
+    if (wrow)
+        hipLaunchKernelGGL(power_pack_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, in,
+                           padded, per, rows, nz, row_pitch, offsets, mean, wrow, wz, bad);
+    else
+        hipLaunchKernelGGL(power_pack_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, in,
+                           padded, per, rows, nz, row_pitch, offsets, mean, wrow, wz, bad);
     return launch_status("power pack");
 }
 
+namespace {
+struct bin_args {
+    dim3 grid;
+    size_t lds;
+    hipStream_t stream;
+    const float2 *a, *c;
+    long long batch_c;
+    int ny, nz;
+    const c21hip_power_tabs *t;
+    const double *mean1, *mean2;
+    double n_cells;
+    double *partials;
+    int *bad;
+};
+
+template <bool CYL, bool CROSS, bool VAR, bool CUT>
+void launch_bin(const bin_args &g) {
+    static bool attr_done = false;  // once per instantiation
+    if (!attr_done) {
+        (void)hipFuncSetAttribute((const void *)power_bin_kernel<CYL, CROSS, VAR, CUT>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, C21HIP_POWER_MAX_LDS);
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((power_bin_kernel<CYL, CROSS, VAR, CUT>), g.grid, dim3(kBlock), g.lds, g.stream, g.a, g.c,
+                       g.batch_c, g.ny, g.nz, *g.t, g.mean1, g.mean2, g.n_cells, g.partials, g.bad);
+}
+
+template <bool CYL, bool VAR, bool CUT>
+void launch_bin_cross(const bin_args &g) {
+    if (g.c) launch_bin<CYL, true, VAR, CUT>(g);
+    else launch_bin<CYL, false, VAR, CUT>(g);
+}
+}  // namespace
+
 extern "C" int c21hip_power_bin(const float *spec1, const float *spec2, int nx, int ny, int nz, int n_batch,
-                                int cylindrical, const c21hip_power_tabs *t, const double *mean1,
+                                int cylindrical, int variance, const c21hip_power_tabs *t, const double *mean1,
                                 const double *mean2, double *partials, int *bad, void *stream) {
-    const size_t lds = c21hip_power_lds_bytes(t->n_local, cylindrical);
+    const size_t lds = c21hip_power_lds_bytes(t->n_local, cylindrical, variance);
+    const bool cut = t->use_mu || t->use_wedge;
     if (nx < 2 || ny < 2 || nz < 2 || n_batch < 1 || t->n_local < 1 || lds > C21HIP_POWER_MAX_LDS ||
-        n_batch > 65535) {
+        n_batch > 65535 || (cut && cylindrical)) {
         c21hip_set_error("power bin: bad launch shape");
         return C21CM_VALUE_ERROR;
     }
     if (t->n_wg == 0) return 0;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void *)power_bin_kernel<false, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C21HIP_POWER_MAX_LDS);
-        (void)hipFuncSetAttribute((const void *)power_bin_kernel<false, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C21HIP_POWER_MAX_LDS);
-        (void)hipFuncSetAttribute((const void *)power_bin_kernel<true, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C21HIP_POWER_MAX_LDS);
-        (void)hipFuncSetAttribute((const void *)power_bin_kernel<true, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C21HIP_POWER_MAX_LDS);
-        attr_done = true;
-    }
-    const long long batch_c = (long long)nx * ny * (nz / 2 + 1);
-    const float2 *a = (const float2 *)spec1, *c = (const float2 *)spec2;
-    const dim3 grid((unsigned)t->n_wg, (unsigned)n_batch);
-    const hipStream_t s = (hipStream_t)stream;
-    const double n_cells = (double)nx * (double)ny * (double)nz;
+    bin_args g;
+    g.grid = dim3((unsigned)t->n_wg, (unsigned)n_batch);
+    g.lds = lds;
+    g.stream = (hipStream_t)stream;
+    g.a = (const float2 *)spec1;
+    g.c = (const float2 *)spec2;
+    g.batch_c = (long long)nx * ny * (nz / 2 + 1);
+    g.ny = ny;
+    g.nz = nz;
+    g.t = t;
+    g.mean1 = mean1;
+    g.mean2 = mean2;
+    g.n_cells = (double)nx * (double)ny * (double)nz;
+    g.partials = partials;
+    g.bad = bad;
     if (cylindrical) {
-        if (c) hipLaunchKernelGGL((power_bin_kernel<true, true>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
-        else hipLaunchKernelGGL((power_bin_kernel<true, false>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
+        if (variance) launch_bin_cross<true, true, false>(g);
+        else launch_bin_cross<true, false, false>(g);
+    } else if (cut) {
+        if (variance) launch_bin_cross<false, true, true>(g);
+        else launch_bin_cross<false, false, true>(g);
     } else {
-        if (c) hipLaunchKernelGGL((power_bin_kernel<false, true>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
-        else hipLaunchKernelGGL((power_bin_kernel<false, false>), grid, dim3(kBlock), lds, s, a, c, batch_c, ny, nz, *t, mean1, mean2, n_cells, partials, bad);
+        if (variance) launch_bin_cross<false, true, false>(g);
+        else launch_bin_cross<false, false, false>(g);
     }
     return launch_status("power bin");
 }
 
 extern "C" int c21hip_power_finish(const double *partials, double *totals, int n_batch, int cylindrical,
-                                   const c21hip_power_tabs *t, double scale, double *power, double *kmean,
-                                   long long *counts, void *stream) {
+                                   int variance, const c21hip_power_tabs *t, double scale, double *power,
+                                   double *kmean, double *var, long long *counts, void *stream) {
     const long long n_dest = (long long)t->n_groups * t->n_local;
     const hipStream_t s = (hipStream_t)stream;
     long long n = n_dest * n_batch;
-    if (cylindrical)
+    const int nv = C21HIP_POWER_NV(cylindrical, variance);
+    if (nv == 5)
+        hipLaunchKernelGGL(power_sum_kernel<5>, dim3((unsigned)n), dim3(kBlock), 0, s, partials, totals, *t, n_dest);
+    else if (nv == 4)
         hipLaunchKernelGGL(power_sum_kernel<4>, dim3((unsigned)n), dim3(kBlock), 0, s, partials, totals, *t, n_dest);
     else
         hipLaunchKernelGGL(power_sum_kernel<3>, dim3((unsigned)n), dim3(kBlock), 0, s, partials, totals, *t, n_dest);
     int st = launch_status("power sum");
     if (st) return st;
     n = (n_dest + (cylindrical ? t->n_groups + t->n_local : 0)) * n_batch;
-    if (cylindrical)
-        hipLaunchKernelGGL(power_mean_kernel<true>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                           totals, scale, t->n_groups, t->n_local, (long long)n_batch, power, kmean, counts);
-    else
-        hipLaunchKernelGGL(power_mean_kernel<false>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                           totals, scale, t->n_groups, t->n_local, (long long)n_batch, power, kmean, counts);
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    if (cylindrical) {
+        if (variance)
+            hipLaunchKernelGGL((power_mean_kernel<true, true>), grid, dim3(kBlock), 0, s, totals, scale, t->n_groups,
+                               t->n_local, (long long)n_batch, power, kmean, var, counts);
+        else
+            hipLaunchKernelGGL((power_mean_kernel<true, false>), grid, dim3(kBlock), 0, s, totals, scale, t->n_groups,
+                               t->n_local, (long long)n_batch, power, kmean, var, counts);
+    } else {
+        if (variance)
+            hipLaunchKernelGGL((power_mean_kernel<false, true>), grid, dim3(kBlock), 0, s, totals, scale, t->n_groups,
+                               t->n_local, (long long)n_batch, power, kmean, var, counts);
+        else
+            hipLaunchKernelGGL((power_mean_kernel<false, false>), grid, dim3(kBlock), 0, s, totals, scale,
+                               t->n_groups, t->n_local, (long long)n_batch, power, kmean, var, counts);
+    }
     return launch_status("power mean");
 }

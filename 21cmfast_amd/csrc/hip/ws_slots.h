@@ -391,6 +391,11 @@ enum c21_ws_slot {
     WS_ABI_DX_LARGE0, /* the catalogue of large halos: masses, coordinates, three deviates */
     WS_ABI_DX_LARGE_LAST = WS_ABI_DX_LARGE0 + 4,
     WS_ABI_DX_OVERLAP, /* the overlap box */
+    /* ---- moments_driver.c ---- */
+    WS_MO_TAB,  /* histogram edges, batch offsets */
+    WS_MO_IN,   /* staged host field */
+    WS_MO_SUMS, /* row sums, means, moments, histogram */
+    WS_MO_FLAG,
 
     WS_COUNT
 };

@@ -2,7 +2,9 @@
  * power_driver.c -- C host driver of the binned power spectrum: pack -> batched r2c (rocFFT)
  * -> one binning launch -> fixed-order sums (csrc/hip/power_kernels.hip).  The host builds what is cheap and
  * must match numpy bit for bit: the per-axis wavenumbers (fftfreq(n, L/n) 2 pi) and, for cylindrical spectra,
- * the k_perp bin of every (x, y) row; the workgroups' row lists follow from them.
+ * the k_perp bin of every (x, y) row; the workgroups' row lists follow from them.  The options of
+ * c21cm_power_opts (taper, mu / wedge cuts, variance) select other instantiations of the same kernels; without
+ * them every launch and every value is what c21cm_power_spectrum_grids always did.
  */
 #include <math.h>
 #include <stdint.h>
@@ -68,10 +70,28 @@ static int digitize(const double *e, int n, double x) {
     return lo - 1;
 }
 
+static int window_ok(const double *w, int n) {
+    int nonzero = 0;
+    for (int i = 0; w && i < n; ++i) {
+        if (!isfinite(w[i])) return 0;
+        nonzero |= w[i] != 0.0;
+    }
+    return !w || nonzero;
+}
+
 int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, int ny, int nz, int n_batch,
                                long long row_pitch, const long long *batch_offsets, double Lx, double Ly,
                                double Lz, const c21cm_power_bins *bins, double *power, double *kmean,
                                long long *counts, void *stream) {
+    return c21cm_power_spectrum_ex_grids(field, field2, nx, ny, nz, n_batch, row_pitch, batch_offsets, Lx, Ly, Lz,
+                                         bins, NULL, power, kmean, NULL, counts, stream);
+}
+
+int c21cm_power_spectrum_ex_grids(const float *field, const float *field2, int nx, int ny, int nz, int n_batch,
+                                  long long row_pitch, const long long *batch_offsets, double Lx, double Ly,
+                                  double Lz, const c21cm_power_bins *bins, const c21cm_power_opts *opts,
+                                  double *power, double *kmean, double *variance, long long *counts,
+                                  void *stream) {
     int status = 0;
     unsigned char *host_tab = NULL;
     int *row_bin = NULL;
@@ -91,9 +111,28 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
         if (batch_offsets[b] < 0) return pw_fail("batch offsets must be >= 0");
     const int n_local = cyl ? bins->n_bins_par : bins->n_bins;
     const int n_groups = cyl ? bins->n_bins : 1;
-    if (c21hip_power_lds_bytes(n_local, cyl) > C21HIP_POWER_MAX_LDS) {
-        c21hip_set_error("power spectrum: %d %s bins do not fit the LDS of one workgroup", n_local,
-                         cyl ? "k_par" : "|k|");
+    const int want_var = opts && opts->want_variance;
+    const int use_mu = opts && opts->use_mu, use_wedge = opts && opts->use_wedge;
+    const int windowed = opts && (opts->window_x || opts->window_y || opts->window_z);
+    if (want_var && !variance) return pw_fail("want_variance needs a variance array");
+    if ((use_mu || use_wedge) && cyl) return pw_fail("mu and wedge cuts apply to spherical bins only");
+    if (use_mu) {
+        if (!(opts->mu_min_sq >= 0 && opts->mu_min_sq <= 1 && opts->mu_max_sq >= 0 && opts->mu_max_sq <= 1))
+            return pw_fail("mu_min and mu_max must lie in [0, 1]");
+        if (opts->mu_min_sq > opts->mu_max_sq) return pw_fail("mu_min must not exceed mu_max");
+    }
+    if (use_wedge && !(opts->wedge_slope_sq >= 0 && isfinite(opts->wedge_slope_sq) && opts->wedge_buffer >= 0 &&
+                       isfinite(opts->wedge_buffer)))
+        return pw_fail("wedge_slope and wedge_buffer must be finite and >= 0");
+    if (windowed) {
+        if (!window_ok(opts->window_x, nx) || !window_ok(opts->window_y, ny) || !window_ok(opts->window_z, nz))
+            return pw_fail("a window must be finite and not all zero");
+        if (!(isfinite(opts->inv_mean_w2) && opts->inv_mean_w2 > 0))
+            return pw_fail("inv_mean_w2 must be positive and finite");
+    }
+    if (c21hip_power_lds_bytes(n_local, cyl, want_var) > C21HIP_POWER_MAX_LDS) {
+        c21hip_set_error("power spectrum: %d %s bins%s do not fit the LDS of one workgroup", n_local,
+                         cyl ? "k_par" : "|k|", want_var ? " with the variance" : "");
         return C21CM_VALUE_ERROR;
     }
 
@@ -141,10 +180,13 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
     int n_wg = 0;
     for (int g = 0; g < n_groups; ++g) n_wg += (group_rows[g + 1] - group_rows[g] + rpw - 1) / rpw;
 
-    /* one table buffer: kx ky kz edges (double) | offsets (int64) | rows wg_rows group_wg (int) */
+    /* one table buffer: kx ky kz edges (double) | offsets (int64) | rows wg_rows group_wg (int) | with a window:
+     * its row factors wx[i] wy[j] and wz (float) */
     const size_t n_dbl = (size_t)nx + ny + nh + (size_t)n_local + 1;
     const size_t n_int = (size_t)n_used + (size_t)n_wg + 1 + (size_t)n_groups + 1;
-    const size_t tab_bytes = sizeof(double) * n_dbl + sizeof(long long) * (size_t)n_batch + sizeof(int) * n_int;
+    const size_t n_flt = windowed ? (size_t)n_rows + (size_t)nz : 0;
+    const size_t tab_bytes =
+        sizeof(double) * n_dbl + sizeof(long long) * (size_t)n_batch + sizeof(int) * n_int + sizeof(float) * n_flt;
     host_tab = (unsigned char *)malloc(tab_bytes);
     if (!host_tab) {
         free(ktab);
@@ -180,6 +222,13 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
         hgw[n_groups] = w;
         hwg[w] = n_used;
     }
+    if (windowed) {
+        /* the row factor is formed in fp64 and rounded once */
+        float *hw = (float *)(hgw + n_groups + 1);
+        const double *wx = opts->window_x, *wy = opts->window_y, *wz = opts->window_z;
+        for (int r = 0; r < n_rows; ++r) hw[r] = (float)((wx ? wx[r / ny] : 1.0) * (wy ? wy[r % ny] : 1.0));
+        for (int l = 0; l < nz; ++l) hw[n_rows + l] = (float)(wz ? wz[l] : 1.0);
+    }
     free(group_rows);
     free(ktab);
 
@@ -190,12 +239,15 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
     const size_t extent = (size_t)max_off + (size_t)(n_rows - 1) * (size_t)row_pitch + (size_t)nz;
     const size_t pad_floats = (size_t)n_rows * 2 * (size_t)nh * (size_t)n_batch;
     const int n_fields = field2 ? 2 : 1;
-    const int NV = cyl ? 4 : 3;
+    const int NV = C21HIP_POWER_NV(cyl, want_var);
     const size_t n_dest = (size_t)n_groups * n_local, n_k = cyl ? (size_t)n_groups + n_local : (size_t)n_local;
     const size_t part_dbl = (size_t)n_batch * n_wg * n_local * NV, tot_dbl = (size_t)n_batch * n_dest * NV;
-    const size_t out_dbl = (size_t)n_batch * (2 * n_dest + n_k); /* power, counts (int64), kmean */
-    /* the box means the pack takes out (per field), and the row sums they come from */
-    const size_t mean_dbl = (size_t)n_fields * (size_t)n_batch, rowsum_dbl = (size_t)n_rows * (size_t)n_batch;
+    /* power, counts (int64), kmean, variance */
+    const size_t out_dbl = (size_t)n_batch * ((want_var ? 3 : 2) * n_dest + n_k);
+    /* the box means the pack takes out (per field; behind them as many zeros: what goes back onto k = 0 with a
+     * window), and the row sums they come from */
+    const size_t mean_dbl = (size_t)(windowed ? 2 : 1) * n_fields * (size_t)n_batch;
+    const size_t rowsum_dbl = (size_t)n_rows * (size_t)n_batch;
 
     unsigned char *d_tab = (unsigned char *)c21hip_ws(WS_PW_TAB, tab_bytes);
     float *d_pad = (float *)c21hip_ws(WS_PW_PAD, sizeof(float) * pad_floats * n_fields);
@@ -222,8 +274,22 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
     t.n_local = n_local;
     t.ignore_zero_mode = bins->ignore_zero_mode != 0;
     t.ignore_kpar_zero = bins->ignore_kpar_zero != 0;
+    t.use_mu = use_mu;
+    t.use_wedge = use_wedge;
+    t.mu_min_sq = use_mu ? opts->mu_min_sq : 0.0;
+    t.mu_max_sq = use_mu ? opts->mu_max_sq : 1.0;
+    t.wedge_slope_sq = use_wedge ? opts->wedge_slope_sq : 0.0;
+    t.wedge_buffer = use_wedge ? opts->wedge_buffer : 0.0;
+    const float *d_wrow = windowed ? (const float *)(t.group_wg + n_groups + 1) : NULL;
+    const float *d_wz = windowed ? d_wrow + n_rows : NULL;
 
     double *d_mean = d_sums + part_dbl + tot_dbl + out_dbl, *d_rowsum = d_mean + mean_dbl;
+    /* what the bin kernel adds to the k = 0 mode */
+    const double *d_back = d_mean;
+    if (windowed) {
+        d_back = d_mean + (size_t)n_fields * n_batch;
+        TRY(c21hip_memset((void *)d_back, 0, sizeof(double) * (size_t)n_fields * n_batch, stream));
+    }
     const float *src[2] = {field, field2};
     int n_host = 0;
     for (int q = 0; q < n_fields; ++q) n_host += !c21hip_is_device_ptr(src[q]);
@@ -244,17 +310,20 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
         }
         float *pad = d_pad + (size_t)q * pad_floats;
         TRY(c21hip_power_pack(in, pad, nx, ny, nz, row_pitch, d_off, n_batch, d_rowsum, d_mean + (size_t)q * n_batch,
-                              d_bad, stream));
+                              d_wrow, d_wz, d_bad, stream));
         TRY(c21hip_fft_r2c_batched(pad, nx, ny, nz, n_batch, stream));
     }
     double *d_part = d_sums, *d_tot = d_part + part_dbl, *d_power = d_tot + tot_dbl;
     long long *d_counts = (long long *)(d_power + (size_t)n_batch * n_dest);
     double *d_kmean = (double *)(d_counts + (size_t)n_batch * n_dest);
-    TRY(c21hip_power_bin(d_pad, field2 ? d_pad + pad_floats : NULL, nx, ny, nz, n_batch, cyl, &t, d_mean,
-                         field2 ? d_mean + n_batch : NULL, d_part, d_bad, stream));
-    /* F = (V/N) DFT: P = |F|^2 / V = (V/N)^2 |DFT|^2 / V */
+    double *d_var = want_var ? d_kmean + (size_t)n_batch * n_k : NULL;
+    TRY(c21hip_power_bin(d_pad, field2 ? d_pad + pad_floats : NULL, nx, ny, nz, n_batch, cyl, want_var, &t, d_back,
+                         field2 ? d_back + n_batch : NULL, d_part, d_bad, stream));
+    /* F = (V/N) DFT: P = |F|^2 / V = (V/N)^2 |DFT|^2 / V; with a window over its mean square */
     const double vol = Lx * Ly * Lz, c = vol / ((double)nx * (double)ny * (double)nz);
-    TRY(c21hip_power_finish(d_part, d_tot, n_batch, cyl, &t, c * c / vol, d_power, d_kmean, d_counts, stream));
+    const double scale = windowed ? c * c / vol * opts->inv_mean_w2 : c * c / vol;
+    TRY(c21hip_power_finish(d_part, d_tot, n_batch, cyl, want_var, &t, scale, d_power, d_kmean, d_var, d_counts,
+                            stream));
     int bad = 0;
     TRY(c21hip_d2h(&bad, d_bad, sizeof(int), stream));
     TRY(c21hip_sync(stream));
@@ -263,11 +332,11 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
         status = C21CM_INFINITY_OR_NAN_ERROR;
         goto done;
     }
-    void *dst[3] = {power, counts, kmean};
-    const void *from[3] = {d_power, d_counts, d_kmean};
-    const size_t nb[3] = {sizeof(double) * n_batch * n_dest, sizeof(long long) * n_batch * n_dest,
-                          sizeof(double) * n_batch * n_k};
-    for (int q = 0; q < 3; ++q) {
+    void *dst[4] = {power, counts, kmean, variance};
+    const void *from[4] = {d_power, d_counts, d_kmean, d_var};
+    const size_t nb[4] = {sizeof(double) * n_batch * n_dest, sizeof(long long) * n_batch * n_dest,
+                          sizeof(double) * n_batch * n_k, sizeof(double) * n_batch * n_dest};
+    for (int q = 0; q < (want_var ? 4 : 3); ++q) {
         if (c21hip_is_device_ptr(dst[q])) TRY(c21hip_d2d(dst[q], from[q], nb[q], stream));
         else TRY(c21hip_d2h(dst[q], from[q], nb[q], stream));
     }

@@ -1292,14 +1292,23 @@ def spline_prefilter(boxes, order: int, out=None, stream=None):
 
 
 def power_spectrum(field, field2, shape, lengths, edges, edges_par=None, *, offsets=(0,), row_pitch=None,
-                   ignore_zero_mode=False, ignore_kperp_zero=False, ignore_kpar_zero=False, stream=None):
+                   ignore_zero_mode=False, ignore_kperp_zero=False, ignore_kpar_zero=False, windows=None,
+                   inv_mean_w2=1.0, mu_range=None, wedge=None, want_variance=False, entry=None, stream=None):
     """Binned power spectra of ``len(offsets)`` boxes of ``shape`` = (nx, ny, nz) cells and ``lengths``
     (Lx, Ly, Lz) read from the float32 array ``field`` (box b at flat element ``offsets[b] + (i ny + j)
     row_pitch + l``; ``row_pitch`` defaults to nz), cross spectra with ``field2`` (same layout) when given.
     ``edges``: the |k| edges, or the k_perp edges with ``edges_par`` the k_par edges (cylindrical).
     Returns ``(power, kmean, counts)``: float64, float64, int64, shaped (n_batch, n_bins) or (n_batch,
     n_perp, n_par) with kmean (n_batch, n_perp + n_par); numpy for numpy input, torch on the field's device
-    for a torch CUDA field."""
+    for a torch CUDA field.
+
+    The options of ``c21cm_power_opts``: ``windows`` = (wx, wy, wz), each None or float64 weights of that axis,
+    with ``inv_mean_w2`` = 1 / <W^2>; ``mu_range`` = (mu_min, mu_max); ``wedge`` = (slope, buffer);
+    ``want_variance`` appends the per-bin variance (shaped as power) to the result.  ``entry``: None takes
+    ``c21cm_power_spectrum_grids`` when every option is off and ``c21cm_power_spectrum_ex_grids`` otherwise;
+    "ex" forces the latter with the options struct, "ex-null" with ``opts = NULL``."""
+    if entry not in (None, "ex", "ex-null"):
+        raise ValueError(f"unknown entry {entry!r}")
     nx, ny, nz = (int(x) for x in shape)
     row_pitch = nz if row_pitch is None else int(row_pitch)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -1329,16 +1338,91 @@ def power_spectrum(field, field2, shape, lengths, edges, edges_par=None, *, offs
         power = torch.empty(pshape, dtype=torch.float64, device=field.device)
         kmean = torch.empty(kshape, dtype=torch.float64, device=field.device)
         counts = torch.empty(pshape, dtype=torch.int64, device=field.device)
+        variance = torch.empty(pshape, dtype=torch.float64, device=field.device) if want_variance else None
     else:
         power, kmean, counts = np.empty(pshape), np.empty(kshape), np.empty(pshape, np.int64)
+        variance = np.empty(pshape) if want_variance else None
+    Lx, Ly, Lz = (float(x) for x in lengths)
+    any_opt = windows is not None or mu_range is not None or wedge is not None or want_variance
+    if entry == "ex-null" and any_opt:
+        raise ValueError("entry='ex-null' carries no options")
+    if any_opt or entry is not None:
+        wins = [None if w is None else np.ascontiguousarray(w, np.float64) for w in (windows or (None,) * 3)]
+        for w, n, ax in zip(wins, (nx, ny, nz), "xyz"):
+            if w is not None and w.shape != (n,):
+                raise ValueError(f"the {ax} window must hold {n} weights")
+        opts = S.PowerOpts(
+            window_x=None if wins[0] is None else wins[0].ctypes.data_as(S.c_double_p),
+            window_y=None if wins[1] is None else wins[1].ctypes.data_as(S.c_double_p),
+            window_z=None if wins[2] is None else wins[2].ctypes.data_as(S.c_double_p),
+            inv_mean_w2=float(inv_mean_w2),
+            mu_min_sq=0.0 if mu_range is None else float(mu_range[0]) * float(mu_range[0]),
+            mu_max_sq=1.0 if mu_range is None else float(mu_range[1]) * float(mu_range[1]),
+            use_mu=int(mu_range is not None),
+            wedge_slope_sq=0.0 if wedge is None else float(wedge[0]) * float(wedge[0]),
+            wedge_buffer=0.0 if wedge is None else float(wedge[1]), use_wedge=int(wedge is not None),
+            want_variance=int(bool(want_variance)))
+        lib = load()
+        lib.c21cm_power_spectrum_ex_grids.restype = C.c_int
+        lib.c21cm_power_spectrum_ex_grids.argtypes = [
+            C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_double,
+            C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p]
+        check(lib.c21cm_power_spectrum_ex_grids(
+            _vptr(field), _vptr(field2), nx, ny, nz, n_batch, row_pitch, offsets.ctypes.data_as(C.c_void_p), Lx, Ly,
+            Lz, C.byref(bins), None if entry == "ex-null" else C.byref(opts), _vptr(power), _vptr(kmean),
+            _vptr(variance), _vptr(counts), _stream(stream)), "c21cm_power_spectrum_ex_grids")
+        return (power, kmean, counts, variance) if want_variance else (power, kmean, counts)
     lib = load()
     lib.c21cm_power_spectrum_grids.restype = C.c_int
     lib.c21cm_power_spectrum_grids.argtypes = [
         C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_double,
         C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    Lx, Ly, Lz = (float(x) for x in lengths)
     check(lib.c21cm_power_spectrum_grids(_vptr(field), _vptr(field2), nx, ny, nz, n_batch, row_pitch,
                                          offsets.ctypes.data_as(C.c_void_p), Lx, Ly, Lz, C.byref(bins),
                                          _vptr(power), _vptr(kmean), _vptr(counts), _stream(stream)),
           "c21cm_power_spectrum_grids")
     return power, kmean, counts
+
+
+def field_moments(field, shape, *, offsets=(0,), row_pitch=None, edges=None, stream=None):
+    """One-point statistics of ``len(offsets)`` boxes of ``shape`` = (nx, ny, nz) cells read from the float32
+    array ``field`` (the layout of ``power_spectrum``): ``(moments, hist)`` with moments float64 (n_batch, 4) =
+    mean, m2, m3, m4 (m_p = sum (v - mean)^p / N) and, with ``edges`` (n_bins + 1, increasing), hist int64
+    (n_batch, n_bins) = the cells per half-open bin as ``np.digitize``; hist is None without edges.  numpy for
+    numpy input, torch on the field's device for a torch CUDA field."""
+    nx, ny, nz = (int(x) for x in shape)
+    row_pitch = nz if row_pitch is None else int(row_pitch)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_batch = len(offsets)
+    _f32_dense(field, "field")
+    size = int(np.prod(field.shape, dtype=np.int64))
+    if n_batch < 1 or offsets.min() < 0 or offsets.max() + (nx * ny - 1) * row_pitch + nz > size:
+        raise ValueError("the boxes do not lie inside the field")
+    n_bins = 0
+    if edges is not None:
+        edges = np.ascontiguousarray(edges, np.float64)
+        if edges.ndim != 1 or edges.size < 2:
+            raise ValueError("edges must be a 1-D array of at least 2 values")
+        n_bins = len(edges) - 1
+    hist = None
+    if _is_torch(field):
+        import torch
+
+        moments = torch.empty((n_batch, 4), dtype=torch.float64, device=field.device)
+        if n_bins:
+            hist = torch.empty((n_batch, n_bins), dtype=torch.int64, device=field.device)
+    else:
+        moments = np.empty((n_batch, 4))
+        if n_bins:
+            hist = np.empty((n_batch, n_bins), np.int64)
+    lib = load()
+    lib.c21cm_field_moments_grids.restype = C.c_int
+    lib.c21cm_field_moments_grids.argtypes = [
+        C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+        C.c_void_p, C.c_void_p]
+    check(lib.c21cm_field_moments_grids(_vptr(field), nx, ny, nz, n_batch, row_pitch,
+                                        offsets.ctypes.data_as(C.c_void_p), n_bins,
+                                        None if edges is None else edges.ctypes.data_as(C.c_void_p), _vptr(moments),
+                                        _vptr(hist), _stream(stream)), "c21cm_field_moments_grids")
+    return moments, hist

@@ -11,6 +11,13 @@ The field is transformed in fp32 (rocFFT) and binned in fp64 by the gfx950 kerne
 counts are exact and two calls give the same bits.  Edges are built here with ``np.linspace`` /
 ``np.geomspace`` and passed to the kernel.
 
+Beyond powerbox (the conventions are written down in ``tests/power_stats_reference.py``): ``window`` tapers
+the field before the transform, f' = (f - mean) wx[i] wy[j] wz[l], the power divided by <W^2>;
+``mu_min`` / ``mu_max`` and ``wedge_slope`` / ``wedge_buffer`` cut the modes of the spherical average;
+``return_variance`` adds the population variance of the per-mode power in each bin.  ``get_moments``,
+``get_pdf`` and ``lightcone_moments`` are the one-point statistics of a box or of the chunks of a
+lightcone (``csrc/hip/moments_kernels.hip``).
+
 Arrays may be numpy (results are numpy) or torch CUDA tensors (results are torch tensors on the same
 device; the field never visits the host).  Argument errors are ``ValueError``; a non-finite field value
 raises ``BackendError`` (InfinityorNaNError).
@@ -118,6 +125,108 @@ def cylindrical_edges(shape, boxlength, kperp_bins=None, kpar_bins=None, log_bin
     return ep, ez
 
 
+_WINDOW_COEFFS = {
+    "hann": (0.5, 0.5),
+    "blackman": (0.42, 0.50, 0.08),
+    "blackmanharris": (0.35875, 0.48829, 0.14128, 0.01168),
+}
+
+
+def taper_window(name: str, n: int) -> np.ndarray:
+    """The symmetric cosine-sum window ``name`` ("hann", "blackman" or "blackmanharris") of ``n`` points,
+    float64: sum_k a_k cos(k x) over x = -pi .. pi in n - 1 steps (one point: 1)."""
+    if name not in _WINDOW_COEFFS:
+        raise ValueError(f"unknown window {name!r}; known: {sorted(_WINDOW_COEFFS)}")
+    if isinstance(n, (bool, np.bool_)) or int(n) != n or int(n) < 1:
+        raise ValueError("a window needs an integer length >= 1")
+    n = int(n)
+    if n == 1:
+        return np.ones(1)
+    x = np.linspace(-np.pi, np.pi, n)
+    w = np.zeros(n)
+    for k, a in enumerate(_WINDOW_COEFFS[name]):
+        w += a * np.cos(k * x)
+    return w
+
+
+def _one_window(w, n: int, axis: str):
+    if w is None:
+        return None
+    if isinstance(w, str):
+        w = taper_window(w, n)
+    else:
+        if _is_torch(w):
+            w = w.detach().cpu().numpy()
+        w = np.array(w, np.float64)
+        if w.shape != (n,):
+            raise ValueError(f"the {axis} window must be a 1-D array of {n} weights, got shape {w.shape}")
+    if not np.all(np.isfinite(w)):
+        raise ValueError(f"the {axis} window is not finite")
+    if not np.any(w != 0):
+        raise ValueError(f"the {axis} window is zero everywhere")
+    return w
+
+
+def resolve_window(window, shape):
+    """``window`` as ``get_power`` accepts it -> ``((wx, wy, wz), 1 / <W^2>)`` with each w float64 weights of
+    its axis or None, <W^2> = mean(wx^2) mean(wy^2) mean(wz^2) in fp64; ``(None, 1.0)`` without a window."""
+    if window is None:
+        return None, 1.0
+    if isinstance(window, tuple):
+        if len(window) != len(shape):
+            raise ValueError(f"a window tuple needs one entry per axis ({len(shape)}), got {len(window)}")
+        ws = tuple(_one_window(w, n, ax) for w, n, ax in zip(window, shape, "xyz"))
+    else:
+        ws = (None,) * (len(shape) - 1) + (_one_window(window, shape[-1], "xyz"[len(shape) - 1]),)
+    if all(w is None for w in ws):
+        return None, 1.0
+    mean_w2 = 1.0
+    for w in ws:
+        if w is not None:
+            mean_w2 = mean_w2 * float(np.mean(w * w))
+    return ws, 1.0 / mean_w2
+
+
+def resolve_cuts(mu_min=None, mu_max=None, wedge_slope=None, wedge_buffer=0.0):
+    """The cut keywords checked -> ``(mu_range, wedge)`` as ``grid_api.power_spectrum`` takes them: (mu_min,
+    mu_max) with the missing side 0 or 1, or None without a mu cut; (slope, buffer), or None without a wedge."""
+    def num(x, what):
+        if isinstance(x, (bool, np.bool_)) or np.ndim(x) != 0:
+            raise ValueError(f"{what} must be a number")
+        try:
+            x = float(x)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a number") from None
+        if not np.isfinite(x):
+            raise ValueError(f"{what} must be finite")
+        return x
+
+    mu_range = None
+    if mu_min is not None or mu_max is not None:
+        lo = 0.0 if mu_min is None else num(mu_min, "mu_min")
+        hi = 1.0 if mu_max is None else num(mu_max, "mu_max")
+        if not (0.0 <= lo <= 1.0 and 0.0 <= hi <= 1.0):
+            raise ValueError("mu_min and mu_max must lie in [0, 1]")
+        if lo > hi:
+            raise ValueError("mu_min must not exceed mu_max")
+        mu_range = (lo, hi)
+    buf = num(wedge_buffer, "wedge_buffer")
+    if buf < 0:
+        raise ValueError("wedge_buffer must be >= 0")
+    wedge = None
+    if wedge_slope is not None:
+        slope = num(wedge_slope, "wedge_slope")
+        if slope < 0:
+            raise ValueError("wedge_slope must be >= 0")
+        wedge = (slope, buf)
+    elif buf != 0:
+        raise ValueError("wedge_buffer needs a wedge_slope")
+    return mu_range, wedge
+
+
+_CUT_KEYS = ("mu_min", "mu_max", "wedge_slope", "wedge_buffer")
+
+
 def _check_field(field, what="field", deltax2=None):
     if field.ndim != 3:
         raise ValueError(f"{what} must be a 3-D array, got {field.ndim} dimensions")
@@ -132,37 +241,72 @@ def _check_field(field, what="field", deltax2=None):
 
 def get_power(field, boxlength, *, deltax2=None, bins=None, log_bins=False, ignore_zero_mode=False,
               bins_upto_boxlen=True, ignore_kperp_zero=False, ignore_kpar_zero=False, bin_ave=True,
-              return_counts=False):
+              return_counts=False, window=None, mu_min=None, mu_max=None, wedge_slope=None, wedge_buffer=0.0,
+              return_variance=False):
     """Spherically binned power spectrum of the 3-D ``field`` (any shape; the line of sight is the last
-    axis) in a box of ``boxlength`` (a scalar or 3 lengths).  Returns ``(power, k[, counts])``: ``k`` the
-    mean |k| of each bin, or the edges when ``bin_ave`` is False; empty bins are NaN."""
+    axis) in a box of ``boxlength`` (a scalar or 3 lengths).  Returns ``(power, k[, counts][, variance])``:
+    ``k`` the mean |k| of each bin, or the edges when ``bin_ave`` is False; empty bins are NaN.
+
+    ``window``: None; "hann", "blackman" or "blackmanharris" (``taper_window``) or nz weights, along the
+    last axis; or a tuple (wx, wy, wz) of None / name / weights per axis.  The field less its mean is
+    multiplied by the weights, the mean does not come back onto k = 0 and the power is divided by <W^2>.
+    ``mu_min`` / ``mu_max`` (0 <= mu <= 1, mu = |kz| / |k|) and ``wedge_slope`` / ``wedge_buffer`` (keep
+    |kz| - buffer >= slope k_perp) drop modes from the average; they combine with each other and with the
+    ignore flags and never move the edges.  ``return_variance``: the population variance of the per-mode
+    power over the modes of each bin (at most 1084 bins; 1417 without)."""
     _check_field(field, deltax2=deltax2)
     shape = _shape(field)
     L = _lengths(boxlength)
     edges = spherical_edges(shape, L, bins, log_bins, bins_upto_boxlen)
-    power, kmean, counts = api.power_spectrum(
+    windows, inv_w2 = resolve_window(window, shape)
+    mu_range, wedge = resolve_cuts(mu_min, mu_max, wedge_slope, wedge_buffer)
+    res = api.power_spectrum(
         _f32(field), None if deltax2 is None else _f32(deltax2), shape, L, edges,
-        ignore_zero_mode=ignore_zero_mode, ignore_kperp_zero=ignore_kperp_zero, ignore_kpar_zero=ignore_kpar_zero)
+        ignore_zero_mode=ignore_zero_mode, ignore_kperp_zero=ignore_kperp_zero, ignore_kpar_zero=ignore_kpar_zero,
+        windows=windows, inv_mean_w2=inv_w2, mu_range=mu_range, wedge=wedge, want_variance=return_variance)
+    power, kmean, counts = res[:3]
     k = kmean[0] if bin_ave else _edges_like(edges, power)
     out = (power[0], k)
-    return out + (counts[0],) if return_counts else out
+    if return_counts:
+        out += (counts[0],)
+    if return_variance:
+        out += (res[3][0],)
+    return out
 
 
 def get_cylindrical_power(field, boxlength, *, deltax2=None, kperp_bins=None, kpar_bins=None, log_bins=False,
-                          ignore_zero_mode=False, return_counts=False):
-    """Cylindrically binned power spectrum: ``(power[n_kperp, n_kpar], kperp, kpar[, counts])`` with
-    k_perp = sqrt(kx^2 + ky^2) and k_par = |kz| (the last axis); ``kperp`` / ``kpar`` are the mean
-    k_perp / k_par of the modes in each row / column of bins; empty bins are NaN."""
+                          ignore_zero_mode=False, return_counts=False, window=None, return_variance=False,
+                          **cuts):
+    """Cylindrically binned power spectrum: ``(power[n_kperp, n_kpar], kperp, kpar[, counts][, variance])``
+    with k_perp = sqrt(kx^2 + ky^2) and k_par = |kz| (the last axis); ``kperp`` / ``kpar`` are the mean
+    k_perp / k_par of the modes in each row / column of bins; empty bins are NaN.  ``window`` and
+    ``return_variance`` as in ``get_power`` (with the variance at most 877 k_par bins; 1084 without); the mu
+    and wedge cuts are for spherical spectra and rejected here."""
+    _reject_cuts(cuts)
     _check_field(field, deltax2=deltax2)
     shape = _shape(field)
     L = _lengths(boxlength)
     ep, ez = cylindrical_edges(shape, L, kperp_bins, kpar_bins, log_bins)
-    power, kmean, counts = api.power_spectrum(
+    windows, inv_w2 = resolve_window(window, shape)
+    res = api.power_spectrum(
         _f32(field), None if deltax2 is None else _f32(deltax2), shape, L, ep, ez,
-        ignore_zero_mode=ignore_zero_mode)
+        ignore_zero_mode=ignore_zero_mode, windows=windows, inv_mean_w2=inv_w2, want_variance=return_variance)
+    power, kmean, counts = res[:3]
     n = len(ep) - 1
     out = (power[0], kmean[0, :n], kmean[0, n:])
-    return out + (counts[0],) if return_counts else out
+    if return_counts:
+        out += (counts[0],)
+    if return_variance:
+        out += (res[3][0],)
+    return out
+
+
+def _reject_cuts(kw):
+    cut = sorted(set(kw) & set(_CUT_KEYS))
+    if cut:
+        raise ValueError(f"{', '.join(cut)}: mu and wedge cuts apply to spherical spectra only")
+    if kw:
+        raise TypeError(f"unexpected keyword arguments: {sorted(kw)}")
 
 
 def _edges_like(edges, ref):
@@ -178,7 +322,8 @@ class LightconePower:
     """What ``lightcone_power_spectra`` returns: ``power`` (n_chunks, n_bins) or (n_chunks, n_kperp,
     n_kpar); ``k`` (spherical) or ``kperp`` / ``kpar`` (cylindrical); ``chunk_starts`` (first slice of
     each chunk); ``redshifts`` (central redshift of each chunk, when slice redshifts were given);
-    ``counts`` (modes per bin, the same for every chunk)."""
+    ``counts`` (modes per bin, the same for every chunk); ``variance`` (shaped as ``power``: the variance of
+    the per-mode power in each bin, with ``return_variance=True``)."""
 
     power: object
     chunk_starts: np.ndarray
@@ -187,23 +332,11 @@ class LightconePower:
     kperp: object = None
     kpar: object = None
     redshifts: np.ndarray | None = None
+    variance: object = None
 
 
-def lightcone_power_spectra(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None,
-                            dimensionless=False, cylindrical=False, **binning):
-    """Power spectra of chunks of a rectilinear ``lightcone`` (nx, ny, n_slices; the line of sight last)
-    of cells of ``cell_size`` [Mpc]: chunk c is slices ``chunk_starts[c] .. + chunk_length`` (default: nx
-    slices, cubic chunks, back to back from slice 0, the remainder dropped), a box of (nx, ny,
-    chunk_length) cells.  All chunks go through one batched transform and one binning launch.
-    ``dimensionless`` multiplies by k^3 / (2 pi^2) with k the bin's mean |k| (cylindrical: sqrt(kperp^2 +
-    kpar^2) of the bin's means).  ``binning``: the keywords of ``get_power`` (or of
-    ``get_cylindrical_power`` when ``cylindrical``), ``deltax2`` a second lightcone for cross spectra."""
-    if lightcone.ndim != 3:
-        raise ValueError(f"lightcone must be a 3-D (nx, ny, n_slices) array, got {lightcone.ndim} dimensions")
-    nx, ny, ns = _shape(lightcone)
-    dx = float(cell_size)
-    if not (np.isfinite(dx) and dx > 0):
-        raise ValueError("cell_size must be positive and finite")
+def _chunks(ns: int, nx: int, chunk_length, chunk_starts, redshifts):
+    """(chunk length, first slices, central redshifts or None) of a lightcone of ``ns`` slices."""
     n = nx if chunk_length is None else chunk_length
     if isinstance(n, (bool, np.bool_)) or int(n) != n or int(n) < 2:
         raise ValueError("chunk_length must be an integer >= 2")
@@ -225,6 +358,27 @@ def lightcone_power_spectra(lightcone, cell_size, *, chunk_length=None, chunk_st
         if zs.shape != (ns,):
             raise ValueError(f"redshifts must hold one value per slice ({ns})")
         z = 0.5 * (zs[starts + (n - 1) // 2] + zs[starts + n // 2])
+    return n, starts, z
+
+
+def lightcone_power_spectra(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None,
+                            dimensionless=False, cylindrical=False, return_variance=False, **binning):
+    """Power spectra of chunks of a rectilinear ``lightcone`` (nx, ny, n_slices; the line of sight last)
+    of cells of ``cell_size`` [Mpc]: chunk c is slices ``chunk_starts[c] .. + chunk_length`` (default: nx
+    slices, cubic chunks, back to back from slice 0, the remainder dropped), a box of (nx, ny,
+    chunk_length) cells.  All chunks go through one batched transform and one binning launch.
+    ``dimensionless`` multiplies by k^3 / (2 pi^2) with k the bin's mean |k| (cylindrical: sqrt(kperp^2 +
+    kpar^2) of the bin's means).  ``binning``: the keywords of ``get_power`` (or of
+    ``get_cylindrical_power`` when ``cylindrical``), ``deltax2`` a second lightcone for cross spectra; a
+    ``window`` tapers every chunk (its last axis has ``chunk_length`` points).  ``return_variance`` fills
+    ``variance``, scaled by the square of the ``dimensionless`` factor."""
+    if lightcone.ndim != 3:
+        raise ValueError(f"lightcone must be a 3-D (nx, ny, n_slices) array, got {lightcone.ndim} dimensions")
+    nx, ny, ns = _shape(lightcone)
+    dx = float(cell_size)
+    if not (np.isfinite(dx) and dx > 0):
+        raise ValueError("cell_size must be positive and finite")
+    n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
     deltax2 = binning.pop("deltax2", None)
     if deltax2 is not None:
         if _is_torch(deltax2) != _is_torch(lightcone) or _shape(deltax2) != _shape(lightcone):
@@ -234,35 +388,160 @@ def lightcone_power_spectra(lightcone, cell_size, *, chunk_length=None, chunk_st
     f1 = _f32(lightcone)
     f2 = None if deltax2 is None else _f32(deltax2)
     if cylindrical:
-        allowed = {"kperp_bins", "kpar_bins", "log_bins", "ignore_zero_mode"}
+        cut = sorted(set(binning) & set(_CUT_KEYS))
+        if cut:
+            raise ValueError(f"{', '.join(cut)}: mu and wedge cuts apply to spherical spectra only")
+        allowed = {"kperp_bins", "kpar_bins", "log_bins", "ignore_zero_mode", "window"}
     else:
         allowed = {"bins", "log_bins", "ignore_zero_mode", "bins_upto_boxlen", "ignore_kperp_zero",
-                   "ignore_kpar_zero", "bin_ave"}
+                   "ignore_kpar_zero", "bin_ave", "window", *_CUT_KEYS}
     unknown = set(binning) - allowed
     if unknown:
         raise ValueError(f"unknown binning keywords: {sorted(unknown)}")
+    windows, inv_w2 = resolve_window(binning.get("window"), shape)
+    extra = dict(windows=windows, inv_mean_w2=inv_w2, want_variance=return_variance)
     if cylindrical:
         ep, ez = cylindrical_edges(shape, L, binning.get("kperp_bins"), binning.get("kpar_bins"),
                                    binning.get("log_bins", False))
-        power, kmean, counts = api.power_spectrum(f1, f2, shape, L, ep, ez, offsets=starts, row_pitch=ns,
-                                                  ignore_zero_mode=binning.get("ignore_zero_mode", False))
+        out = api.power_spectrum(f1, f2, shape, L, ep, ez, offsets=starts, row_pitch=ns,
+                                 ignore_zero_mode=binning.get("ignore_zero_mode", False), **extra)
+        power, kmean, counts = out[:3]
         m = len(ep) - 1
         res = LightconePower(power=power, chunk_starts=starts, counts=counts[0], kperp=kmean[0, :m],
-                             kpar=kmean[0, m:], redshifts=z)
+                             kpar=kmean[0, m:], redshifts=z, variance=out[3] if return_variance else None)
         if dimensionless:
             kk = (res.kperp[:, None] ** 2 + res.kpar[None, :] ** 2) ** 1.5
             res.power = power * (kk / (2 * np.pi**2))[None]
+            if return_variance:
+                res.variance = res.variance * ((kk / (2 * np.pi**2)) ** 2)[None]
         return res
+    mu_range, wedge = resolve_cuts(*(binning.get(key, 0.0 if key == "wedge_buffer" else None) for key in _CUT_KEYS))
     edges = spherical_edges(shape, L, binning.get("bins"), binning.get("log_bins", False),
                             binning.get("bins_upto_boxlen", True))
-    power, kmean, counts = api.power_spectrum(
+    out = api.power_spectrum(
         f1, f2, shape, L, edges, offsets=starts, row_pitch=ns,
         ignore_zero_mode=binning.get("ignore_zero_mode", False),
         ignore_kperp_zero=binning.get("ignore_kperp_zero", False),
-        ignore_kpar_zero=binning.get("ignore_kpar_zero", False))
+        ignore_kpar_zero=binning.get("ignore_kpar_zero", False), mu_range=mu_range, wedge=wedge, **extra)
+    power, kmean, counts = out[:3]
+    variance = out[3] if return_variance else None
     k = kmean[0]
     if dimensionless:
         power = power * (k**3 / (2 * np.pi**2))[None]
+        if return_variance:
+            variance = variance * ((k**3 / (2 * np.pi**2)) ** 2)[None]
     if not binning.get("bin_ave", True):
         k = _edges_like(edges, power)
-    return LightconePower(power=power, chunk_starts=starts, counts=counts[0], k=k, redshifts=z)
+    return LightconePower(power=power, chunk_starts=starts, counts=counts[0], k=k, redshifts=z, variance=variance)
+
+
+def _moment_stats(m):
+    """(mean, variance, skewness, kurtosis) from the last axis {mean, m2, m3, m4} of ``m``; a constant field
+    (m2 = 0) has NaN skewness and kurtosis."""
+    mean, m2, m3, m4 = m[..., 0], m[..., 1], m[..., 2], m[..., 3]
+    if _is_torch(m):
+        return mean, m2, m3 / m2**1.5, m4 / m2**2 - 3.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return mean, m2, m3 / m2**1.5, m4 / m2**2 - 3.0
+
+
+def get_moments(field):
+    """``(mean, variance, skewness, kurtosis)`` of a 3-D ``field``, in fp64 on the device: variance = m2 =
+    sum d^2 / N with d = v - mean, skewness = m3 / m2^1.5, kurtosis = m4 / m2^2 - 3 (NaN for a constant
+    field).  Scalars: Python floats for numpy input, 0-d tensors on the field's device for torch input."""
+    if field.ndim != 3:
+        raise ValueError(f"field must be a 3-D array, got {field.ndim} dimensions")
+    m, _ = api.field_moments(_f32(field), _shape(field))
+    out = _moment_stats(m[0])
+    return out if _is_torch(m) else tuple(float(x) for x in out)
+
+
+def _pdf_edges(bins, value_range, field):
+    if np.ndim(bins) == 0:
+        if isinstance(bins, (bool, np.bool_)) or int(bins) != bins or int(bins) < 1:
+            raise ValueError("bins must be an integer >= 1 or an array of edges")
+        if value_range is None:
+            if _is_torch(field):
+                lo, hi = (float(x) for x in field.aminmax())
+            else:
+                lo, hi = float(np.min(field)), float(np.max(field))
+        else:
+            if np.shape(value_range) != (2,):
+                raise ValueError("range must be (low, high)")
+            lo, hi = float(value_range[0]), float(value_range[1])
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError("the range of the bins is not finite")
+        if lo > hi:
+            raise ValueError("range needs low <= high")
+        if lo == hi:  # as np.histogram
+            lo, hi = lo - 0.5, hi + 0.5
+        return np.linspace(lo, hi, int(bins) + 1)
+    e = np.asarray(bins, np.float64)
+    if e.ndim != 1 or e.size < 2:
+        raise ValueError("bin edges must be a 1-D array of at least 2 values")
+    if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+        raise ValueError("bin edges must be finite and strictly increasing")
+    return e
+
+
+def _pdf_from_counts(hist, edges, density):
+    if not density:
+        return hist
+    if _is_torch(hist):
+        import torch
+
+        widths = torch.from_numpy(np.diff(edges)).to(hist.device)
+        return hist.to(torch.float64) / widths / hist.sum(dim=-1, keepdim=True).to(torch.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return hist / np.diff(edges) / hist.sum(axis=-1, keepdims=True)
+
+
+def get_pdf(field, bins, range=None, density=True):
+    """The histogram of a 3-D ``field``: ``(pdf, edges)``.  ``bins``: edges (1-D, increasing), or a count
+    for ``np.linspace(*range, bins + 1)`` with ``range`` defaulting to the field's minimum and maximum.
+    Bins are half-open as ``np.digitize`` everywhere in this module: a value on the last edge is not
+    counted (so the field's maximum falls out of the default range's last bin).  ``density``: counts /
+    (kept values x bin width), as ``np.histogram`` normalises; otherwise int64 counts.  At most 4096 bins."""
+    if field.ndim != 3:
+        raise ValueError(f"field must be a 3-D array, got {field.ndim} dimensions")
+    f = _f32(field)
+    edges = _pdf_edges(bins, range, f)
+    _, hist = api.field_moments(f, _shape(f), edges=edges)
+    return _pdf_from_counts(hist[0], edges, density), _edges_like(edges, hist)
+
+
+@dataclass
+class LightconeMoments:
+    """What ``lightcone_moments`` returns, one entry per chunk: ``mean``, ``variance``, ``skewness``,
+    ``kurtosis``; ``chunk_starts``; ``redshifts`` (when slice redshifts were given); with ``bins``: ``pdf``
+    (n_chunks, n_bins) and the ``edges`` all chunks share."""
+
+    mean: object
+    variance: object
+    skewness: object
+    kurtosis: object
+    chunk_starts: np.ndarray
+    redshifts: np.ndarray | None = None
+    pdf: object = None
+    edges: object = None
+
+
+def lightcone_moments(lightcone, *, chunk_length=None, chunk_starts=None, redshifts=None, bins=None, range=None,
+                      density=True):
+    """One-point statistics of the chunks of a rectilinear ``lightcone`` (nx, ny, n_slices), chunked as
+    ``lightcone_power_spectra`` chunks it and with its central-redshift rule; all chunks go through one
+    launch per pass.  ``bins`` / ``range`` / ``density`` as in ``get_pdf`` (the default range spans the
+    whole lightcone)."""
+    if lightcone.ndim != 3:
+        raise ValueError(f"lightcone must be a 3-D (nx, ny, n_slices) array, got {lightcone.ndim} dimensions")
+    nx, ny, ns = _shape(lightcone)
+    n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
+    f = _f32(lightcone)
+    edges = None if bins is None else _pdf_edges(bins, range, f)
+    m, hist = api.field_moments(f, (nx, ny, n), offsets=starts, row_pitch=ns, edges=edges)
+    mean, var, skew, kurt = _moment_stats(m)
+    res = LightconeMoments(mean=mean, variance=var, skewness=skew, kurtosis=kurt, chunk_starts=starts, redshifts=z)
+    if edges is not None:
+        res.pdf = _pdf_from_counts(hist, edges, density)
+        res.edges = _edges_like(edges, hist)
+    return res

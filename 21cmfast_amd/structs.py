@@ -547,6 +547,24 @@ class PowerBins(_Base):
     ]
 
 
+class PowerOpts(_Base):
+    """``c21cm_power_opts`` (include/c21cm_grid.h): taper, cuts and variance of a power spectrum."""
+
+    _fields_ = [
+        ("window_x", c_double_p),
+        ("window_y", c_double_p),
+        ("window_z", c_double_p),
+        ("inv_mean_w2", C.c_double),
+        ("mu_min_sq", C.c_double),
+        ("mu_max_sq", C.c_double),
+        ("use_mu", C.c_int),
+        ("wedge_slope_sq", C.c_double),
+        ("wedge_buffer", C.c_double),
+        ("use_wedge", C.c_int),
+        ("want_variance", C.c_int),
+    ]
+
+
 def brightness_spec(n_cells, redshift, cosmo=None, use_ts_fluct=False) -> "BrightnessSpec":
     """The two float constants of BrightnessTemperatureBox.c:43-49 for a CosmoParams struct
     (default cosmology if None)."""

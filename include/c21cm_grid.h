@@ -992,6 +992,49 @@ int c21cm_power_spectrum_grids(const float *field, const float *field2, int nx, 
                                double Lz, const c21cm_power_bins *bins, double *power, double *kmean,
                                long long *counts, void *stream);
 
+/* The options of c21cm_power_spectrum_ex_grids; NULL, or all of them off, is c21cm_power_spectrum_grids.
+ * Taper: with any window_* given the packed field is f' = (f - m) wx[i] wy[j] wz[l] (m the box mean, a NULL
+ * window is 1), the mean is NOT put back onto k = 0 and the power is multiplied by inv_mean_w2 = 1 / (mean(wx^2)
+ * mean(wy^2) mean(wz^2)).  The device multiplies by the fp32 roundings of wz[l] and of wx[i] wy[j] (formed in
+ * fp64).  Cuts (spherical bins only; fp64 + - x in this order, so numpy makes the same decisions): with x = (kx kx
+ * + ky ky) + kz kz a mode is used iff kz kz >= mu_min_sq x and kz kz <= mu_max_sq x (use_mu), and, with a = |kz|
+ * - wedge_buffer, iff a >= 0 and a a >= wedge_slope_sq (kx kx + ky ky) (use_wedge).  A cut mode counts nowhere;
+ * cuts combine with the ignore flags and never move edges.  want_variance: variance[n_batch][bins] = the
+ * population variance of the per-mode power over the modes of the full grid in the bin, sum(w P^2) / sum(w) -
+ * (sum(w P) / sum(w))^2 in fp64 (cross spectra: P = Re(F F2*) / V), NaN in empty bins; it costs LDS, so at most
+ * 1084 |k| bins or 877 k_par bins (1417 / 1084 without).  Errors are C21CM_VALUE_ERROR with a message. */
+typedef struct c21cm_power_opts {
+    const double *window_x;    /* host, nx weights, or NULL */
+    const double *window_y;    /* host, ny weights, or NULL */
+    const double *window_z;    /* host, nz weights, or NULL */
+    double inv_mean_w2;        /* 1 / <W^2> (used with a window) */
+    double mu_min_sq;          /* mu_min^2, 0 <= . <= mu_max_sq <= 1 */
+    double mu_max_sq;
+    int use_mu;
+    double wedge_slope_sq;     /* slope^2 >= 0 */
+    double wedge_buffer;       /* >= 0, in the units of k */
+    int use_wedge;
+    int want_variance;
+} c21cm_power_opts;
+
+/* variance: [n_batch][bins] as power; required iff opts->want_variance, otherwise ignored */
+int c21cm_power_spectrum_ex_grids(const float *field, const float *field2, int nx, int ny, int nz, int n_batch,
+                                  long long row_pitch, const long long *batch_offsets, double Lx, double Ly,
+                                  double Lz, const c21cm_power_bins *bins, const c21cm_power_opts *opts,
+                                  double *power, double *kmean, double *variance, long long *counts,
+                                  void *stream);
+
+/* ---- One-point statistics of boxes and lightcone chunks ----
+ * The layout of c21cm_power_spectrum_grids.  moments[b] = {mean, m2, m3, m4} with m_p = sum d^p / N, d = (double)v
+ * - mean, everything in fp64 and in a fixed order (two calls give the same bits).  With n_bins > 0 (edges: host,
+ * n_bins + 1, increasing): hist[b][i] = the cells with np.digitize((double)v, edges) - 1 == i, half-open bins (a
+ * value on the last edge is dropped); at most 4096 bins (the LDS of one workgroup), beyond that
+ * C21CM_VALUE_ERROR.  n_bins = 0: edges and hist are ignored.  field, moments and hist may be host or device
+ * memory.  A non-finite value is C21CM_INFINITY_OR_NAN_ERROR; nothing is written. */
+int c21cm_field_moments_grids(const float *field, int nx, int ny, int nz, int n_batch, long long row_pitch,
+                              const long long *batch_offsets, int n_bins, const double *edges, double *moments,
+                              long long *hist, void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
