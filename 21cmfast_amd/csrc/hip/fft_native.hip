@@ -632,6 +632,12 @@ struct LinePassArgs {
     // exp-MFP constants (ratio, ratio^2, ratio^3, exp(-1/ratio)) of sweep member 0 / 1: used beyond
     // the node tables' range (x >= (wev_n_nodes - 2) / 4), where the window is evaluated directly
     float wev_mfp[2][4];
+    // filter_box forms exp(-R / mfp) from a FLOAT quotient (filtering.c:320-322).  The window is linear in
+    // that term, W = W(exact term) + (term - exact) * (-3 ratio B(x) / (1 + x^2 ratio^2)^2), and the second
+    // part is a spike of width 1 / ratio at x = 0 (up to 3e-4 high at ratio 40) that nodes 1/4 apart cannot
+    // carry.  The node tables hold the smooth first part; the second is added in the kernel where it
+    // exceeds 2e-8: wev_mfp_fix[member] = (-3 (term - exact), the x below which it does).
+    float wev_mfp_fix[2][2];
     double wev_dkx, wev_dky, wev_dkz;
     // Item order of the main geometry (round 5 experiment): 0 = outer-major (k_y, then
     // the k_z column tiles).  Pass X, 1: column-tile-major -- the LAST items written are then whole
@@ -940,6 +946,24 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
         const float dd = fmaf(xx, r2, 1.f);
         return f * (-3.f * ra * __builtin_amdgcn_rcpf(dd * dd));
     };
+    // the exp-MFP window's term in (exp_term - its exact value), LinePassArgs::wev_mfp_fix: float suffices
+    // (the term is below 1e-3 and is needed to 1e-8).  Few modes are near enough to k = 0 to need it, so it
+    // is added in a pass of its own over the windows of the rare work items that hold such modes
+    // (eval_windows), not in weval_one.
+    auto weval_et_term = [&](const KAbs &k, float R, int rr) -> float {
+        const float ph = __fmul_rn(k.kh, R);
+        const float x = __fadd_rn(ph, __fmaf_rn(k.kl, R, __fmaf_rn(k.kh, R, -ph)));  // x0 of weval_one
+        if (!(x < (rr ? a.wev_mfp_fix[1][1] : a.wev_mfp_fix[0][1]))) return 0.f;
+        const float ra = rr ? a.wev_mfp[1][0] : a.wev_mfp[0][0], r2 = rr ? a.wev_mfp[1][1] : a.wev_mfp[0][1],
+                    r3 = rr ? a.wev_mfp[1][2] : a.wev_mfp[0][2];
+        const float xx = x * x;
+        const float rev = x * 0.15915494309189535f;  // x < 8: the hardware sine and cosine (of revolutions) are within 1e-6
+        const float sinc = (x < 1e-3f) ? 1.f : __builtin_amdgcn_sinf(rev) * __builtin_amdgcn_rcpf(x);
+        const float B = fmaf(fmaf(xx, r2, fmaf(2.f, ra, 1.f)) * ra, __builtin_amdgcn_cosf(rev),
+                             fmaf(xx, r2 - r3, ra + 1.f) * sinc);
+        const float dd = fmaf(xx, r2, 1.f);
+        return (rr ? a.wev_mfp_fix[1][0] : a.wev_mfp_fix[0][0]) * ra * B * __builtin_amdgcn_rcpf(dd * dd);
+    };
     auto weval_one = [&](const KAbs &k, float R, int type, const float *tab, int rr) -> float {
         const float ph = __fmul_rn(k.kh, R);
         const float e = __fmaf_rn(k.kl, R, __fmaf_rn(k.kh, R, -ph));
@@ -993,6 +1017,14 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
         }
         const float *tab0 = wnodes + max(wsel ? a.wev_tab[0][1] : a.wev_tab[0][0], 0) * per;
         const float *tab1 = wnodes + max(wsel ? a.wev_tab[1][1] : a.wev_tab[1][0], 0) * per;
+        // the same for all threads: does this item hold a mode below either member's wev_mfp_fix range?
+        bool et_fix = false;
+        if (type == 3) {
+            const float ky_lo = (it.filter_axis == 0) ? kyc[0] : 0.f;
+            const float kz_lo = (it.filter_axis == 0) ? (float)((double)(it.ct * TZ) * a.wev_dkz) : kzc[0];
+            const float k_lo = sqrtf(ky_lo * ky_lo + kz_lo * kz_lo);
+            et_fix = k_lo * a.wev_R[0] < a.wev_mfp_fix[0][1] || (NR > 1 && k_lo * a.wev_R[1] < a.wev_mfp_fix[1][1]);
+        }
 #pragma unroll
         for (int u = 0; u < NW; u++) {
             // F512: rows r0 + 64 u, u >= 4, are the mirror rows of thread (64 - r0, c4): it evaluates
@@ -1016,6 +1048,31 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
                 const float *tab = rr ? tab1 : tab0;
                 (WPRE ? wpre_half[rr] : wcur_half[rr]) =
                     make_float2(weval_one(k0, R, type, tab, rr), weval_one(k1, R, type, tab, rr));
+            }
+        }
+        if (__builtin_expect(et_fix, 0)) {  // the entries written above, once more
+#pragma unroll
+            for (int u = 0; u < NW; u++) {
+                if (FUSED && u >= NP && !(u == NP && r0 == 0)) continue;
+                const KAbs k0 = k_abs(wev_kx[WEVAL ? u : 0], kyc[0], kzc[0]);
+                const KAbs k1 = k_abs(wev_kx[WEVAL ? u : 0], kyc[1], kzc[1]);
+#pragma unroll
+                for (int rr = 0; rr < NR; rr++) {
+                    const float R = rr ? a.wev_R[1] : a.wev_R[0];
+                    float2 &w = (WPRE ? wpre[rr][WPRE ? u : 0] : wcur[rr][u]);
+                    w.x += weval_et_term(k0, R, rr);
+                    w.y += weval_et_term(k1, R, rr);
+                }
+            }
+            if (!FUSED && r0 == 0) {
+                const KAbs k0 = k_abs(wev_kx_half, kyc[0], kzc[0]), k1 = k_abs(wev_kx_half, kyc[1], kzc[1]);
+#pragma unroll
+                for (int rr = 0; rr < NR; rr++) {
+                    const float R = rr ? a.wev_R[1] : a.wev_R[0];
+                    float2 &w = (WPRE ? wpre_half[rr] : wcur_half[rr]);
+                    w.x += weval_et_term(k0, R, rr);
+                    w.y += weval_et_term(k1, R, rr);
+                }
             }
         }
         if constexpr (FUSED) {  // the mirror halves change hands through the first tile buffer (free here)
@@ -3810,6 +3867,17 @@ struct WevSet {
 WevSet g_wev;
 
 static bool wev_type_ok(int t) { return t == 0 || t == 1 || t == 3; }
+// The x below which the exp-MFP window's term in d_et = exp_term - exact (LinePassArgs::wev_mfp_fix) can
+// exceed 2e-8: scanned downwards from x = 8, beyond which it is below 3 |d_et| 1.2 / x^2 < 1e-9.
+static double wev_et_term_range(double ratio, double d_et) {
+    const double r2 = ratio * ratio, r3 = r2 * ratio;
+    for (double x = 8.; x > 0.; x -= 1. / 64.) {
+        const double B = (x * x * r2 + 2 * ratio + 1) * ratio * cos(x) + (x * x * (r2 - r3) + ratio + 1) * sin(x) / x;
+        const double d = x * x * r2 + 1;
+        if (fabs(3. * d_et * ratio * B / (d * d)) >= 2e-8) return x + 1. / 64.;
+    }
+    return d_et != 0. ? 1. / 64. : 0.;
+}
 // LDS of a pass-X launch with evaluated windows (bytes)
 static size_t wev_lds(int n, bool pair, int n_tabs, int n_nodes) {
     return sizeof(float2) * ((size_t)(pair ? 2 : 1) * n * TZ + n + (n >= 1024 ? n / 2 : 0)) +
@@ -3872,6 +3940,20 @@ static bool wev_use(LinePassArgs &a, int n_grids, const int filter_type[2], cons
         a.wev_mfp[m][1] = (float)(ratio * ratio);
         a.wev_mfp[m][2] = (float)(ratio * ratio * ratio);
         a.wev_mfp[m][3] = (float)exp((double)(-Rm / R_param[win]));
+        // (the radii of a call come back with every call: the range scan is done once per (R, mfp))
+        struct EtFix { float R, R_param, de3, range; };
+        static std::vector<EtFix> seen;
+        const EtFix *hit = nullptr;
+        for (const EtFix &f : seen)
+            if (f.R == Rm && f.R_param == R_param[win]) hit = &f;
+        if (!hit) {
+            const double d_et = exp((double)(-Rm / R_param[win])) - exp(-(double)Rm / (double)R_param[win]);
+            if (seen.size() >= 256) seen.clear();
+            seen.push_back(EtFix{Rm, R_param[win], (float)(-3. * d_et), (float)wev_et_term_range(ratio, d_et)});
+            hit = &seen.back();
+        }
+        a.wev_mfp_fix[m][0] = hit->de3;
+        a.wev_mfp_fix[m][1] = hit->range;
     }
     a.wev_dkx = 2.0 * M_PI / box_len;
     a.wev_dky = 2.0 * M_PI / box_len;
@@ -4282,6 +4364,12 @@ extern "C" int c21hip_wev_prepare(int filter_a, float R_param_a, int filter_b, f
             for (int i = 0; i < n_R; i++) {
                 FilterParams fp;
                 fill_filter(fp, 3, R[i], w.R_param[win], box_len, box_len_z);
+                // the smooth part of the window: exp(-R / mfp) exact instead of from the float quotient
+                // (LinePassArgs::wev_mfp_fix; the kernel adds the rest)
+                ExpMfpConsts &c = fp.mfp;
+                c.exp_term = exp(-(double)R[i] / (double)w.R_param[win]);
+                c.ts_0 = 6 * c.ratio3 - c.exp_term * (6 * c.ratio3 + 6 * c.ratio2 + 3 * c.ratio);
+                c.ts_2 = c.exp_term * (2 * c.ratio2 + 0.5 * c.ratio) - 2 * c.ts_0 * c.ratio2;
                 host[o++] = fp.mfp;
             }
         }

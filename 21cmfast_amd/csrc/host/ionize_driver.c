@@ -1455,10 +1455,19 @@ static int one_radius(ion_ctx *c, int R_ct, unsigned char *first_cross, int next
     }
     TRY(filter_to_real(c, c->delta_unf, c->delta_work, c->delta_fil, s->hii_filter, R, 0.f,
                        apply));
-    if (c->lagrangian)
+    /* Lagrangian loops without a recombination model or mini-halos, cell-scale radius: no window is applied
+     * (IonisationBox.c:606), so the emissivity and x_e grids are the clipped inputs up to the rounding of a
+     * transform pair -- which moves x_HI by up to 1e-5 where n_ion spans decades.  As in the fused loop's
+     * final sweep (r0_direct) they are taken from the inputs, clipped as prepare_box clips them. */
+    const int r0_inputs = R_ct == 0 && c->lagrangian && !c->recomb && !c->lag_mini && r0_direct();
+    if (r0_inputs)
+        TRY(c21hip_pack_clip(c->n_ion, c->stars_fil, c->nx, c->ny, c->nz, 1., 0., 1e20, c->stream));
+    else if (c->lagrangian)
         TRY(filter_to_real(c, c->stars_unf, c->stars_work, c->stars_fil, s->stars_filter, R,
                            (float)s->mfp_meandens, apply));
-    if (s->use_ts_fluct && !(R_ct == 0 && c->r0_mask)) /* (the fused cell-scale sweep reads the x_e input itself) */
+    if (s->use_ts_fluct && r0_inputs)
+        TRY(c21hip_pack_clip(c->xe_dense, c->xe_fil, c->nx, c->ny, c->nz, 1., 0., 1., c->stream));
+    else if (s->use_ts_fluct && !(R_ct == 0 && c->r0_mask)) /* (the fused cell-scale sweep reads the x_e input itself) */
         TRY(filter_to_real(c, c->xe_unf, c->xe_work, c->xe_fil, s->hii_filter, R, 0.f, apply));
 
     if (c->recomb) {

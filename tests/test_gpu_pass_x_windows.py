@@ -614,6 +614,20 @@ def test_evaluated_two_radii_excursion_pair(dev, n, covers):
     excursion_pair_eval(dev, box, *pair_radii(box, covers), covers)
 
 
+@pytest.mark.parametrize("n", [128, 512])
+def test_evaluated_two_radii_at_the_smallest_radii_of_the_loop(dev, n):
+    """R = 0.9305 and 1.2385 Mpc (indices 0 and 3 of the loop's ladder on 1.5 Mpc cells), mfp / R = 40 and 30:
+    filter_box forms exp(-R / mfp) from a float quotient, and what that rounding moves the term by is
+    multiplied by 6 (mfp / R)^3 at k = 0 -- 2.8e-4 and 3.0e-4 of the window for these two radii, in a spike
+    1 / 40 wide in kR that the lowest modes of the box sit in.  The node tables (1/4 apart) cannot carry it;
+    the kernel adds it to the windows of those modes."""
+    shape = x_shape(n)
+    box = box_of(shape)
+    R, R2 = float(np.float32(0.9305)), float(np.float32(0.9305 * 1.1 ** 3))
+    assert ((box.k * R > 0) & (box.k * R < 0.05)).any()  # modes inside the spike
+    excursion_pair_eval(dev, box, R, R2, MFP, True)
+
+
 def test_evaluated_two_radii_512_between_the_caps(dev):
     """512-point lines, top-hat + exp-MFP, two radii: 739 nodes fit beside the two tiles, so a set that needs
     more than that -- but fewer than 4096 -- evaluates directly from kR = 184 on, where the windows are still
