@@ -1453,19 +1453,29 @@ static int one_radius(ion_ctx *c, int R_ct, unsigned char *first_cross, int next
         TRY(c21hip_eulerian_mask(&args, c->nion_dense, xe_dense, mean_dev, first_cross, c->stream));
         goto done;
     }
-    TRY(filter_to_real(c, c->delta_unf, c->delta_work, c->delta_fil, s->hii_filter, R, 0.f,
-                       apply));
-    /* Lagrangian loops without a recombination model or mini-halos, cell-scale radius: no window is applied
-     * (IonisationBox.c:606), so the emissivity and x_e grids are the clipped inputs up to the rounding of a
-     * transform pair -- which moves x_HI by up to 1e-5 where n_ion spans decades.  As in the fused loop's
-     * final sweep (r0_direct) they are taken from the inputs, clipped as prepare_box clips them. */
-    const int r0_inputs = R_ct == 0 && c->lagrangian && !c->recomb && !c->lag_mini && r0_direct();
+    /* Eulerian loops with a recombination model, cell-scale radius: the density (and the x_e and N_rec grids
+     * below) from the clipped inputs, for the reason given next -- here the transform pair moves the box mean
+     * of f_coll by more than float arithmetic does (3.6e-7 against 7e-8 relative at 64^3) */
+    const int r0_eul = R_ct == 0 && !c->lagrangian && c->recomb && !c->mini && r0_direct();
+    if (r0_eul)
+        TRY(c21hip_pack_clip(c->density, c->delta_fil, c->nx, c->ny, c->nz, s->photoncons_adjustment_factor, -1.,
+                             1e6, c->stream));
+    else
+        TRY(filter_to_real(c, c->delta_unf, c->delta_work, c->delta_fil, s->hii_filter, R, 0.f,
+                           apply));
+    /* Lagrangian loops without mini-halos, cell-scale radius: no window is applied (IonisationBox.c:606), so
+     * the emissivity and x_e grids -- and, with a recombination model, the whalo_sfr and N_rec grids -- are the
+     * clipped inputs up to the rounding of a transform pair, which moves x_HI by up to 2e-5 where n_ion spans
+     * decades.  As in the fused loop's final sweep (r0_direct) they are taken from the inputs, clipped as
+     * prepare_box clips them.  (The fused recombination loop ends in this function too:
+     * finish_first_cross_recomb.) */
+    const int r0_inputs = R_ct == 0 && c->lagrangian && !c->lag_mini && r0_direct();
     if (r0_inputs)
         TRY(c21hip_pack_clip(c->n_ion, c->stars_fil, c->nx, c->ny, c->nz, 1., 0., 1e20, c->stream));
     else if (c->lagrangian)
         TRY(filter_to_real(c, c->stars_unf, c->stars_work, c->stars_fil, s->stars_filter, R,
                            (float)s->mfp_meandens, apply));
-    if (s->use_ts_fluct && r0_inputs)
+    if (s->use_ts_fluct && (r0_inputs || r0_eul))
         TRY(c21hip_pack_clip(c->xe_dense, c->xe_fil, c->nx, c->ny, c->nz, 1., 0., 1., c->stream));
     else if (s->use_ts_fluct && !(R_ct == 0 && c->r0_mask)) /* (the fused cell-scale sweep reads the x_e input itself) */
         TRY(filter_to_real(c, c->xe_unf, c->xe_work, c->xe_fil, s->hii_filter, R, 0.f, apply));
@@ -1476,10 +1486,14 @@ static int one_radius(ion_ctx *c, int R_ct, unsigned char *first_cross, int next
             status = C21CM_VALUE_ERROR;
             goto done;
         }
-        if (c->lagrangian)
+        if (r0_inputs)
+            TRY(c21hip_pack_clip(c->whalo_sfr, c->sfr_fil, c->nx, c->ny, c->nz, 1., 0., 1e20, c->stream));
+        else if (c->lagrangian)
             TRY(filter_to_real(c, c->sfr_unf, c->sfr_work, c->sfr_fil, s->stars_filter, R,
                                (float)s->mfp_meandens, apply));
-        if (c->filter_rec)
+        if (c->filter_rec && (r0_inputs || r0_eul))
+            TRY(c21hip_pack_clip(c->prev_nrec, c->nrec_fil, c->nx, c->ny, c->nz, 1., 0., 1e20, c->stream));
+        else if (c->filter_rec)
             TRY(filter_to_real(c, c->nrec_unf, c->nrec_work, c->nrec_fil, s->hii_filter, R, 0.f,
                                apply));
     }

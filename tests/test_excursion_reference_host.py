@@ -126,3 +126,154 @@ def test_accounting_bites_where_compare_does_not(oracle, restated):
     shifted = _corrupt(good, first_cross=(tile, np.where(fc[tile] > 0, fc[tile] + 1, 0)))
     with pytest.raises(AssertionError, match="decided cells with the wrong first-crossing radius"):
         X.check_outputs(ref, shifted)
+
+
+# ---- the recombination loop: tests/recomb_excursion_reference.py ---------------------------------------------
+
+import recomb_excursion_reference as RX  # noqa: E402
+
+#   variant: (recomb model, CELL_RECOMB, x_e grid, Lagrangian)
+RECOMB_VARIANTS = {"cell": (2, 1, False, True), "filtered": (2, 0, False, True), "xe": (2, 1, True, True),
+                   "homogeneous": (1, 1, False, True), "eulerian": (2, 0, False, False)}
+
+
+@pytest.mark.parametrize("n", [32, 35])
+@pytest.mark.parametrize("variant", list(RECOMB_VARIANTS))
+def test_recomb_pinned_to_the_oracle(oracle, variant, n):
+    """The oracle's own float32 outputs as the `device` of check_recomb_outputs: crossing flags and radii
+    through its mean_free_path, Gamma_12 at the crossing, z_reion against the previous one, x_HI, the
+    per-radius means and its N_rec recomputed from its own Gamma_12 and x_HI.
+
+    The oracle sends radius 0 through a float32 transform pair; the float32 chain of this pin does so too, with
+    the oracle's own transforms (recomb_excursion_reference.restate, round_trip0), and the x_HI bound is taken
+    from that chain.  Multiples of the MEASURED deviations the oracle used (bound: FACTOR = 4), printed as
+    `oracle used`: per-radius mean 1.25 (32^3, Lagrangian), 1.36 (35^3, Lagrangian), 1.00 / 1.34 (Eulerian);
+    Gamma_12 0.26 ... 0.47 of the relative-plus-absolute pair; x_HI 1.00 (32^3; it IS that round trip) and 0.83
+    (35^3) in the Lagrangian variants, 0.75 / 1.01 in the Eulerian one; N_rec 0 ulp."""
+    model, cell, ts, lag = RECOMB_VARIANTS[variant]
+    key = (n, n, model, cell, ts, lag, 10.0, 4242)
+    c = RX.restated(key, lambda g: oracle.fft_c2r(oracle.fft_r2c(g) / X.F32(g.size), g.shape[2]))
+    print(RX.caps_line(key, c))
+    out = oracle.ionize_grids(c.spec, c.inp.density, need_nion=not lag, **c.inp.kwargs())
+    out["f_coll_grid_mean"] = np.array(out["report"].f_coll_grid_mean[:c.spec.n_radii])
+    assert 0.05 < (out["mean_free_path"] > 0).mean() < 0.95
+    fig = RX.check_recomb_outputs(c.ref, out)
+    print(f"oracle used {variant} {n}^3: mean {fig['mean_dev_over_bound'] * X.FACTOR:.2f} x the measured deviation, "
+          f"Gamma_12 {fig['gamma_over_bound'] * X.FACTOR:.2f} x, x_HI {fig['xhi_dev'] / c.ref.xhi_tol * X.FACTOR:.2f} x, "
+          f"N_rec {fig['nrec_ulp']} ulp (bound {X.FACTOR} x, 1 ulp)")
+    print(RX.recomb_line(f"oracle {variant} {n}^3", c.ref, c.e, fig))
+    RX.check_recomb_outputs(c.ref, c.e["outputs"])  # the float32 chain's own outputs pass as well
+
+
+@pytest.mark.parametrize("name", list(RX.CASES))
+def test_recomb_caps_hold(name):
+    """Every box of test_gpu_recomb_cells.py: at t = 4 E32 the restatement alone leaves undecided no more than
+    the caps of excursion_reference.py (unchanged: 1e-4 of the flags, 1e-3 of the radii), both branches are
+    taken, the crossings spread over more than half the radii, and the float32 chain's own outputs pass the
+    accounting.  Prints the caps table, one RECOMB-CAPS line per box."""
+    c = RX.restated(name)
+    fig = RX.check_recomb_outputs(c.ref, c.e["outputs"])
+    print(RX.caps_line(name, c))
+    print(RX.recomb_line(name + " (float32 chain on the host)", c.ref, c.e, fig))
+    assert c.ref.flag_undecided_share <= X.FLAG_CAP
+    assert c.ref.radius_undecided_share <= X.RADIUS_CAP
+    assert 0.02 < c.ref.ionised_share < 0.98
+    assert len(np.unique(c.ref.cross_hi)) - 1 > c.spec.n_radii // 2
+
+
+def test_recomb_boxes_cover_both_radius_parities():
+    parities = {RX.make_case(*v)[0].n_radii % 2 for v in RX.CASES.values()}
+    assert parities == {0, 1}
+
+
+def _accepted_by_the_oracle_comparison(got, ref, prev_nrec):
+    """The comparison expressions of test_gpu_recomb.py::test_recombination_models_match_oracle for a box of
+    more than 1e6 cells and model 2 (all but compare(), which reads none of the grids corrupted here)."""
+    ion_g, ion_r = got["mean_free_path"] > 0, ref["mean_free_path"] > 0
+    assert 0.03 < ion_r.mean() < 0.97 and ion_r.size > 10**6
+    same = ion_g == ion_r
+    same_R = same & (got["mean_free_path"] == ref["mean_free_path"])
+    assert np.mean(~same_R & same) <= 2e-4
+    same = same_R
+    np.testing.assert_allclose(got["ionisation_rate_G12"][same], ref["ionisation_rate_G12"][same], rtol=2e-3,
+                               atol=2e-6 * float(ref["ionisation_rate_G12"].max()))
+    np.testing.assert_array_equal(got["mean_free_path"][same], ref["mean_free_path"][same])
+    np.testing.assert_allclose(got["cumulative_recombinations"][same], ref["cumulative_recombinations"][same],
+                               rtol=2e-4, atol=1e-7)
+    assert (ref["cumulative_recombinations"] > prev_nrec).any()
+    return True
+
+
+def test_recomb_accounting_bites():
+    """Four corruptions of the float32 chain's outputs of box r2 (128 x 128 x 256, 4.2 M cells); each must
+    raise, by name.  The first two pass the comparison of test_recombination_models_match_oracle, which masks
+    cells out before it compares and holds Gamma_12 to 2e-3: the gap this accounting closes, kept on record."""
+    c = RX.restated("r2")
+    ref, good = c.ref, c.e["outputs"]
+    RX.check_recomb_outputs(ref, good)
+    cross = RX.device_cross(good["mean_free_path"], ref.R32)
+
+    def corrupted(**changes):
+        new = dict(good)
+        for k, (where, value) in changes.items():
+            new[k] = good[k].copy()
+            new[k][where] = value
+        return new
+
+    # a 16 x 16 x 1 tile with the most radius-decided crossings below the largest radius
+    usable = ref.radius_decided & (cross > 0) & (cross < c.spec.n_radii)
+    z = int(np.argmax(usable.sum(axis=(0, 1))))
+    per_tile = usable[:, :, z].reshape(8, 16, 8, 16).sum(axis=(1, 3))
+    tx, ty = np.unravel_index(np.argmax(per_tile), per_tile.shape)
+    tile = (slice(16 * tx, 16 * tx + 16), slice(16 * ty, 16 * ty + 16), z)
+    assert usable[tile].sum() > 50 and 256 / cross.size < 1e-4
+
+    # (i) Gamma_12 x (1 + 1e-4) in the tile
+    one = corrupted(ionisation_rate_G12=(tile, good["ionisation_rate_G12"][tile] * X.F32(1 + 1e-4)))
+    with pytest.raises(AssertionError, match="Gamma_12 at the radius its mean free path names is off"):
+        RX.check_recomb_outputs(ref, one)
+    assert _accepted_by_the_oracle_comparison(one, good, c.inp.prev_nrec)
+
+    # (ii) the mean free path moved to the next radius in the tile, Gamma_12 left as it is
+    moved = np.where(usable[tile], ref.R32[np.minimum(cross[tile], c.spec.n_radii - 1)], good["mean_free_path"][tile])
+    two = corrupted(mean_free_path=(tile, moved))
+    with pytest.raises(AssertionError, match="decided cells with the wrong first-crossing radius"):
+        RX.check_recomb_outputs(ref, two)
+    assert _accepted_by_the_oracle_comparison(two, good, c.inp.prev_nrec)
+
+    # (iii) one z-line of N_rec evaluated with table row z_ct + 1
+    x, y = np.unravel_index(np.argmax((cross > 0).sum(axis=2)), cross.shape[:2])
+    shifted = ref.rates.cells(good["ionisation_rate_G12"], good["neutral_fraction"], row_shift=1).astype(X.F32)
+    assert (shifted[x, y] != good["cumulative_recombinations"][x, y]).sum() > 10
+    three = corrupted(cumulative_recombinations=((x, y), shifted[x, y]))
+    with pytest.raises(AssertionError, match="cumulative_recombinations more than 1 float ulp"):
+        RX.check_recomb_outputs(ref, three)
+
+    # (iv) z_reion set to the redshift on 20 crossing cells that held an earlier one
+    held = np.flatnonzero(((cross > 0) & (c.inp.prev_z_reion >= 0)).ravel())
+    pick = np.unravel_index(held[:: len(held) // 20][:20], cross.shape)
+    assert len(pick[0]) == 20 and (c.inp.prev_z_reion[pick] != X.F32(c.spec.redshift)).all()
+    four = corrupted(z_reion=(pick, X.F32(c.spec.redshift)))
+    with pytest.raises(AssertionError, match="z_reion is not the previous z_reion on a crossing cell that held one: 20 cells"):
+        RX.check_recomb_outputs(ref, four)
+
+
+def test_rr_spline_restatement_matches_the_oracle(oracle):
+    """The numpy rr_spline against oracle_splined_recombination_rate: rows, the floor and the ceiling of
+    ln Gamma, knots, interior points."""
+    import ctypes as C
+
+    from recomb_helpers import synthetic_rr_tables
+
+    lib = oracle.load()
+    lib.oracle_splined_recombination_rate.restype = C.c_double
+    lib.oracle_splined_recombination_rate.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double]
+    y, c = synthetic_rr_tables()
+    knots = RX.ln_gamma_knots()
+    rng = np.random.default_rng(1)
+    z = np.concatenate([rng.uniform(-1.0, 70.0, 300), [0.0, 0.1, 0.3, 59.8, 1e7]])
+    g = np.concatenate([np.exp(rng.uniform(-12.0, 17.0, 300)), [0.0, np.exp(-10.0), np.exp(knots[-1]), 1e12, np.exp(knots[7])]])
+    want = np.array([lib.oracle_splined_recombination_rate(y.ctypes.data, c.ctypes.data, zz, gg) for zz, gg in zip(z, g)])
+    got = RX.rr_spline(y, c, z, g)
+    assert (want == 0).sum() > 10 and (want > 0).sum() > 200
+    np.testing.assert_allclose(got, want, rtol=1e-13, atol=0)
