@@ -9,21 +9,15 @@ namespace {
 constexpr double kFractFloatErr = 1e-7;  // reference: Constants.h FRACT_FLOAT_ERR
 
 // reference: hmf.c:1187-1203 (float in, double polynomial, float out).  The result is a float
-// and the formula itself is a 1.2e-7 approximation of erfc, so the two expensive pieces are
-// evaluated to float accuracy instead of with ~55 fp64 instructions: 1/(1 + q/2) from the
-// hardware reciprocal plus one Newton step (1e-14), and exp(u) as 2^n * exp2(frac) with the
-// hardware exp2 on the fraction (2e-7 relative).  The polynomial stays in double.  The pass-Z
-// sweep that carries this was fp64-ALU bound (0.48 ms against 0.20 ms for the plain store).
-// Round 5 (C21X_ERFC_F32, default): the whole evaluation in fp32 with explicit FMAs -- Horner in float, the
-// reciprocal with one float Newton step, exp(u) = 2^n exp2(fma(u, log2 e, -n)).  The closed-form pass Z was
+// and the formula itself is a 1.2e-7 approximation of erfc, so the whole evaluation runs in fp32 with explicit
+// FMAs -- Horner in float, 1/(1 + q/2) from the hardware reciprocal plus one float Newton step,
+// exp(u) = 2^n exp2(fma(u, log2 e, -n)) with the hardware exp2 on the fraction.  The closed-form pass Z was
 // fp64-issue bound (1600 of its 5300 instructions were the double polynomial, 4.4 cycles each against 2.7):
 // against the double polynomial the float result moves by <= 7e-7 relative for x < 3, i.e. where f_coll zeta
 // can reach a barrier (2e-6 at x = 6, f ~ 1e-17), mean 1e-7 -- the size of the fit's own error.  Every
 // sweep of the closed form (dense, banded, deferred, stand-alone) calls this one function.
-#ifndef C21X_ERFC_F32
-#define C21X_ERFC_F32 1
-#endif
-#if C21X_ERFC_F32
+// (The double polynomial with only the reciprocal and the exponential in float, rounds 2-4: slower by that
+//  measure; removed.)
 __device__ __forceinline__ float erfcc_f(float x) {
     const float q = fabsf(x);
     const float d = __fmaf_rn(0.5f, q, 1.0f);
@@ -46,30 +40,6 @@ __device__ __forceinline__ float erfcc_f(float x) {
     const float ans = t * e;
     return x >= 0.0f ? ans : 2.0f - ans;
 }
-#else
-__device__ __forceinline__ float erfcc_f(float x) {
-    const double q = fabs((double)x);
-    const double d = 1.0 + 0.5 * q;
-    const double t0 = (double)__builtin_amdgcn_rcpf((float)d);
-    const double t = t0 * (2.0 - d * t0);
-    const double u = -q * q - 1.2655122 +
-                     t * (1.0000237 +
-                          t * (0.374092 +
-                               t * (0.0967842 +
-                                    t * (-0.1862881 +
-                                         t * (0.2788681 +
-                                              t * (-1.13520398 +
-                                                   t * (1.4885159 +
-                                                        t * (-0.82215223 + t * 0.17087277))))))));
-    const double w = u * 1.4426950408889634;  // log2(e)
-    const double n = floor(w);
-    // below 2^-160 the float result is zero anyway; clamping keeps the int conversion defined
-    const float e = (n < -160.) ? 0.f
-                                : ldexpf(__builtin_amdgcn_exp2f((float)(w - n)), (int)n);
-    const float ans = (float)(t * (double)e);
-    return x >= 0.0f ? ans : 2.0f - ans;
-}
-#endif
 
 // reference: hmf.c:1205-1241.  sig (from the float sigmas) is precomputed on the host.
 __device__ __forceinline__ double fgtrm_bias_fast(float growthf, float del_bias, double sig,

@@ -4,80 +4,14 @@
 // namespace; the arithmetic of a line is the same instruction sequence wherever it is instantiated
 // (-ffp-contract=off), which is what keeps the fused and the unfused passes bit-identical.
 #pragma once
-#ifndef C21X_ZW_DPP
-#define C21X_ZW_DPP 0
-#endif
-
 // ------------------------------------------------------------------ complex helpers
-// Round 5: what the SLP vectoriser made of this scalar arithmetic cost the transforms a quarter of their
-// vector instructions -- it packs pairs of additions / multiplications into v_pk_add_f32 / v_pk_mul_f32 and
-// builds the operand pairs with v_mov (four moves per complex product in the c2r pre-processing; 300 of
-// the fused pass Z's 2050 vector instructions were moves).  Two ways out, both bit-identical to the old
-// code (same multiplications, additions and roundings; -ffp-contract=off), both measured:
-//   C21X_PKASM = 1: the complex products and the multiplications by +-i hand-written as the packed
-//     instructions they are (op_sel and neg modifiers: a complex product is three instructions, no move):
-//     fused pass Z 2047 -> 1496 vector instructions, 0.309 -> 0.27 ms per 512^3 radius;
-//   the default build: NO packing at all (-fno-slp-vectorize, Makefile): 1976 vector instructions, all
-//     plain -- and as fast (0.26-0.27 ms), 3 % faster at 1024^3, because a packed fp32 instruction issues in
-//     ~8 cycles per wave on gfx950 where a plain one takes ~2.7 (tools/valu_rate_probe.hip).  No inline
-//     assembly in the default build.
-#ifndef C21X_PKASM
-#define C21X_PKASM 0  // measured equal to the scalar forms built with -fno-slp-vectorize (the default build)
-#endif
+// Scalar arithmetic, built with -fno-slp-vectorize (Makefile): the SLP vectoriser packed it into
+// v_pk_add_f32 / v_pk_mul_f32 plus operand moves and cost the transforms a quarter of their vector
+// instructions.  The same products hand-written as packed instructions in inline assembly (round 5) measured
+// equal to this scalar code built with -fno-slp-vectorize; removed (DESIGN_HISTORY.md, round 5).
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
-#if C21X_PKASM
-// a b = (a.x b.x - a.y b.y, a.y b.x + a.x b.y):  t = (a.x, a.y) b.x,  u = (a.y, a.x) b.y,  t -+ u
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    float2 t, u, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(b));
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,1]" : "=v"(u) : "v"(a), "v"(b));
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(t), "v"(u));
-    return r;
-}
-// a conj(b) = (a.x b.x + a.y b.y, a.y b.x - a.x b.y): bitwise cmul(a, (b.x, -b.y))
-__device__ __forceinline__ float2 cmulc(float2 a, float2 b) {
-    float2 t, u, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(b));
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,1]" : "=v"(u) : "v"(a), "v"(b));
-    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(t), "v"(u));
-    return r;
-}
-// a + i b = (a.x - b.y, a.y + b.x),  a - i b = (a.x + b.y, a.y - b.x)
-__device__ __forceinline__ float2 cadd_i(float2 a, float2 b) {
-    float2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float2 csub_i(float2 a, float2 b) {
-    float2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// (a.x + b.x, a.y - b.y) and (a.x - b.x, a.y + b.y): X + conj(B), X - conj(B)
-__device__ __forceinline__ float2 cadd_c(float2 a, float2 b) {
-    float2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float2 csub_c(float2 a, float2 b) {
-    float2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// h a, -h a for a real h
-__device__ __forceinline__ float2 cscale(float h, float2 a) {
-    float2 r, hh = make_float2(h, h);
-    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(hh), "v"(a));
-    return r;
-}
-__device__ __forceinline__ float2 cscale_neg(float h, float2 a) {
-    float2 r, hh = make_float2(h, h);
-    asm("v_pk_mul_f32 %0, %1, %2 neg_lo:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(hh), "v"(a));
-    return r;
-}
-#else
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
@@ -88,7 +22,6 @@ __device__ __forceinline__ float2 cadd_c(float2 a, float2 b) { return make_float
 __device__ __forceinline__ float2 csub_c(float2 a, float2 b) { return make_float2(a.x - b.x, a.y + b.y); }
 __device__ __forceinline__ float2 cscale(float h, float2 a) { return make_float2(h * a.x, h * a.y); }
 __device__ __forceinline__ float2 cscale_neg(float h, float2 a) { return make_float2(-h * a.x, -h * a.y); }
-#endif
 // multiply by +i (SIGN > 0) or -i (SIGN < 0)
 template <int SIGN>
 __device__ __forceinline__ float2 mul_i(float2 a) {
@@ -166,27 +99,7 @@ struct Dft<8, SIGN> {
 // ------------------------------------------------------------------ constant twiddles
 // a w for w = (sx W[IX], sy W[IY]) taken out of ONE register pair W = (cos, sin): the twiddles of the 16-
 // and 32-point DFTs are (c, s), (s, c), (-s, c), (-c, s) of three angles, so three pairs (and h) serve
-// them all through op_sel / neg modifiers.  NX / NY: negate the real / imaginary part of w.
-#if C21X_PKASM
-template <int IX, int NX, int IY, int NY>
-__device__ __forceinline__ float2 cmul_k(float2 a, float2 W) {
-    float2 t, u, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,%3] op_sel_hi:[1,%3] neg_lo:[0,%4] neg_hi:[0,%4]"
-        : "=v"(t) : "v"(a), "v"(W), "n"(IX), "n"(NX));
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,%3] op_sel_hi:[0,%3] neg_lo:[0,%4] neg_hi:[0,%4]"
-        : "=v"(u) : "v"(a), "v"(W), "n"(IY), "n"(NY));
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(t), "v"(u));
-    return r;
-}
-// (sa t.x + sb t.y, sc t.x + sd t.y) in one instruction (N* = 1: minus)
-template <int NA, int NB, int NC, int ND>
-__device__ __forceinline__ float2 cmix(float2 t) {
-    float2 r;
-    asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[0,1] neg_lo:[%2,%3] neg_hi:[%4,%5]"
-        : "=v"(r) : "v"(t), "n"(NA), "n"(NB), "n"(NC), "n"(ND));
-    return r;
-}
-#else
+// them all.  NX / NY: negate the real / imaginary part of w.
 template <int IX, int NX, int IY, int NY>
 __device__ __forceinline__ float2 cmul_k(float2 a, float2 W) {
     const float wx = IX ? W.y : W.x, wy = IY ? W.y : W.x;
@@ -196,7 +109,6 @@ template <int NA, int NB, int NC, int ND>
 __device__ __forceinline__ float2 cmix(float2 t) {
     return make_float2((NA ? -t.x : t.x) + (NB ? -t.y : t.y), (NC ? -t.x : t.x) + (ND ? -t.y : t.y));
 }
-#endif
 // a (h + SIGN i h) and a (-h + SIGN i h) from t = h a:
 //   (h, h): (t.x - t.y, t.x + t.y);  (h, -h): (t.x + t.y, t.y - t.x);
 //   (-h, h): (-t.x - t.y, t.x - t.y);  (-h, -h): (t.y - t.x, -t.x - t.y)
@@ -311,35 +223,19 @@ __device__ __forceinline__ void wave_c2r(float2 (&x)[A], float xh, float2 *L, co
     static_assert(A % P == 0, "rows per lane");
     constexpr int H = P * A;
     // The mirror partner X[H - k] of k = P a + b lives in lane (P - b) % P, register A - 1 - a
-    // (b = 0: the own lane, register (A - a) % A).  With 16 lanes per line that lane permutation is
-    // row_mirror followed by row_ror:1 -- two DPP moves per register instead of an LDS write and
-    // read of the whole line (LDS bytes count like global bytes inside a CU: 8 -> 4 KB of LDS
-    // traffic per 2 KB line).
-    constexpr bool DPP = C21X_ZW_DPP && P == 16;
-    float2 part[DPP ? A : 1];
-    if constexpr (DPP) {
+    // (b = 0: the own lane, register (A - a) % A): read back through the line's LDS region.  (Fetching it
+    // with two DPP lane moves per register instead took 230 VGPRs against 184 and measured equal in the
+    // loop, slower alone; removed.)
 #pragma unroll
-        for (int a = 0; a < A; a++) {
-            const float2 src = x[A - 1 - a];
-            int px = __builtin_amdgcn_update_dpp(0, __float_as_int(src.x), 0x140, 0xf, 0xf, false);
-            int py = __builtin_amdgcn_update_dpp(0, __float_as_int(src.y), 0x140, 0xf, 0xf, false);
-            px = __builtin_amdgcn_update_dpp(0, px, 0x121, 0xf, 0xf, false);
-            py = __builtin_amdgcn_update_dpp(0, py, 0x121, 0xf, 0xf, false);
-            const float2 own = x[(A - a) % A];
-            part[a] = (b == 0) ? own : make_float2(__int_as_float(px), __int_as_float(py));
-        }
-    } else {
-#pragma unroll
-        for (int a = 0; a < A; a++) L[a * (P + 1) + b] = x[a];
-        wave_fence();
-    }
+    for (int a = 0; a < A; a++) L[a * (P + 1) + b] = x[a];
+    wave_fence();
     // Z[k] = E + i O, E = X[k] + conj(X[H-k]), O = (X[k] - conj(X[H-k])) exp(+2 pi i k / 2H)
 #pragma unroll
     for (int a = 0; a < A; a++) {
         const int k = P * a + b;
         const int kp = (H - k) & (H - 1);  // k = 0 pairs with the Nyquist value below
         const float2 Xk = x[a];
-        float2 B = DPP ? part[DPP ? a : 0] : L[(kp / P) * (P + 1) + (kp % P)];
+        float2 B = L[(kp / P) * (P + 1) + (kp % P)];
         if (k == 0) B = make_float2(xh, 0.f);
         const float2 E = cadd_c(Xk, B);
         const float2 D = csub_c(Xk, B);

@@ -42,58 +42,28 @@
 #include "c21cm_abi.h"
 #include "c21cm_grid.h"
 
-// experiment switches (tools/build_variant.sh; the defaults are the shipped configuration)
+// numeric tunables (tools/build_variant.sh; the defaults are the shipped configuration)
 #ifndef C21X_XPAIR_THREADS
 #define C21X_XPAIR_THREADS 512
-#endif
-#ifndef C21X_FUSE512  // 512-point line passes: first and last radix-8 stage in registers (one LDS stage)
-#define C21X_FUSE512 1
-#endif
-#ifndef C21X_FUSE1024  // the same for 1024-point lines (radix-2 split + the first stage of both halves in registers)
-#define C21X_FUSE1024 1
-#endif
-#ifndef C21X_F512_MERGE   // 1: second stage of both tiles of a two-radius sweep between one pair of barriers
-#define C21X_F512_MERGE 1
-#endif
-#ifndef C21X_F512_HOIST2  // 1: second-stage twiddles kept in registers for the whole kernel (12-30 spilled
-#define C21X_F512_HOIST2 0  // VGPRs in the two-radius kernels, no faster)
-#endif
-#ifndef C21X_XPAIR_SKIP_FFT  // diagnostic (wrong results): 1 = the two-radius pass X skips its transforms (512-point
-#define C21X_XPAIR_SKIP_FFT 0  // lines: windows + one LDS round trip stay), 3 = registers straight back out (R + 2 W only)
-#endif
-#ifndef C21X_XPAIR_TWO_SETS
-#define C21X_XPAIR_TWO_SETS 0
-#endif
-#ifndef C21X_XPAIR_NOWIN
-#define C21X_XPAIR_NOWIN 0
-#endif
-#ifndef C21X_ZW_OCC       // min waves per SIMD requested for the fused pass Z (0: compiler's choice)
-#define C21X_ZW_OCC 0
 #endif
 #ifndef C21X_ZW_TSRC_OCC  // waves per SIMD asked of the three-line barrier kernel of the recombination loop
 #define C21X_ZW_TSRC_OCC 1
 #endif
-#ifndef C21X_EPI4_MASK16
-#define C21X_EPI4_MASK16 1
-#endif
-#ifndef C21X_ZW_TSRC_LEAN  // three-line barrier kernel: mask rows as 16-byte pieces, N_rec rows parked in LDS
-#define C21X_ZW_TSRC_LEAN 1
-#endif
-#ifndef C21X_ZW_TSRC_FENCE
-#define C21X_ZW_TSRC_FENCE 1
-#endif
 #ifndef C21X_ZW_BLOCK     // threads per workgroup of the fused pass Z on 512-point lines (64, 128, 256)
 #define C21X_ZW_BLOCK 256
 #endif
-#ifndef C21X_ZW_DPP       // 1: the mirror partner X[H-k] of the c2r pre-processing through DPP lane moves
-#define C21X_ZW_DPP 0     //    (16 lanes per line) instead of a round trip through LDS: 230 instead of 184
-#endif                    //    VGPRs, fused pass Z 0.304 ms in the loop either way (354 against 315 us alone)
-#ifndef C21X_ZW_MASK16    // 1: mask rows of the fused pass Z as 16-byte loads / stores through the line's LDS region (measured: 312 vs 306 us, off)
-#define C21X_ZW_MASK16 0
-#endif
-#ifndef C21X_ZW_LATE      // 1: second grid and mask rows requested after the first transform
-#define C21X_ZW_LATE 0
-#endif
+// Yes/no experiments of the tuning rounds, folded to what shipped (DESIGN_HISTORY.md has the accounts):
+//   512- and 1024-point line passes keep their first and last radix-8 stage in registers (one LDS stage);
+//   the second stage of both tiles of a two-radius sweep runs between one pair of barriers;
+//   second-stage twiddles hoisted into registers for the whole kernel: 12-30 spilled VGPRs, no faster; removed;
+//   two register sets in the two-radius pass X: 0.736 against 0.706-0.721 ms per launch; removed;
+//   the two-radius pass X without its windows or without its transforms (wrong results): timing diagnostics; removed;
+//   an occupancy hint for the fused pass Z (compiler's choice kept) and its second grid and mask rows
+//   requested after the first transform: never on in a shipped build; removed;
+//   mask rows of the fused pass Z as 16-byte pieces through LDS: 312 against 306 us, so only the three-line
+//   barrier kernel of the recombination loop (and epilogue 4) moves them that way, N_rec rows parked in LDS;
+//   the c2r mirror partner through DPP lane moves: 230 against 184 VGPRs, 0.304 ms in the loop either way
+//   (354 against 315 us alone); removed.
 
 namespace {
 constexpr int kBlock = 256;
@@ -707,7 +677,7 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
     constexpr int RSTEP = kBlock / CPAIR;  // rows covered by one sweep of the workgroup
     constexpr bool WEVAL = (FMODE >= 6 && FMODE <= 9);  // windows from node tables in LDS
     constexpr bool WDIRECT = (FMODE == 8 || FMODE == 9);  // ... and directly beyond the tables' range
-    constexpr bool WIN = (FMODE == 3 || (FMODE == 5 && !C21X_XPAIR_NOWIN) || WEVAL);
+    constexpr bool WIN = (FMODE == 3 || FMODE == 5 || WEVAL);
     constexpr bool PAIR = (FMODE == 5 || FMODE == 7 || FMODE == 9);
     constexpr int NR = PAIR ? 2 : 1;     // radii per sweep
     using LineItem = LineItemT<PAIR>;
@@ -743,8 +713,8 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
     const int r0 = threadIdx.x / CPAIR, c4 = threadIdx.x % CPAIR;
     // F512: the butterfly index of this thread is r0 in all three stages, so the twiddles of the
     // first (tw[r0 j]) and second stage (tw[(r0 & ~7) j]) are constants of the kernel
-    constexpr bool F512_ = C21X_FUSE512 && N == 512 && kBlock == 512 && (FMODE == 0 || WEVAL);
-    float2 twd1[F512_ ? 8 : 1], twd2[F512_ ? 8 : 1];
+    constexpr bool F512_ = N == 512 && kBlock == 512 && (FMODE == 0 || WEVAL);
+    float2 twd1[F512_ ? 8 : 1];
     if constexpr (F512_) {
         __syncthreads();  // tw is in LDS
         auto fill = [&](float2(&t)[8], int ps) {
@@ -761,7 +731,6 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
                 for (int j = 1; j < 8; j++) t[j].y = -t[j].y;
         };
         fill(twd1, r0);
-        if (C21X_F512_HOIST2) fill(twd2, r0 & ~7);
     }
     const int n_work0 = (a.g0.pair_outer ? (a.g0.n_outer / 2 + 1) : a.g0.n_outer) * a.g0.n_ctiles;
     const int n_work1 =
@@ -865,7 +834,7 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
     // Two radii per sweep: ONE set.  The next tile's loads go out before the two transforms of
     // this one, which is the look-ahead two sets buy the single-radius pass; the second set only
     // cost registers there (256 VGPRs + 84 bytes of scratch; 0.95 against 0.89 ms at 512^3).
-    constexpr bool TWO_SETS = (N < 1024) && (!PAIR || C21X_XPAIR_TWO_SETS);
+    constexpr bool TWO_SETS = (N < 1024) && !PAIR;
     float4 reg_a[2 * NP], reg_b[2 * NP];
     // FMODE 3: window values of this thread's row pairs x 2 columns; `pre` is in flight ahead
     // of the member that starts a new window, `cur` serves the members after it
@@ -881,13 +850,13 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
     // were on the critical path (the two-radius pass X without its transforms ran at 5.0 TB/s,
     // with them at 3.6).  Mirror rows are no longer in one thread: eight window values per column
     // instead of four.
-    constexpr bool F512 = C21X_FUSE512 && N == 512 && kBlock == 512 && (FMODE == 0 || WEVAL);
+    constexpr bool F512 = N == 512 && kBlock == 512 && (FMODE == 0 || WEVAL);
     // F1024: the same for 1024-point lines (16 rows r0 + 64 u per thread): the radix-2 split
     // a = x[k] + x[k + 512], b = (x[k] - x[k + 512]) w^k and the first stage of both 512-point halves
     // on the registers, the second stage of both halves in LDS, the third on the way out, where
     // A[m] = X[2 m] and B[m] = X[2 m + 1] go to adjacent rows.  Streamed window tables (FMODE 3) are
     // read per row (row and mirror row name the same table row; the partner thread's read hits L1).
-    constexpr bool F1024 = C21X_FUSE1024 && N == 1024 && kBlock == 512 && (FMODE == 0 || FMODE == 3 || WEVAL);
+    constexpr bool F1024 = N == 1024 && kBlock == 512 && (FMODE == 0 || FMODE == 3 || WEVAL);
     constexpr bool FUSED = F512 || F1024;
     constexpr int NW = FUSED ? 2 * NP : NP;  // window values (rows) per thread and column
     constexpr bool WPRE = (N >= 512) && !FUSED;
@@ -1311,28 +1280,12 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
                 c0[u] = make_float2(v.x, v.y);
                 c1[u] = make_float2(v.z, v.w);
             }
-            if constexpr (PAIR && C21X_XPAIR_SKIP_FFT == 3) {
-                // diagnostic (wrong results): the tile leaves as it came -- one read, two writes in this kernel's
-                // access pattern, no LDS, no arithmetic: the data-movement ceiling of the two-radius pass X
-                float2 *stp = member_grid(it, m) ? (rr ? it.dst1b : it.dst1) : (rr ? it.dst0b : it.dst0);
-                stp += member_base(it, m);
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int row = r0 + RSTEP * u;
-                    const unsigned roff = row_off(it, row < N / 2 ? row : row - N / 2);
-                    float2 *pp = stp + (row < N / 2 ? 0 : st_half);
-                    *reinterpret_cast<float4 *>(pp + (roff + 2u * c4)) = reg[u];
-                }
-                continue;
-            }
-            if (!(PAIR && C21X_XPAIR_SKIP_FFT)) {
-                Dft<8, SIGN>::run(c0);
-                Dft<8, SIGN>::run(c1);
-            }
+            Dft<8, SIGN>::run(c0);
+            Dft<8, SIGN>::run(c1);
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 float2 o0 = c0[j], o1 = c1[j];
-                if (j > 0 && !(PAIR && C21X_XPAIR_SKIP_FFT)) {
+                if (j > 0) {
                     o0 = cmul(o0, twd1[F512_ ? j : 0]);
                     o1 = cmul(o1, twd1[F512_ ? j : 0]);
                 }
@@ -1431,11 +1384,12 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
             }
             __syncthreads();
         }
-        if constexpr (F512 && !(PAIR && C21X_XPAIR_SKIP_FFT)) {
+        if constexpr (F512) {
             // second Stockham stage (s = 8) of all tiles of the sweep between ONE pair of barriers:
             // butterfly r0 of columns 2 c4, 2 c4 + 1: inputs rows r0 + 64 k, outputs rows
             // (r0 & 7) + 64 (r0 >> 3) + 8 j times tw[(r0 & ~7) j]
-            constexpr int GRP = C21X_F512_MERGE ? NR : 1;  // tiles per barrier pair
+            // (the variant with one tile per barrier pair is gone: the loop below makes one trip with all NR)
+            constexpr int GRP = NR;  // tiles per barrier pair
             const int obase = (r0 & 7) + 64 * (r0 >> 3);
 #pragma unroll
             for (int g = 0; g < NR; g += GRP) {
@@ -1451,7 +1405,7 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
                     }
                 __syncthreads();
                 float2 w2[8];
-                if (!C21X_F512_HOIST2) {
+                {
                     const int ps = r0 & ~7;
                     w2[1] = tw[ps];
                     w2[2] = tw[2 * ps];
@@ -1472,9 +1426,8 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
                     for (int j = 0; j < 8; j++) {
                         float2 o0 = s0[rr][j], o1 = s1[rr][j];
                         if (j > 0) {
-                            const float2 w = C21X_F512_HOIST2 ? twd2[F512_ ? j : 0] : w2[j];
-                            o0 = cmul(o0, w);
-                            o1 = cmul(o1, w);
+                            o0 = cmul(o0, w2[j]);
+                            o1 = cmul(o1, w2[j]);
                         }
                         *reinterpret_cast<float4 *>(tile + (g + rr) * N * TZ + (obase + 8 * j) * TZ + 2 * c4) =
                             make_float4(o0.x, o0.y, o1.x, o1.y);
@@ -1523,7 +1476,6 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
             continue;
         }
         if constexpr (F512) {
-            if constexpr (PAIR && C21X_XPAIR_SKIP_FFT == 3) continue;
             // third stage (s = 64, no twiddles: inputs rows r0 + 64 k, outputs rows r0 + 64 j) on the
             // values read back for the store
             float2 c0[8], c1[8];
@@ -1533,10 +1485,8 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
                 c0[k] = make_float2(t.x, t.y);
                 c1[k] = make_float2(t.z, t.w);
             }
-            if (!(PAIR && C21X_XPAIR_SKIP_FFT)) {
-                Dft<8, SIGN>::run(c0);
-                Dft<8, SIGN>::run(c1);
-            }
+            Dft<8, SIGN>::run(c0);
+            Dft<8, SIGN>::run(c1);
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 float4 v = make_float4(c0[j].x, c0[j].y, c1[j].x, c1[j].y);
@@ -1553,8 +1503,7 @@ line_pass_kernel(LinePassArgs a, const float2 *__restrict__ tw_global) {
             }
             continue;
         }
-        if (!(PAIR && C21X_XPAIR_SKIP_FFT)) line_fft<N, TZ, SIGN, kBlock>(tile_r, tw, tw_half);
-        if (PAIR && C21X_XPAIR_SKIP_FFT == 2 && rr == 1) continue;
+        line_fft<N, TZ, SIGN, kBlock>(tile_r, tw, tw_half);
         // ---- store
 #pragma unroll
         for (int u = 0; u < 2 * NP; u++) {
@@ -2417,11 +2366,7 @@ constexpr int zw_lines(int P) { return kBlock / P; }
 // CB: the barrier's outcome goes to a.cross_bits (one bit per cell, write only) instead of the mask.
 template <int A, bool TS, int P = 16, bool RC = false, bool CB = false>
 __global__ void
-#if C21X_ZW_OCC
-__launch_bounds__(kBlock, (A == 16 && !TS) ? C21X_ZW_OCC : 1)
-#else
 __launch_bounds__((A == 16 && P == 16) ? C21X_ZW_BLOCK : kBlock, (TS && RC && A == 16 && P == 16) ? C21X_ZW_TSRC_OCC : 1)
-#endif
 zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
                  const float2 *__restrict__ twN_global) {
     constexpr int ZBLK = (A == 16 && P == 16) ? C21X_ZW_BLOCK : kBlock;  // threads of this workgroup
@@ -2444,7 +2389,7 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
     const long line = (long)blk * ZWL + lw;
     float2 *L = lines + lw * LINE_LDS;
     const float2 *dm = a.d_main + line * H, *sm = a.s_main + line * H;
-    constexpr bool EARLY = (A == 16) && !C21X_ZW_LATE;
+    constexpr bool EARLY = (A == 16);
     static_assert(!CB || (A == 16 && P == 16 && !TS && !RC), "crossing bits: the two-grid kernel on 512-point lines");
     float2 xd[A], xs[A];
 #pragma unroll
@@ -2460,8 +2405,9 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
     // MASK16: the line's mask row as 2 A contiguous bytes per lane (16-byte loads in flight with the
     // spectra); after the transforms the row goes through the line's LDS region, where the lanes pick
     // their (cell 2j, 2j + 1) pairs and leave the changes; changed 16-byte pieces go back to the grid.
-    // Sixteen 2-byte loads and up to sixteen 2-byte stores per lane otherwise.
-    constexpr bool MASK16 = !CB && EARLY && (C21X_ZW_MASK16 || (TS && RC && C21X_ZW_TSRC_LEAN));
+    // Sixteen 2-byte loads and up to sixteen 2-byte stores per lane otherwise.  Only the three-line barrier
+    // kernel of the recombination loop takes this form: for the others it measured 312 against 306 us.
+    constexpr bool MASK16 = !CB && EARLY && TS && RC;
     constexpr int MV = MASK16 ? A / 8 : 1;
     uint4 mreg[MV];
     uchar2 old[(EARLY && !MASK16) ? A : 1];
@@ -2480,7 +2426,7 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
     // Three lines + N_rec (x_e grid of a spin-temperature run + CELL_RECOMB): 318 registers and one wave
     // per SIMD that way.  STASH: the line's N_rec row is requested as 16-byte pieces with the spectra,
     // parked in LDS after the first transform (2 KB per line) and read from there in the barrier loop.
-    constexpr bool STASH = TS && RC && A == 16 && P == 16 && C21X_ZW_TSRC_LEAN;
+    constexpr bool STASH = TS && RC && A == 16 && P == 16;
     constexpr int NRH = (RC && A == 16 && !STASH) ? A / 2 : 1;
     float2 nr_lo[NRH], nr_hi[NRH];
     __shared__ __attribute__((aligned(16))) float nstash[STASH ? ZWL * NZ : 4];
@@ -2633,11 +2579,9 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
             if (n0 && a.rc != 2) grow[0] = fmaxf(xd[q].x, dmin);
             if (n1 && a.rc != 2) grow[1] = fmaxf(xd[q].y, dmin);
         }
-#if C21X_ZW_TSRC_FENCE
         // three lines + N_rec: keep the iterations apart, or the scheduler's hoisting across the
         // unrolled loop costs the second wave per SIMD (318 registers)
         if constexpr (TS && RC) __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     if constexpr (MASK16) {
         wave_fence();
@@ -2699,7 +2643,7 @@ zw_c2r_kernel(ZPassArgs a, const float2 *__restrict__ twH_global,
     // the transform); the lanes' (cell 2j, 2j + 1) pairs are picked out of the line's LDS region afterwards
     // (EPI 4 reads the rows the same way -- sixteen 2-byte loads per lane issued after the transform
     //  made the Gamma_12 pass slower than a pass Z that stores its whole grid: 0.30 against 0.25 ms)
-    constexpr bool MROW = (EPI == 7 || EPI == 8 || EPI == 9 || (EPI == 4 && C21X_EPI4_MASK16));
+    constexpr bool MROW = (EPI == 4 || EPI == 7 || EPI == 8 || EPI == 9);
     constexpr int MV = MROW ? A / 8 : 1;
     uint4 mreg[MV];
     if constexpr (MROW) {
@@ -2780,8 +2724,7 @@ zw_c2r_kernel(ZPassArgs a, const float2 *__restrict__ twH_global,
             if (h0 || h1) reinterpret_cast<uchar2 *>(a.mask_rw + lline * NZ)[j] = m;
         } else if (EPI == 4) {
             // (requesting the crossings' delta_R before the transform was tried: 0.289 against 0.252 ms)
-            const uchar2 m = MROW ? reinterpret_cast<const uchar2 *>(L)[j]
-                                  : reinterpret_cast<const uchar2 *>(a.mask + lline * NZ)[j];
+            const uchar2 m = reinterpret_cast<const uchar2 *>(L)[j];
             float *grow = a.out + lline * NZ + 2 * j;
             if (m.x == (unsigned char)a.r_index)
                 grow[0] = (float)(a.const_factor / (1. + (double)grow[0]) * (double)fmaxf(v.x, 0.f));
@@ -3592,14 +3535,6 @@ extern "C" int c21hip_pair_sweep_supported(int nx) { return nx <= 512; }
 // 1 unless C21CM_YNYQ_SPLIT is 0 in this process
 extern "C" int c21hip_ynyq_split_enabled(void) { return ynyq_split_on() ? 1 : 0; }
 
-// ---- the timing hook of this file for launches issued elsewhere (bench.py: c21hip_ktime_*)
-extern "C" const void *c21hip_twiddles_dev(int n) { return twiddles(n); }
-extern "C" void *c21hip_ktime_begin(int kind, void *stream) {
-    return g_ktime_on ? new KTimeScope(kind, (hipStream_t)stream) : nullptr;
-}
-extern "C" void c21hip_ktime_end(void *scope) { delete static_cast<KTimeScope *>(scope); }
-
-
 // Placement probe (ionize_driver.c: place_work_partner): pass Y of two work spectra in one launch, in place on
 // whatever the buffers hold, `reps` launches timed with events on the stream -> *ms per launch.  Which physical
 // region of the HBM two buffers written by one launch sit in decides 10-20 % of that launch's time
@@ -3632,95 +3567,6 @@ extern "C" int c21hip_probe_pass_y2(float *work_a, float *work_b, int nx, int ny
         return C21CM_IO_ERROR;
     }
     int st = dispatch_line_pass<+1>(ny, a, 0, stream);  // warm-up (first touch of the pages)
-    (void)hipEventRecord(e0, stream);
-    for (int r = 0; r < reps && !st; r++) st = dispatch_line_pass<+1>(ny, a, 0, stream);
-    (void)hipEventRecord(e1, stream);
-    float t = 0.f;
-    if (!st && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)) {
-        (void)hipGetLastError();
-        st = C21CM_IO_ERROR;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms = t / (float)reps;
-    return st;
-}
-
-// Diagnostic: pass Y of ONE spectrum from `src` to `dst` (the same pointer: in place, what the product runs),
-// timed like c21hip_probe_pass_y2 (tools/scratch/placement_probe5.py: is an out-of-place pass Y into another region
-// of the HBM faster than the in-place one?)
-extern "C" int c21hip_probe_pass_y1(const float *src, float *dst, int nx, int ny, int nz, int reps, float *ms,
-                                    void *stream_) {
-    if (!c21hip_native_fft_supported(nx, ny, nz) || !src || !dst || reps < 1 || !ms) return C21CM_VALUE_ERROR;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int H = nz / 2;
-    const long nlines = (long)nx * ny;
-    LinePassArgs a{};
-    a.fp.type = -1;
-    a.n_y = ny;
-    a.n_z = nz;
-    a.out_scale = 1.0f;
-    a.n_geo = 2;
-    a.n_grids = 1;
-    a.g0 = geo_y_main(nx, ny, H, line_tile_cols(ny), split_xb_log2(nx));
-    a.g1 = geo_y_nyq(nx, ny, line_tile_cols(ny));
-    a.g1_strided = 1;
-    const float2 *s2 = reinterpret_cast<const float2 *>(src);
-    float2 *d2 = reinterpret_cast<float2 *>(dst);
-    geo_ptrs(a.g0, 0, s2, d2);
-    geo_ptrs(a.g1, 0, s2 + nlines * H, d2 + nlines * H);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        (void)hipGetLastError();
-        if (e0) (void)hipEventDestroy(e0);
-        return C21CM_IO_ERROR;
-    }
-    int st = dispatch_line_pass<+1>(ny, a, 0, stream);
-    (void)hipEventRecord(e0, stream);
-    for (int r = 0; r < reps && !st; r++) st = dispatch_line_pass<+1>(ny, a, 0, stream);
-    (void)hipEventRecord(e1, stream);
-    float t = 0.f;
-    if (!st && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)) {
-        (void)hipGetLastError();
-        st = C21CM_IO_ERROR;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms = t / (float)reps;
-    return st;
-}
-
-// ... and of TWO spectra, each from its source to its destination (diagnostic)
-extern "C" int c21hip_probe_pass_y2o(const float *src_a, float *dst_a, const float *src_b, float *dst_b, int nx, int ny,
-                                     int nz, int reps, float *ms, void *stream_) {
-    if (!c21hip_native_fft_supported(nx, ny, nz) || !src_a || !dst_a || !src_b || !dst_b || reps < 1 || !ms)
-        return C21CM_VALUE_ERROR;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int H = nz / 2;
-    const long nlines = (long)nx * ny;
-    LinePassArgs a{};
-    a.fp.type = -1;
-    a.n_y = ny;
-    a.n_z = nz;
-    a.out_scale = 1.0f;
-    a.n_geo = 2;
-    a.n_grids = 2;
-    a.g0 = geo_y_main(nx, ny, H, line_tile_cols(ny), split_xb_log2(nx));
-    a.g1 = geo_y_nyq(nx, ny, line_tile_cols(ny));
-    a.g1_strided = 1;
-    const float2 *sp[2] = {reinterpret_cast<const float2 *>(src_a), reinterpret_cast<const float2 *>(src_b)};
-    float2 *dp[2] = {reinterpret_cast<float2 *>(dst_a), reinterpret_cast<float2 *>(dst_b)};
-    for (int g = 0; g < 2; g++) {
-        geo_ptrs(a.g0, g, sp[g], dp[g]);
-        geo_ptrs(a.g1, g, sp[g] + nlines * H, dp[g] + nlines * H);
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        (void)hipGetLastError();
-        if (e0) (void)hipEventDestroy(e0);
-        return C21CM_IO_ERROR;
-    }
-    int st = dispatch_line_pass<+1>(ny, a, 0, stream);
     (void)hipEventRecord(e0, stream);
     for (int r = 0; r < reps && !st; r++) st = dispatch_line_pass<+1>(ny, a, 0, stream);
     (void)hipEventRecord(e1, stream);
@@ -5106,7 +4952,7 @@ extern "C" int c21hip_split_z_ionise_recomb_xe_nrec(const float *delta_work, con
                                                     int ny, int nz, int r_index, double rhocrit_omb,
                                                     double ion_eff, int mass_dep_zeta, double f_limit,
                                                     void *stream) {
-    if (nz != 512 || !C21X_ZW_TSRC_LEAN) {
+    if (nz != 512) {
         c21hip_set_error("fused pass Z with an x_e grid and a filtered N_rec: 512-point z-lines only");
         return C21CM_VALUE_ERROR;
     }
@@ -5137,7 +4983,7 @@ extern "C" int c21hip_split_z_ionise_recomb_xe_nrec(const float *delta_work, con
 }
 extern "C" int c21hip_z_ionise_recomb_xe_nrec_supported(int nx, int ny, int nz) {
     const long nlines = (long)nx * ny;
-    return C21X_ZW_TSRC_LEAN && nz == 512 && zw_lines_of(nz, nlines) != 0 && !zw3_selected(nz, nlines);
+    return nz == 512 && zw_lines_of(nz, nlines) != 0 && !zw3_selected(nz, nlines);
 }
 extern "C" int c21hip_z_ionise_recomb_supported(int nx, int ny, int nz) {
     const long nlines = (long)nx * ny;

@@ -24,8 +24,8 @@ constexpr int kMaxSlots = WS_COUNT;
 struct Slot {
     void *ptr = nullptr;
     size_t bytes = 0;
-    // scattered placement (C21CM_WS_ALLOC=scatter): a reserved address range backed by 2 MB chunks mapped in a
-    // shuffled order
+    // a buffer adopted from the placement walk (c21hip_ws_adopt_vmm): a reserved address range and the physical
+    // chunk mapped into it
     std::vector<hipMemGenericAllocationHandle_t> chunks;
     size_t va_bytes = 0;
 };
@@ -47,73 +47,6 @@ void slot_free(Slot &s) {
     s.bytes = 0;
 }
 
-// Large workspace buffers whose 2 MB pages are NOT in physical order.  On a GPU whose memory is unfragmented
-// hipMalloc hands out physically contiguous ranges, and the line passes that walk rows at a power-of-two pitch
-// (pass Y: 128-byte pieces every 2 / 4 KB) then run 8-20 % slower than on a box whose memory has been churned
-// (profiles/r05_placement_study.txt): the regular address-to-channel map serves such a walk from a subset of the
-// HBM channels at a time.  Chunks of the allocation granularity are created in order and mapped at a
-// pseudo-randomly permuted position of a reserved address range.
-void *scatter_alloc(Slot &s, size_t bytes) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    hipMemAllocationProp prop{};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = dev;
-    size_t gran = 0;
-    if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || !gran) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    size_t want = (size_t)2 << 20;  // C21CM_WS_SCATTER_MB: chunk size of the experiment (default 2 MB)
-    if (const char *e = getenv("C21CM_WS_SCATTER_MB")) want = (size_t)atol(e) << 20;
-    const size_t chunk = (want + gran - 1) / gran * gran;
-    const size_t n = (bytes + chunk - 1) / chunk, total = n * chunk;
-    void *va = nullptr;
-    if (hipMemAddressReserve(&va, total, chunk, nullptr, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    std::vector<hipMemGenericAllocationHandle_t> hs(n);
-    size_t made = 0;
-    bool ok = true;
-    for (; made < n; made++)
-        if (hipMemCreate(&hs[made], chunk, &prop, 0) != hipSuccess) {
-            ok = false;
-            break;
-        }
-    // position of chunk i: a fixed odd multiplier modulo a power of two >= n, cycled into range (a permutation)
-    size_t m = 1;
-    while (m < n) m <<= 1;
-    size_t mapped = 0;
-    if (ok) {
-        size_t pos = 0;
-        for (size_t i = 0; i < m && ok; i++) {
-            const size_t j = (i * 0x9E3779B1ull + 12345u) & (m - 1);  // odd multiplier: a bijection on [0, m)
-            if (j >= n) continue;
-            if (hipMemMap((char *)va + j * chunk, chunk, 0, hs[pos++], 0) != hipSuccess) ok = false;
-            else mapped++;
-        }
-        ok = ok && mapped == n;
-    }
-    if (ok) {
-        hipMemAccessDesc acc{};
-        acc.location.type = hipMemLocationTypeDevice;
-        acc.location.id = dev;
-        acc.flags = hipMemAccessFlagsProtReadWrite;
-        ok = hipMemSetAccess(va, total, &acc, 1) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        if (mapped) (void)hipMemUnmap(va, total);
-        for (size_t i = 0; i < made; i++) (void)hipMemRelease(hs[i]);
-        (void)hipMemAddressFree(va, total);
-        return nullptr;
-    }
-    s.chunks.swap(hs);
-    s.va_bytes = total;
-    return va;
-}
 thread_local char g_error[512] = "";
 }  // namespace
 
@@ -184,26 +117,9 @@ extern "C" void *c21hip_ws(int slot, size_t bytes) {
     if (s.bytes >= bytes && s.ptr) return s.ptr;
     slot_free(s);
     void *p = nullptr;
-    // C21CM_WS_ALLOC=contig: large buffers physically contiguous (hipDeviceMallocContiguous) -- placement study
-    // of the two speeds of the line passes (DESIGN Appendix B.0); anything else: plain hipMalloc
-    static int contig = -1;
-    if (contig < 0) {
-        const char *e = getenv("C21CM_WS_ALLOC");
-        contig = (e && e[0] == 'c') ? 1 : ((e && e[0] == 's') ? 2 : 0);
-    }
-    hipError_t e = hipErrorUnknown;
-    if (contig == 2 && bytes >= ((size_t)64 << 20)) {
-        p = scatter_alloc(s, bytes);
-        if (p) e = hipSuccess;
-    }
-    if (contig == 1 && bytes >= ((size_t)64 << 20)) {
-        e = hipExtMallocWithFlags(&p, bytes, hipDeviceMallocContiguous);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-        }
-    }
-    if (e != hipSuccess) e = hipMalloc(&p, bytes ? bytes : 16);
+    // (physically contiguous buffers and 2 MB chunks mapped in a shuffled order were the placement study of the
+    //  two speeds of the line passes, profiles/r05_placement_study.txt; removed: csrc/host/placement.c came of it)
+    const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         c21hip_set_error("hipMalloc of %zu bytes for workspace slot %d failed: %s", bytes, slot,
@@ -504,16 +420,9 @@ extern "C" int c21hip_stream_wait_event(void *stream, void *ev) {
 extern "C" void *c21hip_aux_stream(void) {
     static hipStream_t aux = nullptr;
     if (!aux) {
-        // C21CM_AUX_PRIO=low: lowest stream priority, so that what runs here (window tables of
-        // the coming radii) only fills in behind the caller's kernels.  Measured no difference at
-        // 512^3, so the default stays a plain non-blocking stream.
-        int least = 0, greatest = 0;
-        const char *e = getenv("C21CM_AUX_PRIO");
-        const bool low = e && e[0] == 'l' &&
-                         hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-        const hipError_t st = low ? hipStreamCreateWithPriority(&aux, hipStreamNonBlocking, least)
-                                  : hipStreamCreateWithFlags(&aux, hipStreamNonBlocking);
-        if (st != hipSuccess) aux = nullptr;
+        // (the lowest stream priority, so that what runs here only fills in behind the caller's kernels,
+        //  measured no difference at 512^3; removed: a plain non-blocking stream)
+        if (hipStreamCreateWithFlags(&aux, hipStreamNonBlocking) != hipSuccess) aux = nullptr;
     }
     return aux;
 }

@@ -692,12 +692,7 @@ ts_accumulate2_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
 // ---- table modes, third version: everything a shell needs sits in LDS -- the 400-knot tables of
 // all shells (64 KB for 40), the folded frequency-integral weights as (w[m], w[m+1]) pairs (one
 // 16-byte read per integral) -- so a workgroup is 1024 threads, one per CU (16 waves: the loop is
-// issue-bound, not occupancy-bound, at ~40 slots per cell and shell); two cells per thread with the
-// lookup written on 2-vectors so that the compiler emits packed fp32 instructions for both cells.
-#ifndef C21X_TS_PACKED
-#define C21X_TS_PACKED 0
-#endif
-typedef float v2f __attribute__((ext_vector_type(2)));
+// issue-bound, not occupancy-bound, at ~40 slots per cell and shell); two cells per thread.
 constexpr int kAccBlock = 1024;
 constexpr int kWP = 3 * C21CM_X_INT_NXHII;  // (w[m], w[m+1]) pairs per shell: heat, ion, lya
 
@@ -772,30 +767,9 @@ ts_accumulate3_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
             if (R > 0) g = ga2[(size_t)(R - 1) * nitems + it];  // the next (smaller) shell
             const ShellLookup L = LK[R];
             const float *y = TAB + R * TS;
-#if C21X_TS_PACKED  // (the round-3 form: 2-vectors so that the compiler emits packed fp32 instructions)
-            const v2f d = {c.x, c.y};
-            const v2f x = d * L.growth;
-            int i0, i1;
-            const v2f ip = {shell_bin(c.x, L, &i0), shell_bin(c.y, L, &i1)};
-            const v2f y0 = {y[i0], y[i1]}, y1 = {y[i0 + 1], y[i1 + 1]};
-            const v2f r = ip * (y1 - y0);
-            v2f tv;
-            if (MODE == 1) {
-                const float L_hi = 1.44269502162933349609375f, L_lo = 1.925963033500011e-8f;
-                const v2f w = y0 * L_hi;
-                const v2f nn = {rintf(w.x), rintf(w.y)};
-                const v2f f = __builtin_elementwise_fma(y0, (v2f){L_hi, L_hi}, -nn) +
-                              __builtin_elementwise_fma(y0, (v2f){L_lo, L_lo}, r * L_hi);
-                tv.x = ldexpf(__builtin_amdgcn_exp2f(f.x), (int)fmaxf(nn.x, -200.f));
-                tv.y = ldexpf(__builtin_amdgcn_exp2f(f.y), (int)fmaxf(nn.y, -200.f));
-            } else {
-                tv = y0 + r;
-            }
-            const v2f sf = (x + 1.0f) * tv;  // del_fcoll_Rct is a float upstream
-#else
-            // the same arithmetic on scalars (round 5: a packed fp32 instruction issues in 8 cycles per wave on
-            // gfx950, a plain one in 2.7 -- tools/valu_rate_probe.hip; the operations and their order are those of
-            // the packed form, so the sums are the same bits)
+            // the lookup of both cells on scalars, each operation rounded on its own.  (Round 3 wrote it on
+            // 2-vectors so that the compiler emitted packed fp32 instructions: a packed instruction issues in 8
+            // cycles per wave on gfx950, a plain one in 2.7 -- tools/valu_rate_probe.hip; same bits; removed.)
             float2 sf;
             {
                 const float cc[2] = {c.x, c.y};
@@ -821,7 +795,6 @@ ts_accumulate3_kernel(c21hip_ts_args a, const float *__restrict__ prev_xe,
                 }
                 sf = make_float2(sv[0], sv[1]);
             }
-#endif
             const double xs[2] = {(double)sf.x, (double)sf.y};
             const double2 *wr = WP + R * kWP;
             const double *sr = SS + 3 * R;

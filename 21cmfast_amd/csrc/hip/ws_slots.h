@@ -315,7 +315,6 @@ enum c21_ws_slot {
      * word once shared an id with WS_EUL_XEPEND, whose reallocation freed it.) */
     WS_SHARD_STATUS,
     WS_SHARD_SLABBITS,
-    WS_ARENA,      /* experiment: the spectra of the two-grid loop out of one allocation (C21CM_ARENA) */
     WS_NREC_WORK2, /* fused recombination loop with x_e AND a filtered N_rec: N_rec of the second radius */
     WS_TSS_ROWMAX, /* shard_rccl.c */
     WS_EUL_WORK3,  /* Eulerian table loop, two radii per pass-X sweep: the second set of k-space buffers */

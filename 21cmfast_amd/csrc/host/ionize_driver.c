@@ -331,31 +331,18 @@ static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedFiel
     const size_t gbytes = c->npad * sizeof(float), dbytes = c->ntot * sizeof(float);
 
     c->native = c21hip_fft_is_native(c->nx, c->ny, c->nz);
-    /* experiment (round 5): the four spectra of the two-grid loop out of ONE allocation, `skew` bytes
-     * between consecutive buffers (C21CM_ARENA=skew; default: separate workspace slots) */
-    char *arena = NULL;
-    size_t astep = 0;
-    {
-        const char *e = getenv("C21CM_ARENA");
-        if (e && c->lagrangian) {
-            const size_t skew = (size_t)atol(e);
-            astep = ((gbytes + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1)) + skew;
-            arena = (char *)c21hip_ws(WS_ARENA, 4 * astep);
-            if (!arena) return C21CM_MEMORY_ALLOC_ERROR;
-        }
-    }
-    c->delta_unf = arena ? (float *)arena : (float *)c21hip_ws(WS_DELTA_UNF, gbytes);
+    /* (the four spectra of the two-grid loop carved out of ONE allocation ran at the slow speed of the 1024^3
+     * line passes for every skew tried -- round 5, DESIGN "Two speeds of the 1024^3 line passes"; removed) */
+    c->delta_unf = (float *)c21hip_ws(WS_DELTA_UNF, gbytes);
     c->delta_fil = (float *)c21hip_ws(WS_DELTA_FIL, gbytes);
     if (!c->delta_unf || !c->delta_fil) return C21CM_MEMORY_ALLOC_ERROR;
-    if (c->native && !(c->delta_work = arena ? (float *)(arena + 2 * astep) : (float *)c21hip_ws(WS_DELTA_WORK, gbytes)))
-        return C21CM_MEMORY_ALLOC_ERROR;
+    if (c->native && !(c->delta_work = (float *)c21hip_ws(WS_DELTA_WORK, gbytes))) return C21CM_MEMORY_ALLOC_ERROR;
     if (c->lagrangian) {
-        c->stars_unf = arena ? (float *)(arena + astep) : (float *)c21hip_ws(WS_STARS_UNF, gbytes);
+        c->stars_unf = (float *)c21hip_ws(WS_STARS_UNF, gbytes);
         c->stars_fil = (float *)c21hip_ws(WS_STARS_FIL, gbytes);
         if (!c->stars_unf || !c->stars_fil) return C21CM_MEMORY_ALLOC_ERROR;
-        if (c->native && !(c->stars_work = arena ? (float *)(arena + 3 * astep)
-                                                 : c21_place_work_partner(WS_DELTA_WORK, WS_STARS_WORK, gbytes, c->nx, c->ny,
-                                                                      c->nz, stream)))
+        if (c->native && !(c->stars_work = c21_place_work_partner(WS_DELTA_WORK, WS_STARS_WORK, gbytes, c->nx, c->ny,
+                                                                  c->nz, stream)))
             return C21CM_MEMORY_ALLOC_ERROR;
     }
     if (s->use_ts_fluct) {
@@ -720,13 +707,6 @@ static int tab_build_async(ion_ctx *c, int R_ct, int buf) {
     int status = 0;
     const c21cm_ionize_spec *s = c->s;
     TRY(c21hip_stream_wait_event(g_tab.aux, g_tab.ev_used[buf]));
-#ifdef C21CM_DIAG_BUILD /* (make EXTRA=-DC21CM_DIAG_BUILD: timing diagnostics that change results) */
-    /* C21CM_DIAG_SKIP_TABLES=1 (WRONG results): no table kernels after the first step -- what the R
-     * loop would cost if the windows came for free */
-    static int skip = -1;
-    if (skip < 0) skip = getenv("C21CM_DIAG_SKIP_TABLES") != NULL;
-    if (!(skip && c->tab_seq > 0))
-#endif
     TRY(c21hip_window_tables(buf, s->hii_filter, 0.f, s->stars_filter, (float)s->mfp_meandens,
                              c->nx, c->ny, c->nz, s->box_len, s->box_len_z, (float)s->R[R_ct],
                              g_tab.aux));
@@ -884,12 +864,8 @@ static int fused_step(ion_ctx *c, int R_a, int R_b, unsigned char *first_cross, 
     if (R_b >= 1) {
         /* X (both radii) -> Y_a -> Z_a -> Y_b -> Z_b: each fused pass Z directly follows the pass
          * Y that wrote its input and walks the lines backwards, so its first quarter comes out
-         * of the Infinity Cache (C21CM_PAIR_ORDER=yy: both passes Y first) */
-        static int yy = -1;
-        if (yy < 0) {
-            const char *e = getenv("C21CM_PAIR_ORDER");
-            yy = (e && e[0] == 'y') ? 1 : 0;
-        }
+         * of the Infinity Cache (this order and the backward walk: 0.5 ms per call against both passes Y
+         * first and a forward walk, DESIGN_HISTORY; the other order is removed) */
         /* third spectrum handed to z_ionise_radius: whalo_sfr on the fused recombination loop (the
          * x_e spectrum of such a run travels in c->cur_xe), else x_e */
         const float *xw[2] = {c->fused_rc ? c->sfr_work : (s->use_ts_fluct ? c->xe_work : NULL),
@@ -905,28 +881,23 @@ static int fused_step(ion_ctx *c, int R_a, int R_b, unsigned char *first_cross, 
             /* x_e (N_rec) shares the density grid's window (IonisationBox.c:1551-1553, :613), whalo_sfr
              * the emissivity's (IonisationBox.c:583-663): together they are a second two-grid sweep
              * with the same window pair (one pass X, one pass Y per radius instead of two each) */
-            static int merge34 = -1;
-            if (merge34 < 0) {
-                const char *e = getenv("C21CM_RECOMB_MERGE34");
-                merge34 = (e && e[0] == '0') ? 0 : 1;
-            }
-            if (c->x3_on && c->fused_rc && c->wev && merge34) {
+            if (c->x3_on && c->fused_rc && c->wev) {
                 TRY(c21hip_split_filter_xy2_pair(
                     c->x3_unf, c->x3_work, c->x3_work2, s->hii_filter, 0.f, c->sfr_unf, c->sfr_work,
                     c->sfr_work2, s->stars_filter, (float)s->mfp_meandens, c->nx, c->ny, c->nz,
                     s->box_len, s->box_len_z, (float)s->R[R_a], (float)s->R[R_b], buf_a, buf_b,
                     bits & ~1, c->stream));
             } else {
-            if (c->x3_on)
-                TRY(c21hip_split_filter_xy_shared_pair(
-                    c->x3_unf, c->x3_work, c->x3_work2, s->hii_filter, c->nx, c->ny, c->nz,
-                    s->box_len, s->box_len_z, (float)s->R[R_a], (float)s->R[R_b], buf_a, buf_b,
-                    bits & ~1, c->stream));
-            if (c->fused_rc)
-                TRY(c21hip_split_filter_xy_single_pair(
-                    c->sfr_unf, c->sfr_work, c->sfr_work2, s->stars_filter, (float)s->mfp_meandens,
-                    c->nx, c->ny, c->nz, s->box_len, s->box_len_z, (float)s->R[R_a],
-                    (float)s->R[R_b], bits & ~1, c->stream));
+                if (c->x3_on)
+                    TRY(c21hip_split_filter_xy_shared_pair(
+                        c->x3_unf, c->x3_work, c->x3_work2, s->hii_filter, c->nx, c->ny, c->nz,
+                        s->box_len, s->box_len_z, (float)s->R[R_a], (float)s->R[R_b], buf_a, buf_b,
+                        bits & ~1, c->stream));
+                if (c->fused_rc)
+                    TRY(c21hip_split_filter_xy_single_pair(
+                        c->sfr_unf, c->sfr_work, c->sfr_work2, s->stars_filter, (float)s->mfp_meandens,
+                        c->nx, c->ny, c->nz, s->box_len, s->box_len_z, (float)s->R[R_a],
+                        (float)s->R[R_b], bits & ~1, c->stream));
             }
             if (c->x4_on) /* N_rec under the density grid's window too (IonisationBox.c:613) */
                 TRY(c21hip_split_filter_xy_shared_pair(
@@ -935,22 +906,17 @@ static int fused_step(ion_ctx *c, int R_a, int R_b, unsigned char *first_cross, 
                     bits & ~1, c->stream));
             /* (the tables are free after pass X, their only reader; releasing them there lets the
              * next builds run under pass Y, which measured 4 ms per call slower than under pass Z) */
-            if (ph == (yy ? 2 : 1) && tab_async) {
+            if (ph == 1 && tab_async) {
                 TRY(c21hip_event_record(g_tab.ev_used[buf_a], c->stream));
                 TRY(c21hip_event_record(g_tab.ev_used[buf_b], c->stream));
             }
-            if (ph == 1 && !yy) {
+            if (ph == 1) {
                 c->cur_xe = xe_of[0];
                 c->cur_x4 = c->x4_work;
                 TRY(z_ionise_radius(c, R_a, c->delta_work, c->stars_work, xw[0], first_cross));
             }
         }
         c->tab_seq++;
-        if (yy) {
-            c->cur_xe = xe_of[0];
-            c->cur_x4 = c->x4_work;
-            TRY(z_ionise_radius(c, R_a, c->delta_work, c->stars_work, xw[0], first_cross));
-        }
         c->cur_xe = xe_of[1];
         c->cur_x4 = c->x4_work2;
         TRY(z_ionise_radius(c, R_b, c->delta_work2, c->stars_work2, xw[1], first_cross));
@@ -1250,10 +1216,8 @@ static int eul_band_after(ion_ctx *c, int R_ct, int next_R, int banded, int sig_
         if (h2 >= 0) t_cur = d1 / (log(s->R[h1]) - log(s->R[h2]));
     }
     /* three equally spaced points in ln R (the ladder is geometric; a rank's share of it too): quadratic
-     * extrapolation -- the E-INTEGRAL mean doubles over the ladder and bends (C21CM_EUL_BAND_QUAD=0: linear) */
-    const char *e_q = getenv("C21CM_EUL_BAND_QUAD");
-    const int quad = h1 >= 0 && h2 >= 0 && next_R >= 1 && fabs(t_next - 1.) < 1e-6 && fabs(t_cur - 1.) < 1e-6 &&
-                     !(e_q && e_q[0] == '0');
+     * extrapolation -- the E-INTEGRAL mean doubles over the ladder and bends (linear otherwise) */
+    const int quad = h1 >= 0 && h2 >= 0 && next_R >= 1 && fabs(t_next - 1.) < 1e-6 && fabs(t_cur - 1.) < 1e-6;
     TRY(c21hip_eul_band(partials, n_part, sum_dev, (double)c->ntot, s->mass_dep_zeta,
                         s->f_limit_acg, c->scalars + SC_MEANS, R_ct, h1, h2, t_cur, t_next,
                         predict_next ? next_R : -1, banded, s->fix_mean, s->mean_f_coll, s->ion_eff_factor,
