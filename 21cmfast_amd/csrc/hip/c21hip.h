@@ -76,6 +76,10 @@ int c21hip_fft_r2c(float *padded, int nx, int ny, int nz, void *stream);
 int c21hip_fft_c2r(float *padded, int nx, int ny, int nz, void *stream);
 /* n_batch padded boxes back to back (rocFFT, one batched plan) */
 int c21hip_fft_r2c_batched(float *padded, int nx, int ny, int nz, int n_batch, void *stream);
+/* the inverse of n_batch padded boxes back to back, unnormalised as c21hip_fft_c2r (rocFFT, one batched plan),
+ * and its double-precision twin on double[n_batch][nx][ny][2(nz/2+1)] */
+int c21hip_fft_c2r_batched(float *padded, int nx, int ny, int nz, int n_batch, void *stream);
+int c21hip_fft_c2r_batched_f64(double *padded, int nx, int ny, int nz, int n_batch, void *stream);
 void c21hip_fft_release(void);
 /* 1 when the hand-written power-of-two transform is used, 0 for rocFFT */
 int c21hip_fft_is_native(int nx, int ny, int nz);
@@ -871,6 +875,36 @@ int c21hip_moments_mean(const float *in, int nx, int ny, int nz, long long row_p
 int c21hip_moments_central(const float *in, int nx, int ny, int nz, long long row_pitch, const long long *offsets,
                            int n_batch, const double *mean, int n_bins, const double *edges, double *rowsum,
                            double *part, double *moments, unsigned long long *hist, void *stream);
+
+/* ---- bispectrum_kernels.hip : bispectra of boxes and lightcone chunks (bispectrum_driver.c) ---- */
+#define C21HIP_BISPEC_MAX_BINS 32
+#define C21HIP_BISPEC_GROUP 8 /* third shells one products workgroup accumulates */
+/* ints per products group: b1, b2, the number of third shells (1 .. GROUP), then GROUP third shells (unused
+ * places repeat b2 and are not read) */
+#define C21HIP_BISPEC_GROUP_INTS (3 + C21HIP_BISPEC_GROUP)
+typedef struct c21hip_bispec_tabs { /* device pointers the driver fills */
+    const double *kx, *ky, *kz; /* wavenumbers per axis: nx, ny, nz/2 + 1 */
+    const double *thr;          /* n_bins + 1: the |k|^2 thresholds of the shell edges (as the power bins') */
+    int n_bins;
+} c21hip_bispec_tabs;
+/* one pass over the half spectrum complex[nx][ny][nz/2+1]: stack[s][mode] = the mode where its shell is s, else 0,
+ * for every s < n_bins and every mode (each element written once).  as_double = 0: float2 stack, the modes of spec;
+ * 1: double2 stack, 1 + 0i in place of the mode (the shell indicators; spec is not read) */
+int c21hip_bispec_fill(const float *spec, void *stack, int as_double, int nx, int ny, int nz,
+                       const c21hip_bispec_tabs *t, void *stream);
+/* slabs of whole rows the products kernel cuts a box into, and rows per slab: a function of the shape alone */
+int c21hip_bispec_slabs(int nx, int ny, int nz, int *rows_per_slab);
+/* stack: n_bins padded real boxes [nx ny][2(nz/2+1)] (float, or double when as_double).  Group g (groups, device:
+ * n_groups x C21HIP_BISPEC_GROUP_INTS) and slab s give partials[s][g GROUP + j] = the fp64 sum over the slab's
+ * cells, in a fixed order, of box(b1) box(b2) box(b3_j) */
+int c21hip_bispec_products(const void *stack, int as_double, int nx, int ny, int nz, const int *groups,
+                           int n_groups, double *partials, void *stream);
+/* S[b][t] = the sum over the slabs, in a fixed order, of partials[b][slab][slot[t]].  counts_in given: out_b[b][t] =
+ * scale S / (n_cells counts_in[t]), NaN where the count is 0.  Otherwise (n_batch = 1) counts_out[t] = the nearest
+ * integer to S / n_cells */
+int c21hip_bispec_finish(const double *partials, int n_batch, int n_slabs, int n_slots, const int *slot, int n_tri,
+                         double scale, double n_cells, const long long *counts_in, double *out_b,
+                         long long *counts_out, void *stream);
 
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */

@@ -30,12 +30,12 @@ struct Plan {
     void *work = nullptr;
     size_t work_bytes = 0;
 };
-using Key = std::tuple<int, int, int, int, int>;  // nx, ny, nz, inverse, batch
+using Key = std::tuple<int, int, int, int, int, int>;  // nx, ny, nz, inverse, batch, double precision
 std::map<Key, Plan> g_plans;
 std::mutex g_mutex;
 bool g_setup = false;
 
-int make_plan(Plan &p, int nx, int ny, int nz, int inverse, int batch) {
+int make_plan(Plan &p, int nx, int ny, int nz, int inverse, int batch, int f64) {
     if (!g_setup) {
         if (rocfft_setup() != rocfft_status_success) {
             c21hip_set_error("rocfft_setup failed");
@@ -67,7 +67,8 @@ int make_plan(Plan &p, int nx, int ny, int nz, int inverse, int batch) {
         st = rocfft_plan_create(&p.plan, rocfft_placement_inplace,
                                 inverse ? rocfft_transform_type_real_inverse
                                         : rocfft_transform_type_real_forward,
-                                rocfft_precision_single, 3, lengths, (size_t)batch, desc);
+                                f64 ? rocfft_precision_double : rocfft_precision_single, 3, lengths,
+                                (size_t)batch, desc);
     if (desc) rocfft_plan_description_destroy(desc);
     if (st != rocfft_status_success) {
         c21hip_set_error("rocFFT plan creation failed (%dx%dx%d, inverse=%d, status %d)", nx, ny,
@@ -88,15 +89,15 @@ int make_plan(Plan &p, int nx, int ny, int nz, int inverse, int batch) {
     return 0;
 }
 
-int run_rocfft(float *padded, int nx, int ny, int nz, int inverse, void *stream, int batch = 1) {
+int run_rocfft(void *padded, int nx, int ny, int nz, int inverse, void *stream, int batch = 1, int f64 = 0) {
     Plan *p = nullptr;
     {
         std::lock_guard<std::mutex> lock(g_mutex);
-        Key key(nx, ny, nz, inverse, batch);
+        Key key(nx, ny, nz, inverse, batch, f64);
         auto it = g_plans.find(key);
         if (it == g_plans.end()) {
             Plan fresh;
-            int st = make_plan(fresh, nx, ny, nz, inverse, batch);
+            int st = make_plan(fresh, nx, ny, nz, inverse, batch, f64);
             if (st) return st;
             it = g_plans.emplace(key, fresh).first;
         }
@@ -137,6 +138,22 @@ extern "C" int c21hip_fft_r2c_batched(float *padded, int nx, int ny, int nz, int
         return C21CM_VALUE_ERROR;
     }
     return run_rocfft(padded, nx, ny, nz, 0, stream, n_batch);
+}
+
+extern "C" int c21hip_fft_c2r_batched(float *padded, int nx, int ny, int nz, int n_batch, void *stream) {
+    if (n_batch < 1) {
+        c21hip_set_error("batched c2r: n_batch must be >= 1");
+        return C21CM_VALUE_ERROR;
+    }
+    return run_rocfft(padded, nx, ny, nz, 1, stream, n_batch);
+}
+
+extern "C" int c21hip_fft_c2r_batched_f64(double *padded, int nx, int ny, int nz, int n_batch, void *stream) {
+    if (n_batch < 1) {
+        c21hip_set_error("batched c2r: n_batch must be >= 1");
+        return C21CM_VALUE_ERROR;
+    }
+    return run_rocfft(padded, nx, ny, nz, 1, stream, n_batch, 1);
 }
 
 extern "C" int c21hip_fft_c2r(float *padded, int nx, int ny, int nz, void *stream) {

@@ -395,6 +395,13 @@ enum c21_ws_slot {
     WS_MO_IN,   /* staged host field */
     WS_MO_SUMS, /* row sums, means, moments, histogram */
     WS_MO_FLAG,
+    /* ---- bispectrum_driver.c ---- */
+    WS_BS_TAB,   /* wavenumbers, thresholds, batch offsets, counts, products groups, slots */
+    WS_BS_IN,    /* staged host field */
+    WS_BS_PAD,   /* the packed chunks and, in place, their half spectra */
+    WS_BS_STACK, /* one padded box per shell: float, or double in the indicator pass */
+    WS_BS_SUMS,  /* row sums and means of the pack, products partials, outputs */
+    WS_BS_FLAG,
 
     WS_COUNT
 };

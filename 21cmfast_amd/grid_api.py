@@ -1426,3 +1426,43 @@ def field_moments(field, shape, *, offsets=(0,), row_pitch=None, edges=None, str
                                         None if edges is None else edges.ctypes.data_as(C.c_void_p), _vptr(moments),
                                         _vptr(hist), _stream(stream)), "c21cm_field_moments_grids")
     return moments, hist
+
+
+def bispectrum(field, shape, lengths, edges, triangles, *, offsets=(0,), row_pitch=None, stream=None):
+    """Bispectra of ``len(offsets)`` boxes of ``shape`` = (nx, ny, nz) cells and ``lengths`` (Lx, Ly, Lz) read from
+    the float32 array ``field`` (the layout of ``power_spectrum``: box b at flat element ``offsets[b] + (i ny + j)
+    row_pitch + l``).  ``edges``: the n_bins + 1 shell edges in |k|; ``triangles``: (n, 3) shell indices b1 <= b2 <=
+    b3.  Returns ``(bispectrum, n_triangles)``: float64 (n_batch, n) and int64 (n,), the closed mode triplets of
+    each triangle (the same for every box); numpy for numpy input, torch on the field's device for a torch CUDA
+    field.  The estimator is written down at ``c21cm_bispectrum_grids`` (include/c21cm_grid.h)."""
+    nx, ny, nz = (int(x) for x in shape)
+    row_pitch = nz if row_pitch is None else int(row_pitch)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_batch = len(offsets)
+    _f32_dense(field, "field")
+    size = int(np.prod(field.shape, dtype=np.int64))
+    if n_batch < 1 or offsets.min() < 0 or offsets.max() + (nx * ny - 1) * row_pitch + nz > size:
+        raise ValueError("the boxes do not lie inside the field")
+    edges = np.ascontiguousarray(edges, np.float64)
+    if edges.ndim != 1 or edges.size < 2:
+        raise ValueError("edges must be a 1-D array of at least 2 values")
+    tri = np.asarray(triangles)
+    if tri.ndim != 2 or tri.shape[1] != 3 or tri.shape[0] < 1 or tri.dtype.kind not in "iu":
+        raise ValueError("triangles must be an (n, 3) array of integers, n >= 1")
+    tri = np.ascontiguousarray(tri, np.int32)
+    n_tri = len(tri)
+    if _is_torch(field):
+        import torch
+
+        out = torch.empty((n_batch, n_tri), dtype=torch.float64, device=field.device)
+        counts = torch.empty((n_tri,), dtype=torch.int64, device=field.device)
+    else:
+        out, counts = np.empty((n_batch, n_tri)), np.empty((n_tri,), np.int64)
+    bins = S.BispecBins(n_bins=len(edges) - 1, edges=edges.ctypes.data_as(S.c_double_p), n_triangles=n_tri,
+                        triangles=tri.ctypes.data_as(C.POINTER(C.c_int)))
+    Lx, Ly, Lz = (float(x) for x in lengths)
+    lib = load()
+    check(lib.c21cm_bispectrum_grids(_vptr(field), nx, ny, nz, n_batch, row_pitch, offsets.ctypes.data_as(C.c_void_p),
+                                     Lx, Ly, Lz, C.byref(bins), _vptr(out), _vptr(counts), _stream(stream)),
+          "c21cm_bispectrum_grids")
+    return out, counts

@@ -16,7 +16,9 @@ the field before the transform, f' = (f - mean) wx[i] wy[j] wz[l], the power div
 ``mu_min`` / ``mu_max`` and ``wedge_slope`` / ``wedge_buffer`` cut the modes of the spherical average;
 ``return_variance`` adds the population variance of the per-mode power in each bin.  ``get_moments``,
 ``get_pdf`` and ``lightcone_moments`` are the one-point statistics of a box or of the chunks of a
-lightcone (``csrc/hip/moments_kernels.hip``).
+lightcone (``csrc/hip/moments_kernels.hip``).  ``get_bispectrum`` and ``lightcone_bispectra`` are the three-point
+statistic, the FFT estimator over shells in |k| (``csrc/hip/bispectrum_kernels.hip``; its spec is
+``tests/bispectrum_reference.py``).
 
 Arrays may be numpy (results are numpy) or torch CUDA tensors (results are torch tensors on the same
 device; the field never visits the host).  Argument errors are ``ValueError``; a non-finite field value
@@ -544,4 +546,141 @@ def lightcone_moments(lightcone, *, chunk_length=None, chunk_starts=None, redshi
     if edges is not None:
         res.pdf = _pdf_from_counts(hist, edges, density)
         res.edges = _edges_like(edges, hist)
+    return res
+
+
+BISPECTRUM_MAX_BINS = 32
+
+
+def bispectrum_k_range(shape, boxlength) -> tuple:
+    """``(k_min, k_max)`` of the default bispectrum shells: half the largest fundamental, max(2 pi / L) / 2, up to
+    (2/3) min(pi n / L) -- two thirds of the smallest Nyquist wavenumber, below which no triplet of modes closes
+    modulo the grid and no Nyquist mode is in a shell."""
+    L = _lengths(boxlength, len(shape))
+    return max(2.0 * np.pi / l for l in L) / 2.0, (2.0 / 3.0) * min(np.pi * int(n) / l for n, l in zip(shape, L))
+
+
+def bispectrum_edges(shape, boxlength, bins=8, log_bins=False) -> np.ndarray:
+    """The shell edges ``get_bispectrum`` uses for a grid of ``shape``: an int gives ``np.linspace(k_min, k_max,
+    bins + 1)`` (``log_bins``: ``np.geomspace``) over ``bispectrum_k_range``; an array is taken as the edges.
+    Checked either way: 1 to 32 shells, finite and increasing, the first edge > 0 (k = 0 is in no shell), the last
+    <= k_max."""
+    kmin, kmax = bispectrum_k_range(shape, boxlength)
+    e = make_edges(bins, kmin, kmax, kmin, log_bins)
+    if not 1 <= len(e) - 1 <= BISPECTRUM_MAX_BINS:
+        raise ValueError(f"a bispectrum takes 1 to {BISPECTRUM_MAX_BINS} shells, got {len(e) - 1}")
+    if not e[0] > 0:
+        raise ValueError("the first edge must be > 0: k = 0 is in no shell")
+    if e[-1] > kmax:
+        raise ValueError(f"the last edge {e[-1]!r} exceeds k_max = (2/3) min(pi n / L) = {kmax!r}")
+    return e
+
+
+def bispectrum_triangles(edges) -> np.ndarray:
+    """Every triangle of shells (b1 <= b2 <= b3) that can hold a closed triplet of modes, ``e[b3] < e[b1 + 1] +
+    e[b2 + 1]``, in lexicographic order: int32 (n, 3)."""
+    e = np.asarray(edges, np.float64)
+    if e.ndim != 1 or e.size < 2:
+        raise ValueError("edges must be a 1-D array of at least 2 values")
+    n = e.size - 1
+    b1, b2, b3 = np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij")
+    keep = (b1 <= b2) & (b2 <= b3) & (e[b3] < e[b1 + 1] + e[b2 + 1])
+    return np.stack([b1[keep], b2[keep], b3[keep]], axis=1).astype(np.int32)
+
+
+def _check_triangles(triangles, edges) -> np.ndarray:
+    if triangles is None:
+        return bispectrum_triangles(edges)
+    if _is_torch(triangles):
+        triangles = triangles.detach().cpu().numpy()
+    t = np.asarray(triangles)
+    if t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in "iu":
+        raise ValueError("triangles must be an (n, 3) array of integers")
+    if t.shape[0] < 1:
+        raise ValueError("at least one triangle is needed")
+    n = len(edges) - 1
+    if t.min() < 0 or t.max() >= n or np.any(t[:, 0] > t[:, 1]) or np.any(t[:, 1] > t[:, 2]):
+        raise ValueError(f"every triangle needs 0 <= b1 <= b2 <= b3 < {n}")
+    return np.ascontiguousarray(t, np.int32)
+
+
+@dataclass
+class Bispectrum:
+    """What ``get_bispectrum`` and ``lightcone_bispectra`` return (the latter with a leading chunk axis on
+    ``bispectrum``, ``power`` and ``reduced``): ``bispectrum`` (n_tri,) float64, NaN where a triangle holds no
+    closed triplet; ``triangles`` (n_tri, 3) shell indices; ``n_triangles`` (n_tri,) int64 closed triplets of modes;
+    ``k`` (n_tri, 3) the mean |k| of the three shells; ``power`` / ``n_modes`` (n_bins,) of the shells, as
+    ``get_power(bins=edges)``; ``reduced`` B / (P1 P2 + P2 P3 + P3 P1) when asked for; ``edges``; for a lightcone
+    ``chunk_starts`` and ``redshifts`` (central redshift of each chunk, when slice redshifts were given)."""
+
+    bispectrum: object
+    triangles: object
+    n_triangles: object
+    k: object
+    power: object
+    n_modes: object
+    edges: object
+    reduced: object = None
+    chunk_starts: np.ndarray | None = None
+    redshifts: np.ndarray | None = None
+
+
+def _bispectrum_result(f, shape, L, edges, tri, offsets, row_pitch, reduced):
+    power, kmean, counts = api.power_spectrum(f, None, shape, L, edges, offsets=offsets, row_pitch=row_pitch)
+    B, n_tri = api.bispectrum(f, shape, L, edges, tri, offsets=offsets, row_pitch=row_pitch)
+    if _is_torch(B):
+        import torch
+
+        idx = torch.from_numpy(tri.astype(np.int64)).to(B.device)
+        tri_out = torch.from_numpy(tri.copy()).to(B.device)
+    else:
+        idx = tri_out = tri
+    red = None
+    if reduced:
+        p1, p2, p3 = power[:, idx[:, 0]], power[:, idx[:, 1]], power[:, idx[:, 2]]
+        red = B / (p1 * p2 + p2 * p3 + p3 * p1)
+    return Bispectrum(bispectrum=B, triangles=tri_out, n_triangles=n_tri, k=kmean[0][idx], power=power,
+                      n_modes=counts[0], edges=_edges_like(edges, B), reduced=red)
+
+
+def get_bispectrum(field, boxlength, *, bins=8, log_bins=False, triangles=None, reduced=False) -> Bispectrum:
+    """The bispectrum of the 3-D ``field`` in a box of ``boxlength`` (a scalar or 3 lengths) by the FFT estimator,
+    conventions as ``get_power``: with D the unnormalised DFT, delta_b(x) = sum_{k in shell b} D(k) exp(+i k x) and
+    I_b the same sum of ones, B(b1, b2, b3) = (V^2 / N^3) sum_x delta_b1 delta_b2 delta_b3 / sum_x I_b1 I_b2 I_b3.
+    ``bins`` / ``log_bins``: the shells (``bispectrum_edges``; a shell is exactly a ``get_power`` bin of the same
+    edges); ``triangles``: (n, 3) shell indices b1 <= b2 <= b3, default ``bispectrum_triangles``.  A triangle's
+    value does not depend on which others are asked for, and two calls give the same bits.  The device holds one
+    padded box per shell (twice that, in fp64, the first time a geometry is seen: the triangle counts)."""
+    _check_field(field)
+    shape = _shape(field)
+    L = _lengths(boxlength)
+    edges = bispectrum_edges(shape, L, bins, log_bins)
+    tri = _check_triangles(triangles, edges)
+    res = _bispectrum_result(_f32(field), shape, L, edges, tri, (0,), None, reduced)
+    res.bispectrum, res.power = res.bispectrum[0], res.power[0]
+    if reduced:
+        res.reduced = res.reduced[0]
+    return res
+
+
+def lightcone_bispectra(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None, bins=8,
+                        log_bins=False, triangles=None, reduced=False) -> Bispectrum:
+    """Bispectra of the chunks of a rectilinear ``lightcone`` (nx, ny, n_slices) of cells of ``cell_size`` [Mpc],
+    chunked as ``lightcone_power_spectra`` chunks it and with its central-redshift rule; all chunks go through one
+    library call and share the shells, the triangles and their counts.  ``bispectrum``, ``power`` and ``reduced``
+    carry a leading chunk axis."""
+    if lightcone.ndim != 3:
+        raise ValueError(f"lightcone must be a 3-D (nx, ny, n_slices) array, got {lightcone.ndim} dimensions")
+    nx, ny, ns = _shape(lightcone)
+    dx = float(cell_size)
+    if not (np.isfinite(dx) and dx > 0):
+        raise ValueError("cell_size must be positive and finite")
+    n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
+    if min(nx, ny) < 2:
+        raise ValueError("every axis of a chunk needs at least 2 cells")
+    shape, L = (nx, ny, n), (nx * dx, ny * dx, n * dx)
+    edges = bispectrum_edges(shape, L, bins, log_bins)
+    tri = _check_triangles(triangles, edges)
+    res = _bispectrum_result(_f32(lightcone), shape, L, edges, tri, starts, ns, reduced)
+    res.chunk_starts, res.redshifts = starts, z
     return res

@@ -565,6 +565,17 @@ class PowerOpts(_Base):
     ]
 
 
+class BispecBins(_Base):
+    """``c21cm_bispec_bins`` (include/c21cm_grid.h): the shells and triangles of a bispectrum."""
+
+    _fields_ = [
+        ("n_bins", C.c_int),
+        ("edges", c_double_p),
+        ("n_triangles", C.c_int),
+        ("triangles", C.POINTER(C.c_int)),
+    ]
+
+
 def brightness_spec(n_cells, redshift, cosmo=None, use_ts_fluct=False) -> "BrightnessSpec":
     """The two float constants of BrightnessTemperatureBox.c:43-49 for a CosmoParams struct
     (default cosmology if None)."""

@@ -1035,6 +1035,30 @@ int c21cm_field_moments_grids(const float *field, int nx, int ny, int nz, int n_
                               const long long *batch_offsets, int n_bins, const double *edges, double *moments,
                               long long *hist, void *stream);
 
+/* ---- Bispectra of boxes and lightcone chunks (the spec is tests/bispectrum_reference.py) ----
+ * The layout, the wavenumbers and the half-open shells e[b] <= |k| < e[b+1] of c21cm_power_spectrum_grids (a shell
+ * is exactly one of its bins).  With D the unnormalised DFT of a box (fp32 transforms), delta_b(x) = sum_{k in b}
+ * D(k) exp(+i k x) and I_b(x) the same sum of ones, a triangle of shells b1 <= b2 <= b3 has S = sum_x delta_b1
+ * delta_b2 delta_b3 (fp64 sums in a fixed order), n_tri = (1/N) sum_x I_b1 I_b2 I_b3 -- the number of mode triplets
+ * with k1 + k2 + k3 = 0, an integer, from fp64 transforms and kept for the next call with the same shape, lengths
+ * and edges -- and B = (V^2 / N^3) S / (N n_tri), V = Lx Ly Lz, N = nx ny nz; NaN where n_tri = 0.  1 <= n_bins <=
+ * 32; 0 < edges[0]; edges[n_bins] <= (2/3) min(pi nx / Lx, pi ny / Ly, pi nz / Lz), below which no triplet closes
+ * modulo the grid and no Nyquist mode is in a shell.  Outputs (host or device): bispectrum[n_batch][n_triangles],
+ * n_triangles[n_triangles] (the same for every box).  Deterministic: two calls give the same bits, and a triangle's
+ * value does not depend on which other triangles are asked for.  Device memory: n_bins padded boxes (twice that
+ * while the counts of a new geometry are made) beside the packed boxes.  Errors are C21CM_VALUE_ERROR with a
+ * message; a non-finite field value is C21CM_INFINITY_OR_NAN_ERROR, nothing is written. */
+typedef struct c21cm_bispec_bins {
+    int n_bins;            /* shells, 1 .. 32 */
+    const double *edges;   /* host, n_bins + 1, increasing, edges[0] > 0 */
+    int n_triangles;       /* >= 1 */
+    const int *triangles;  /* host, n_triangles x {b1, b2, b3}, 0 <= b1 <= b2 <= b3 < n_bins */
+} c21cm_bispec_bins;
+
+int c21cm_bispectrum_grids(const float *field, int nx, int ny, int nz, int n_batch, long long row_pitch,
+                           const long long *batch_offsets, double Lx, double Ly, double Lz,
+                           const c21cm_bispec_bins *bins, double *bispectrum, long long *n_triangles, void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
