@@ -157,36 +157,43 @@ int c21hip_wev_applicable(int filter_a, int filter_b, int n_grids, int nx, int n
 int c21hip_split_filter_xy_single_pair(const float *src, float *work, float *work2, int filter_type,
                                        float R_param, int nx, int ny, int nz, double box_len,
                                        double box_len_z, float R, float R2, int phases, void *stream);
-/* fused pass Z with a recombination model (CELL_RECOMB): barrier (1 + N_rec / (1 + delta)), delta_R
- * of a first crossing left in the Gamma_12 grid */
+/* Fused pass Z of delta_R and the filtered emissivity + sum(stars) + ionisation barrier for Lagrangian source
+ * grids at radius index > 0 (IonisationBox.c:634-638,821-837,1054-1151): one entry, one descriptor.  NULL: absent. */
+typedef struct c21hip_z_ionise_desc {
+    size_t size;                  /* sizeof(c21hip_z_ionise_desc); any other value is refused (C21CM_VALUE_ERROR) */
+    const float *delta_work;      /* density and emissivity spectra after passes X, Y */
+    const float *stars_work;
+    const float *xe_work;         /* filtered x_e spectrum of a spin-temperature run: barrier f zeta > 1 - x_e
+                                   * (IonisationBox.c:1118); 256- / 512- / 1024-point z-lines */
+    const float *nrec_work;       /* recomb, CELL_RECOMB = false: the previous snapshot's N_rec filtered at this
+                                   * radius (with xe_work too: four spectra, 512-point z-lines) */
+    const float *nrec;            /* recomb without nrec_work: the cell's own previous N_rec, dense ... */
+    double rec0;                  /* ... or, nrec == NULL, the homogeneous model's one number */
+    int recomb;                   /* recombination model: barrier (1 + N_rec / (1 + delta)); a first crossing
+                                   * leaves delta_R in g12 for c21hip_split_z_sfr_gamma12; sum_out is not used */
+    float *g12;                   /* recomb: dense Gamma_12 grid */
+    unsigned char *first_cross;   /* uint8 [N] mask of first crossings, updated; or, instead of it, ... */
+    unsigned *cross_plane;        /* ... this radius' plane of crossing bits (c21hip_z_cross_bits_supported) */
+    double *partials;             /* c21hip_z_ionise_partials doubles: sum(stars) per workgroup */
+    double *sum_out;              /* the sum on the device; NULL defers the reduction: the partials of every radius
+                                   * stay at partials + R * stride and c21hip_batched_means reduces them at once */
+    int nx, ny, nz, r_index;
+    double rhocrit_omb, ion_eff;
+    int mass_dep_zeta;
+    double f_limit;
+} c21hip_z_ionise_desc;
+int c21hip_split_z_ionise(const c21hip_z_ionise_desc *desc, void *stream);
+/* which boxes the entry serves with ... an x_e grid */
+int c21hip_z_ionise_xe_supported(int nx, int ny, int nz);
+/* ... a recombination model; with a third spectrum too (x_e or the filtered N_rec); with both */
+int c21hip_z_ionise_recomb_supported(int nx, int ny, int nz);
 int c21hip_z_ionise_recomb_xe_supported(int nx, int ny, int nz);
-int c21hip_split_z_ionise_recomb_xe(const float *delta_work, const float *stars_work, const float *xe_work,
-                                    const float *nrec, double rec0, float *g12, unsigned char *first_cross,
-                                    double *partials, int nx, int ny, int nz, int r_index,
-                                    double rhocrit_omb, double ion_eff, int mass_dep_zeta, double f_limit,
-                                    void *stream);
-/* ... with N_rec of the previous snapshot filtered at this radius as the third line (CELL_RECOMB = false) */
-int c21hip_split_z_ionise_recomb_nrec(const float *delta_work, const float *stars_work, const float *nrec_work,
-                                      float *g12, unsigned char *first_cross, double *partials, int nx,
-                                      int ny, int nz, int r_index, double rhocrit_omb, double ion_eff,
-                                      int mass_dep_zeta, double f_limit, void *stream);
-/* ... and with both: the x_e grid of a spin-temperature run AND the filtered N_rec (four spectra, nz = 512) */
 int c21hip_z_ionise_recomb_xe_nrec_supported(int nx, int ny, int nz);
-int c21hip_split_z_ionise_recomb_xe_nrec(const float *delta_work, const float *stars_work, const float *xe_work,
-                                         const float *nrec_work, float *g12, unsigned char *first_cross,
-                                         double *partials, int nx, int ny, int nz, int r_index,
-                                         double rhocrit_omb, double ion_eff, int mass_dep_zeta, double f_limit,
-                                         void *stream);
-int c21hip_split_z_ionise_recomb(const float *delta_work, const float *stars_work, const float *nrec,
-                                 double rec0, float *g12, unsigned char *first_cross,
-                                 double *partials, int nx, int ny, int nz, int r_index,
-                                 double rhocrit_omb, double ion_eff, int mass_dep_zeta,
-                                 double f_limit, void *stream);
-/* ... followed, per radius, by the pass Z of the filtered whalo_sfr: first crossings of r_index
+int c21hip_z_ionise_partials(int nx, int ny, int nz);
+/* a recombination radius is followed by the pass Z of the filtered whalo_sfr: first crossings of r_index
  * (g12 holds their delta_R) receive Gamma_12 = g12_scale / (1 + delta_R) max(sfr_R, 0) */
 int c21hip_split_z_sfr_gamma12(const float *sfr_work, const unsigned char *first_cross, float *g12,
                                int nx, int ny, int nz, int r_index, double g12_scale, void *stream);
-int c21hip_z_ionise_recomb_supported(int nx, int ny, int nz);
 /* Eulerian source models with an x_e grid: pass Z of the filtered x_e spectrum with the barrier
  * f_coll zeta > 1 - x_e(R) fused in (nion_dense: the radius' dense f_coll, *mean_dev its mean);
  * first crossings go into the mask, x_e(R) is never stored (IonisationBox.c:1091-1118) */
@@ -267,38 +274,17 @@ int c21hip_copy_filter_split(const float *src_split, float *dst_split, int nx, i
                              float R_param, int apply, void *stream);
 int c21hip_split_z_c2r(const float *split_work, float *real_out, long out_zstride, int nx, int ny,
                        int nz, void *stream);
-/* Fused pass Z of delta_R and the filtered emissivity + sum(stars) + ionisation barrier for
- * Lagrangian source grids at radius index > 0; writes only first_cross (uint8 [N]).
- * partials: nx*ny/8 doubles.  reference: IonisationBox.c:634-638,821-837,1054-1151 */
-int c21hip_split_z_ionise_stars(const float *delta_work, const float *stars_work,
-                                unsigned char *first_cross, double *partials, double *sum_out,
-                                int nx, int ny, int nz, int r_index, double rhocrit_omb,
-                                double ion_eff, int mass_dep_zeta, double f_limit, void *stream);
-/* sum_out == NULL in c21hip_split_z_ionise_stars defers the reduction: the partials of every
- * radius stay at partials + R * stride and ONE launch turns them into sums[R] / means[R] for
- * R = first, first - step, ... (count radii) */
-int c21hip_z_ionise_partials(int nx, int ny, int nz);
+/* the deferred sums of the fused pass Z (c21hip_z_ionise_desc.sum_out == NULL): ONE launch turns the partials at
+ * partials + R * stride into sums[R] / means[R] for R = first, first - step, ... (count radii) */
 int c21hip_batched_means(const double *partials, long stride, int n_partials, int first, int step,
                          int count, double ntot, int mass_dep_zeta, double f_limit, double *sums,
                          double *means, void *stream);
-/* fused pass Z with the filtered x_e spectrum as a third grid (spin-temperature runs; the
- * barrier becomes f_coll zeta > 1 - x_e, IonisationBox.c:1118); 512/1024-point z-lines */
-int c21hip_split_z_ionise_stars_xe(const float *delta_work, const float *stars_work,
-                                   const float *xe_work, unsigned char *first_cross,
-                                   double *partials, double *sum_out, int nx, int ny, int nz,
-                                   int r_index, double rhocrit_omb, double ion_eff,
-                                   int mass_dep_zeta, double f_limit, void *stream);
-int c21hip_z_ionise_xe_supported(int nx, int ny, int nz);
 /* Crossing bits: the two-grid fused pass Z on 512-point z-lines writes this radius' barrier outcome as
  * one bit per cell into its own plane (nx*ny*nz/8 bytes, write only) instead of updating the uint8
  * mask; c21hip_resolve_crossings turns the planes of the radii r_hi ... r_lo (the plane of radius r at
  * bits + (r - 1) * nlines * 16 words) into first_cross[nlines][512], every byte written.  The bit order
  * is private to the two kernels.  C21CM_CROSS_BITS=0: _supported returns 0 (the mask path). */
 int c21hip_z_cross_bits_supported(int nx, int ny, int nz);
-int c21hip_split_z_ionise_stars_bits(const float *delta_work, const float *stars_work,
-                                     unsigned *cross_plane, double *partials, double *sum_out, int nx,
-                                     int ny, int nz, int r_index, double rhocrit_omb, double ion_eff,
-                                     int mass_dep_zeta, double f_limit, void *stream);
 int c21hip_resolve_crossings(const unsigned *bits, int r_hi, int r_lo, unsigned char *first_cross,
                              size_t nlines, void *stream);
 /* passes X, Y of one grid with window a of the two-grid tables in buffer table_slot */

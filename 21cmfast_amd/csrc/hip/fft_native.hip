@@ -2325,12 +2325,21 @@ int dispatch_line_pass(int n, const LinePassArgs &a, int fmode, hipStream_t stre
     }
 }
 
+// One pass-Z launch: the twiddle pair of nz-point lines, the grid, the launch, its check.
+template <class Args>
+int launch_z(void (*fn)(Args, const float2 *, const float2 *), int nz, long n_groups, int block, size_t lds,
+             const Args &a, hipStream_t stream) {
+    const float2 *twH = twiddles(nz / 2);
+    const float2 *twN = twiddles(nz);
+    if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_groups), dim3(block), lds, stream, a, twH, twN);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 template <int NZ, int EPI = 0>
 int launch_z_c2r(const ZPassArgs &a, long nlines, hipStream_t stream) {
     constexpr int H = NZ / 2;
-    const float2 *twH = twiddles(H);
-    const float2 *twN = twiddles(NZ);
-    if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
     const size_t lds = sizeof(float2) * ((size_t)H * (LZ_PLAIN + 1) + H + H / 2 + 1);
     static bool attr_done = false;
     if (!attr_done) {
@@ -2338,10 +2347,7 @@ int launch_z_c2r(const ZPassArgs &a, long nlines, hipStream_t stream) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
-    hipLaunchKernelGGL((z_c2r_kernel<NZ, EPI>), dim3((unsigned)(nlines / LZ_PLAIN)), dim3(kBlock),
-                       lds, stream, a, twH, twN);
-    LAUNCH_CHECK();
-    return 0;
+    return launch_z(z_c2r_kernel<NZ, EPI>, NZ, nlines / LZ_PLAIN, kBlock, lds, a, stream);
 }
 
 // ---- fused pass Z, 512-point lines: wave-level transform -------------------------------------
@@ -3257,124 +3263,114 @@ int zw_lines_of(int nz, long nlines) {
     return (l && nlines % l == 0) ? l : 0;
 }
 
+// The fused pass-Z kernel of one request, chosen in ONE place: dispatch_z_fused launches what z_fused_select
+// returns, and the exported c21hip_z_*_supported predicates and c21hip_z_ionise_partials ask it too.
+struct ZFusedWant {
+    bool xe, rc, nrec, bits;  // x_e spectrum, recombination barrier, filtered N_rec spectrum, crossing bits
+};
+struct ZFusedPick {
+    void (*fn)(ZFusedArgs, const float2 *, const float2 *);  // nullptr: no kernel serves this request
+    int block, lines;  // threads per workgroup; z-lines per workgroup (one partial sum each)
+    size_t lds;        // dynamic LDS (the tile kernels)
+};
+
 template <int NZ>
-int launch_z_fused(const ZFusedArgs &a, long nlines, hipStream_t stream) {
+ZFusedPick z_fused_tile() {
     constexpr int H = NZ / 2;
-    const float2 *twH = twiddles(H);
-    const float2 *twN = twiddles(NZ);
-    if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-    const size_t lds = sizeof(float2) * ((size_t)H * (LZ_FUSED + 1) + H + H / 2 + 1);
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void *)z_c2r_ionise_kernel<NZ>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
+    return {z_c2r_ionise_kernel<NZ>, kBlock, LZ_FUSED, sizeof(float2) * ((size_t)H * (LZ_FUSED + 1) + H + H / 2 + 1)};
+}
+
+// say_why: a refusal leaves its reason in the error text (the dispatcher; the predicates ask silently).
+// `lines` is valid in a refusal too: what the two-grid kernel of this shape would write.
+ZFusedPick z_fused_select(int nz, long nlines, ZFusedWant w, bool say_why) {
+    const bool third = w.xe || w.nrec;  // a third spectrum beside density and emissivity
+    const int zwl = zw_lines_of(nz, nlines);
+    const bool zw3 = zw3_selected(nz, nlines);
+    ZFusedPick k{nullptr, kBlock, zw3 ? kBlock / 64 : (zwl ? zwl : LZ_FUSED), 0};
+    auto refuse = [&](const char *why) {
+        if (say_why) c21hip_set_error("%s", why);
+        return k;
+    };
+    if (w.xe && w.nrec && nz != 512)
+        return refuse("fused pass Z with an x_e grid and a filtered N_rec: 512-point z-lines only");
+    if (w.bits && !(nz == 512 && zwl && !w.rc && !third))
+        return refuse("fused pass Z: crossing bits need the two-grid wave kernel on 512-point z-lines");
+    if (w.rc && (zw3 || !zwl))
+        return refuse("fused pass Z with recombinations needs the 16-lane wave kernel (z-lines of 256 / 512 points)");
+    if (zw3) {  // 1024-point lines: three radix-8 stages per wave
+        k.fn = w.xe ? zw3_ionise_kernel<true> : zw3_ionise_kernel<false>;
+        return k;
     }
-    hipLaunchKernelGGL((z_c2r_ionise_kernel<NZ>), dim3((unsigned)(nlines / LZ_FUSED)), dim3(kBlock), lds,
-                       stream, a, twH, twN);
-    LAUNCH_CHECK();
-    return 0;
+    if (zwl) {
+        if (nz == 512) {  // (A = 16, P = 16)
+            k.block = C21X_ZW_BLOCK;
+            k.lines = C21X_ZW_BLOCK / 16;
+        }
+        if (w.rc && third) {  // recombinations AND a third spectrum (x_e of a spin-temperature run, or N_rec)
+            if (nz == 256)
+                k.fn = zw_ionise_kernel<16, true, 8, true>;
+            else if (nz == 512)
+                k.fn = zw_ionise_kernel<16, true, 16, true>;
+            else
+                return refuse("fused pass Z with recombinations and an x_e grid: 256- / 512-point z-lines only");
+        } else if (w.rc) {
+            if (nz == 256)
+                k.fn = zw_ionise_kernel<16, false, 8, true>;
+            else if (nz == 512)
+                k.fn = zw_ionise_kernel<16, false, 16, true>;
+            else
+                k.fn = zw_ionise_kernel<32, false, 16, true>;
+        } else if (third) {
+            if (nz == 256)
+                k.fn = zw_ionise_kernel<16, true, 8>;
+            else if (nz == 512)
+                k.fn = zw_ionise_kernel<16, true, 16>;
+            else
+                k.fn = zw_ionise_kernel<32, true, 16>;
+        } else if (nz == 256)
+            k.fn = zw_ionise_kernel<16, false, 8>;
+        else if (nz == 512 && w.bits)
+            k.fn = zw_ionise_kernel<16, false, 16, false, true>;
+        else if (nz == 512)
+            k.fn = zw_ionise_kernel<16, false, 16>;
+        else
+            k.fn = zw_ionise_kernel<32, false, 16>;
+        return k;
+    }
+    if (third) return refuse("fused pass Z with an x_e grid needs 256-, 512- or 1024-point z-lines");
+    switch (nz) {
+        case 64: return z_fused_tile<64>();
+        case 128: return z_fused_tile<128>();
+        case 192: return z_fused_tile<192>();
+        case 256: return z_fused_tile<256>();
+        case 384: return z_fused_tile<384>();
+        case 512: return z_fused_tile<512>();
+        case 768: return z_fused_tile<768>();
+        case 1024: return z_fused_tile<1024>();
+        case 1536: return z_fused_tile<1536>();
+        default:
+            if (say_why) c21hip_set_error("native FFT: unsupported z length %d for the fused pass", nz);
+            return k;
+    }
 }
 
 // *n_partials: how many workgroup partials of sum(stars) the launch wrote
-int dispatch_z_fused(int nz, const ZFusedArgs &a, long nlines, hipStream_t stream, int *n_partials) {
+int dispatch_z_fused(int nz, const ZFusedArgs &a, ZFusedWant w, long nlines, hipStream_t stream, int *n_partials) {
     KTimeScope kt(2, stream);
-    *n_partials = (int)(nlines / LZ_FUSED);
-    if (a.cross_bits && !(nz == 512 && zw_lines_of(nz, nlines) && !a.rc && !a.x_main)) {
-        c21hip_set_error("fused pass Z: crossing bits need the two-grid wave kernel on 512-point z-lines");
-        return C21CM_VALUE_ERROR;
+    const ZFusedPick k = z_fused_select(nz, nlines, w, true);
+    *n_partials = (int)(nlines / k.lines);
+    if (!k.fn) return C21CM_VALUE_ERROR;
+    static const void *attr_done = nullptr;  // the tile kernel whose dynamic LDS limit was raised last
+    if (k.lds && attr_done != (const void *)k.fn) {
+        (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+        attr_done = (const void *)k.fn;
     }
-    if (a.rc && (zw3_selected(nz, nlines) || !zw_lines_of(nz, nlines))) {
-        c21hip_set_error("fused pass Z with recombinations needs the 16-lane wave kernel (z-lines of 256 / 512 points)");
-        return C21CM_VALUE_ERROR;
-    }
-    if (zw3_selected(nz, nlines)) {  // 1024-point lines: three radix-8 stages per wave
-        const float2 *twH = twiddles(nz / 2);
-        const float2 *twN = twiddles(nz);
-        if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-        *n_partials = (int)(nlines / (kBlock / 64));
-        const dim3 grid((unsigned)(nlines / (kBlock / 64)));
-        if (a.x_main)
-            hipLaunchKernelGGL(zw3_ionise_kernel<true>, grid, dim3(kBlock), 0, stream, a, twH, twN);
-        else
-            hipLaunchKernelGGL(zw3_ionise_kernel<false>, grid, dim3(kBlock), 0, stream, a, twH, twN);
-        LAUNCH_CHECK();
-        return 0;
-    }
-    if (int zwl = zw_lines_of(nz, nlines)) {
-        const float2 *twH = twiddles(nz / 2);
-        const float2 *twN = twiddles(nz);
-        if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-        const int zblk = (nz == 512) ? C21X_ZW_BLOCK : kBlock;  // (A = 16, P = 16)
-        if (nz == 512) zwl = zblk / 16;
-        *n_partials = (int)(nlines / zwl);
-        const dim3 grid((unsigned)(nlines / zwl));
-#define ZW_FUSED(A, TS, P) \
-    hipLaunchKernelGGL((zw_ionise_kernel<A, TS, P>), grid, dim3(zblk), 0, stream, a, twH, twN)
-#define ZW_FUSED_RC(A, P) \
-    hipLaunchKernelGGL((zw_ionise_kernel<A, false, P, true>), grid, dim3(zblk), 0, stream, a, twH, twN)
-        if (a.rc && a.x_main) {  // recombinations AND the x_e grid of a spin-temperature run (round 4)
-            if (nz == 256)
-                hipLaunchKernelGGL((zw_ionise_kernel<16, true, 8, true>), grid, dim3(zblk), 0, stream, a, twH, twN);
-            else if (nz == 512)
-                hipLaunchKernelGGL((zw_ionise_kernel<16, true, 16, true>), grid, dim3(zblk), 0, stream, a, twH, twN);
-            else {
-                c21hip_set_error("fused pass Z with recombinations and an x_e grid: 256- / 512-point z-lines only");
-                return C21CM_VALUE_ERROR;
-            }
-        } else if (a.rc) {
-            if (nz == 256)
-                ZW_FUSED_RC(16, 8);
-            else if (nz == 512)
-                ZW_FUSED_RC(16, 16);
-            else
-                ZW_FUSED_RC(32, 16);
-        } else if (a.x_main) {
-            if (nz == 256)
-                ZW_FUSED(16, true, 8);
-            else if (nz == 512)
-                ZW_FUSED(16, true, 16);
-            else
-                ZW_FUSED(32, true, 16);
-        } else if (nz == 256)
-            ZW_FUSED(16, false, 8);
-        else if (nz == 512 && a.cross_bits)
-            hipLaunchKernelGGL((zw_ionise_kernel<16, false, 16, false, true>), grid, dim3(zblk), 0, stream, a, twH, twN);
-        else if (nz == 512)
-            ZW_FUSED(16, false, 16);
-        else
-            ZW_FUSED(32, false, 16);
-#undef ZW_FUSED
-#undef ZW_FUSED_RC
-        LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.x_main) {
-        c21hip_set_error("fused pass Z with an x_e grid needs 256-, 512- or 1024-point z-lines");
-        return C21CM_VALUE_ERROR;
-    }
-    switch (nz) {
-        case 64: return launch_z_fused<64>(a, nlines, stream);
-        case 128: return launch_z_fused<128>(a, nlines, stream);
-        case 192: return launch_z_fused<192>(a, nlines, stream);
-        case 256: return launch_z_fused<256>(a, nlines, stream);
-        case 384: return launch_z_fused<384>(a, nlines, stream);
-        case 512: return launch_z_fused<512>(a, nlines, stream);
-        case 768: return launch_z_fused<768>(a, nlines, stream);
-        case 1024: return launch_z_fused<1024>(a, nlines, stream);
-        case 1536: return launch_z_fused<1536>(a, nlines, stream);
-        default:
-            c21hip_set_error("native FFT: unsupported z length %d for the fused pass", nz);
-            return C21CM_VALUE_ERROR;
-    }
+    return launch_z(k.fn, nz, nlines / k.lines, k.block, k.lds, a, stream);
 }
 
 template <int NZ>
 int launch_z_r2c(const ZFwdArgs &a, long nlines, hipStream_t stream) {
     constexpr int H = NZ / 2;
-    const float2 *twH = twiddles(H);
-    const float2 *twN = twiddles(NZ);
-    if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
     const size_t lds = sizeof(float2) * ((size_t)H * (LZ_PLAIN + 1) + H + H / 2 + 1);
     static bool attr_done = false;
     if (!attr_done) {
@@ -3382,10 +3378,7 @@ int launch_z_r2c(const ZFwdArgs &a, long nlines, hipStream_t stream) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
-    hipLaunchKernelGGL((z_r2c_kernel<NZ>), dim3((unsigned)(nlines / LZ_PLAIN)), dim3(kBlock), lds,
-                       stream, a, twH, twN);
-    LAUNCH_CHECK();
-    return 0;
+    return launch_z(z_r2c_kernel<NZ>, NZ, nlines / LZ_PLAIN, kBlock, lds, a, stream);
 }
 
 // C21CM_Z_R2C=w: 1024-point forward z-lines on the 32-values-per-lane kernel (A/B switch)
@@ -3396,28 +3389,12 @@ bool zw3_r2c_on() {
 
 int dispatch_z_r2c(int nz, const ZFwdArgs &a, long nlines, hipStream_t stream) {
     if (nz == 1024 && a.in_zstride % 2 == 0 && zw3_selected(nz, nlines) && nlines % (2 * (kBlock / 64)) == 0 &&
-        zw3_r2c_on()) {
-        const float2 *twH = twiddles(nz / 2);
-        const float2 *twN = twiddles(nz);
-        if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-        hipLaunchKernelGGL((zw3_r2c_kernel<2>), dim3((unsigned)(nlines / (2 * (kBlock / 64)))), dim3(kBlock), 0,
-                           stream, a, twH, twN);
-        LAUNCH_CHECK();
-        return 0;
-    }
+        zw3_r2c_on())
+        return launch_z(zw3_r2c_kernel<2>, nz, nlines / (2 * (kBlock / 64)), kBlock, 0, a, stream);
     if (const int zwl = (a.in_zstride % 2 == 0) ? zw_lines_of(nz, nlines) : 0) {
-        const float2 *twH = twiddles(nz / 2);
-        const float2 *twN = twiddles(nz);
-        if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-        const dim3 grid((unsigned)(nlines / zwl));
-        if (nz == 256)
-            hipLaunchKernelGGL((zw_r2c_kernel<16, 8>), grid, dim3(kBlock), 0, stream, a, twH, twN);
-        else if (nz == 512)
-            hipLaunchKernelGGL((zw_r2c_kernel<16, 16>), grid, dim3(kBlock), 0, stream, a, twH, twN);
-        else
-            hipLaunchKernelGGL((zw_r2c_kernel<32, 16>), grid, dim3(kBlock), 0, stream, a, twH, twN);
-        LAUNCH_CHECK();
-        return 0;
+        auto fn = zw_r2c_kernel<16, 8>;  // 256-point lines
+        if (nz != 256) fn = (nz == 512) ? zw_r2c_kernel<16, 16> : zw_r2c_kernel<32, 16>;
+        return launch_z(fn, nz, nlines / zwl, kBlock, 0, a, stream);
     }
     switch (nz) {
         case 64: return launch_z_r2c<64>(a, nlines, stream);
@@ -3453,18 +3430,9 @@ int dispatch_z_c2r(int nz, const ZPassArgs &a_, long nlines, hipStream_t stream)
     a.reverse = zw_reverse_default();  // (every caller runs this right after the pass Y of the same spectrum)
     // (partial arrays of the EPI variants are sized for 16 lines per workgroup: P = 16 only)
     if (const int zwl = (a.out_zstride % 2 == 0 && (EPI == 0 || nz != 256)) ? zw_lines_of(nz, nlines) : 0) {
-        const float2 *twH = twiddles(nz / 2);
-        const float2 *twN = twiddles(nz);
-        if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-        const dim3 grid((unsigned)(nlines / zwl));
-        if (nz == 256)
-            hipLaunchKernelGGL((zw_c2r_kernel<16, EPI, 8>), grid, dim3(kBlock), 0, stream, a, twH, twN);
-        else if (nz == 512)
-            hipLaunchKernelGGL((zw_c2r_kernel<16, EPI, 16>), grid, dim3(kBlock), 0, stream, a, twH, twN);
-        else
-            hipLaunchKernelGGL((zw_c2r_kernel<32, EPI, 16>), grid, dim3(kBlock), 0, stream, a, twH, twN);
-        LAUNCH_CHECK();
-        return 0;
+        auto fn = zw_c2r_kernel<16, EPI, 8>;  // 256-point lines
+        if (nz != 256) fn = (nz == 512) ? zw_c2r_kernel<16, EPI, 16> : zw_c2r_kernel<32, EPI, 16>;
+        return launch_z(fn, nz, nlines / zwl, kBlock, 0, a, stream);
     }
     if constexpr (EPI == 6 || EPI == 7 || EPI == 9 || EPI == 10) {
         c21hip_set_error("pass Z with the deferred / banded barrier (EPI 6, 7, 9) or the extrema alone (10) needs the wave-level kernel");
@@ -4315,19 +4283,46 @@ extern "C" int c21hip_split_r2c(const float *real_in, long in_zstride, float *sp
     return dispatch_line_pass<-1>(nx, a, 0, stream);
 }
 
-// Pass Z: split_work -> real rows of out_zstride floats.
-extern "C" int c21hip_split_z_c2r(const float *split_work, float *real_out, long out_zstride,
-                                  int nx, int ny, int nz, void *stream) {
-    const long nlines = (long)nx * ny;
+// ---- one-grid pass Z: the pieces its exported launchers share
+// What every ZPassArgs starts from: the spectrum's two blocks, the line mapping, real rows `out` of out_zstride
+// floats (the launchers that store nothing dense still pass the stride their kernel indexes with).
+static ZPassArgs z_pass_base(const float *split_work, float *out, long out_zstride, int nx, int ny, int nz) {
     ZPassArgs z{};
     z.ny = ny;
     z.lb = split_xb_log2(nx);
     z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out = real_out;
+    z.nyq = z.main + (long)nx * ny * (nz / 2);
+    z.out = out;
     z.out_zstride = out_zstride;
     z.out_scale = 1.0f;
-    return dispatch_z_c2r(nz, z, nlines, (hipStream_t)stream);
+    return z;
+}
+// 1 / (growthf sqrt(2 (sigma_min^2 - sigma_max^2))) of the closed-form f_coll, -1 where the sigmas are equal
+// (hmf.c:1221-1232: float sigmas, float products, double sqrt)
+static int fgtrm_sig(double growthf, double sigma_min, double sigma_max, double *sig) {
+    const float ss = (float)sigma_min, sl = (float)sigma_max;
+    if (sl > ss) {
+        c21hip_set_error("FgtrM requested in a region where M_min > M_max (sigma %g > %g)", (double)sl, (double)ss);
+        return C21CM_VALUE_ERROR;
+    }
+    *sig = (sl != ss) ? 1.0 / ((double)(float)growthf * (sqrt(2.) * sqrt((double)(ss * ss - sl * sl)))) : -1.;
+    return 0;
+}
+// out[0..] = {min, max[, sum]} of the nb workgroup partials a pass left as arrays of minima, maxima[, sums];
+// the stage areas of the two-level reductions lie beyond the arrays
+static int reduce_extrema(double *partials, int nb, bool with_sum, double *out, void *stream) {
+    double *stage = partials + (with_sum ? 3 : 2) * (size_t)nb;
+    int st = c21hip_reduce_op(partials, nb, 1, stage, out, stream);
+    if (!st) st = c21hip_reduce_op(partials + nb, nb, 2, stage + nb / 1024 + 2, out + 1, stream);
+    if (!st && with_sum) st = c21hip_reduce_op(partials + 2 * (size_t)nb, nb, 0, stage, out + 2, stream);
+    return st;
+}
+
+// Pass Z: split_work -> real rows of out_zstride floats.
+extern "C" int c21hip_split_z_c2r(const float *split_work, float *real_out, long out_zstride,
+                                  int nx, int ny, int nz, void *stream) {
+    return dispatch_z_c2r(nz, z_pass_base(split_work, real_out, out_zstride, nx, ny, nz), (long)nx * ny,
+                          (hipStream_t)stream);
 }
 
 // Pass Z with the stored value divided by `divisor` (0: no division): the "/ VOLUME" of the
@@ -4343,18 +4338,11 @@ extern "C" int c21hip_split_z_c2r_div(const float *split_work, float *real_out, 
 extern "C" int c21hip_split_z_c2r_out(const float *split_work, float *real_out, long out_zstride,
                                       int nx, int ny, int nz, float scale, float divisor,
                                       int floor_density, void *stream) {
-    const long nlines = (long)nx * ny;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out = real_out;
-    z.out_zstride = out_zstride;
+    ZPassArgs z = z_pass_base(split_work, real_out, out_zstride, nx, ny, nz);
     z.out_scale = scale;
     z.out_div = divisor;
     z.out_floor = floor_density;
-    return dispatch_z_c2r(nz, z, nlines, (hipStream_t)stream);
+    return dispatch_z_c2r(nz, z, (long)nx * ny, (hipStream_t)stream);
 }
 
 extern "C" int c21hip_split_xblock_log2(int nx) { return split_xb_log2(nx); }
@@ -4366,21 +4354,11 @@ extern "C" int c21hip_split_z_c2r_minmax(const float *split_work, float *real_ou
                                          double *partials, double *minmax_out, void *stream) {
     const long nlines = (long)nx * ny;
     const int nb = (int)(nlines / LZ_PLAIN);
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out = real_out;
-    z.out_zstride = out_zstride;
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(split_work, real_out, out_zstride, nx, ny, nz);
     z.p0 = partials;
     z.p1 = partials + nb;
-    int st = dispatch_z_c2r<1>(nz, z, nlines, (hipStream_t)stream);
-    if (st) return st;
-    double *stage = partials + 2 * (size_t)nb;  // beyond both partial arrays
-    if ((st = c21hip_reduce_op(z.p0, nb, 1, stage, minmax_out, stream))) return st;
-    return c21hip_reduce_op(z.p1, nb, 2, stage + nb / 1024 + 2, minmax_out + 1, stream);
+    const int st = dispatch_z_c2r<1>(nz, z, nlines, (hipStream_t)stream);
+    return st ? st : reduce_extrema(partials, nb, false, minmax_out, stream);
 }
 
 // ... the extrema ALONE (EPI 10: nothing is stored), and the table sweep of the same spectrum with the banded
@@ -4399,13 +4377,7 @@ extern "C" int c21hip_split_z_minmax_only(const float *split_work, int nx, int n
     }
     const long nlines = (long)nx * ny;
     const int nb = (int)(nlines / LZ_PLAIN);
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out_zstride = nz;
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(split_work, nullptr, nz, nx, ny, nz);
     z.p0 = partials;
     z.p1 = partials + nb;
     int st;
@@ -4413,10 +4385,7 @@ extern "C" int c21hip_split_z_minmax_only(const float *split_work, int nx, int n
         KTimeScope kt(13, (hipStream_t)stream);  // kind 13: one-grid pass Z, extrema only
         st = dispatch_z_c2r<10>(nz, z, nlines, (hipStream_t)stream);
     }
-    if (st) return st;
-    double *stage = partials + 2 * (size_t)nb;  // beyond both partial arrays
-    if ((st = c21hip_reduce_op(z.p0, nb, 1, stage, minmax_out, stream))) return st;
-    return c21hip_reduce_op(z.p1, nb, 2, stage + nb / 1024 + 2, minmax_out + 1, stream);
+    return st ? st : reduce_extrema(partials, nb, false, minmax_out, stream);
 }
 // nx*ny/16 partial sums of f_coll are left in `partials` for c21hip_eul_band (as the closed form's EPI 7 leaves them)
 extern "C" int c21hip_split_z_fcoll_table_band(const float *split_work, float *f_pend, const double *band_dev,
@@ -4429,14 +4398,7 @@ extern "C" int c21hip_split_z_fcoll_table_band(const float *split_work, float *f
         c21hip_set_error("pass Z with the table sweep and the banded barrier: unsupported box, mode or radius index");
         return C21CM_VALUE_ERROR;
     }
-    const long nlines = (long)nx * ny;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out_zstride = nz;
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(split_work, nullptr, nz, nx, ny, nz);
     z.f_out = f_pend;
     z.band = band_dev;
     z.mean_dev = thr_prev_dev;
@@ -4449,7 +4411,7 @@ extern "C" int c21hip_split_z_fcoll_table_band(const float *split_work, float *f
     z.tab_width = tab_width;
     z.tab_mode = mode;
     KTimeScope kt(14, (hipStream_t)stream);  // kind 14: one-grid pass Z + table f_coll + banded barrier
-    return dispatch_z_c2r<9>(nz, z, nlines, (hipStream_t)stream);
+    return dispatch_z_c2r<9>(nz, z, (long)nx * ny, (hipStream_t)stream);
 }
 
 // Pass Z with the floor-and-scale store of the spin-temperature filter tables
@@ -4462,27 +4424,15 @@ extern "C" int c21hip_split_z_c2r_stats(const float *split_work, float *real_out
                                         double *stats_out, void *stream) {
     const long nlines = (long)nx * ny;
     const int nb = (int)(nlines / LZ_PLAIN);
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out = real_out;
-    z.out_zstride = out_zstride;
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(split_work, real_out, out_zstride, nx, ny, nz);
     z.p0 = partials;
     z.p1 = partials + nb;
     z.p2 = partials + 2 * (size_t)nb;
     z.min_value = min_value;
     z.const_factor = const_factor;
-    int st = dispatch_z_c2r<3>(nz, z, nlines, (hipStream_t)stream);
-    if (st) return st;
-    if (!stats_out) return 0;  // deferred: c21hip_batched_stats reduces several windows at once
-    double *stage = partials + 3 * (size_t)nb;
-    if ((st = c21hip_reduce_op(z.p0, nb, 1, stage, stats_out, stream))) return st;
-    if ((st = c21hip_reduce_op(z.p1, nb, 2, stage + nb / 1024 + 2, stats_out + 1, stream)))
-        return st;
-    return c21hip_reduce_op(z.p2, nb, 0, stage, stats_out + 2, stream);
+    const int st = dispatch_z_c2r<3>(nz, z, nlines, (hipStream_t)stream);
+    if (st || !stats_out) return st;  // stats_out NULL: c21hip_batched_stats reduces several windows at once
+    return reduce_extrema(partials, nb, true, stats_out, stream);
 }
 
 // Pass Z of the filtered density fused with the CONST-ION-EFF closed-form f_coll(delta_R):
@@ -4492,28 +4442,12 @@ extern "C" int c21hip_split_z_fcoll_erfc(const float *split_work, float *nion_de
                                          double sigma_max, double delta_c, double *partials,
                                          double *sum_out, void *stream) {
     const long nlines = (long)nx * ny;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(split_work, nullptr, 0, nx, ny, nz);
     z.f_out = nion_dense;
     z.p0 = partials;
     z.delta_c = delta_c;
-    z.sig = -1.;
-    {
-        // hmf.c:1221-1232: float sigmas, float products, double sqrt
-        const float ss = (float)sigma_min, sl = (float)sigma_max;
-        if (sl > ss) {
-            c21hip_set_error("FgtrM requested in a region where M_min > M_max (sigma %g > %g)",
-                             (double)sl, (double)ss);
-            return C21CM_VALUE_ERROR;
-        }
-        if (sl != ss)
-            z.sig = 1.0 / ((double)(float)growthf * (sqrt(2.) * sqrt((double)(ss * ss - sl * sl))));
-    }
-    int st;
+    int st = fgtrm_sig(growthf, sigma_min, sigma_max, &z.sig);
+    if (st) return st;
     {
         KTimeScope kt(12, (hipStream_t)stream);
         st = dispatch_z_c2r<2>(nz, z, nlines, (hipStream_t)stream);
@@ -4541,12 +4475,7 @@ extern "C" int c21hip_split_z_fcoll_erfc_mask(const float *split_work, float *ni
         return C21CM_VALUE_ERROR;
     }
     const long nlines = (long)nx * ny;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(split_work, nullptr, 0, nx, ny, nz);
     z.f_out = nion_dense;
     z.f_prev = nion_prev;
     z.mean_dev = mean_prev_dev;
@@ -4559,19 +4488,8 @@ extern "C" int c21hip_split_z_fcoll_erfc_mask(const float *split_work, float *ni
     z.ion_eff = ion_eff;
     z.p0 = partials;
     z.delta_c = delta_c;
-    z.sig = -1.;
-    {
-        const float ss = (float)sigma_min, sl = (float)sigma_max;  // hmf.c:1221-1232, as above
-        if (sl > ss) {
-            c21hip_set_error("FgtrM requested in a region where M_min > M_max (sigma %g > %g)",
-                             (double)sl, (double)ss);
-            return C21CM_VALUE_ERROR;
-        }
-        if (sl != ss)
-            z.sig = 1.0 / ((double)(float)growthf * (sqrt(2.) * sqrt((double)(ss * ss - sl * sl))));
-    }
-    int st = dispatch_z_c2r<6>(nz, z, nlines, (hipStream_t)stream);
-    if (st) return st;
+    int st = fgtrm_sig(growthf, sigma_min, sigma_max, &z.sig);
+    if (st || (st = dispatch_z_c2r<6>(nz, z, nlines, (hipStream_t)stream))) return st;
     return c21hip_reduce_sum(partials, (int)(nlines / LZ_PLAIN), sum_out, stream);
 }
 
@@ -4590,12 +4508,7 @@ extern "C" int c21hip_split_z_fcoll_erfc_band(const float *split_work, float *f_
         return C21CM_VALUE_ERROR;
     }
     const long nlines = (long)nx * ny;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(split_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(split_work, nullptr, 0, nx, ny, nz);
     z.f_out = f_pend;
     z.band = band_dev;
     z.mean_dev = thr_prev_dev;
@@ -4604,18 +4517,8 @@ extern "C" int c21hip_split_z_fcoll_erfc_band(const float *split_work, float *f_
     z.r_prev = r_prev;
     z.p0 = partials;
     z.delta_c = delta_c;
-    z.sig = -1.;
-    {
-        const float ss = (float)sigma_min, sl = (float)sigma_max;  // hmf.c:1221-1232, as above
-        if (sl > ss) {
-            c21hip_set_error("FgtrM requested in a region where M_min > M_max (sigma %g > %g)",
-                             (double)sl, (double)ss);
-            return C21CM_VALUE_ERROR;
-        }
-        if (sl != ss)
-            z.sig = 1.0 / ((double)(float)growthf * (sqrt(2.) * sqrt((double)(ss * ss - sl * sl))));
-    }
-    int st;
+    int st = fgtrm_sig(growthf, sigma_min, sigma_max, &z.sig);
+    if (st) return st;
     {
         KTimeScope kt(12, (hipStream_t)stream);  // kind 12: one-grid pass Z + closed-form f_coll (+ banded barrier)
         st = dispatch_z_c2r<7>(nz, z, nlines, (hipStream_t)stream);
@@ -4635,216 +4538,130 @@ extern "C" int c21hip_split_filter_c2r(const float *split_src, float *split_work
     return c21hip_split_z_c2r(split_work, real_out, out_zstride, nx, ny, nz, stream);
 }
 
-// Fused pass Z of the density and emissivity grids + f_coll sum + ionisation barrier
-// (Lagrangian source grids, radius index > 0).  partials: nx*ny/8 doubles.
-extern "C" int c21hip_split_z_ionise_stars(const float *delta_work, const float *stars_work,
-                                           unsigned char *first_cross, double *partials,
-                                           double *sum_out, int nx, int ny, int nz, int r_index,
-                                           double rhocrit_omb, double ion_eff, int mass_dep_zeta,
-                                           double f_limit, void *stream) {
-    return c21hip_split_z_ionise_stars_xe(delta_work, stars_work, NULL, first_cross, partials,
-                                          sum_out, nx, ny, nz, r_index, rhocrit_omb, ion_eff,
-                                          mass_dep_zeta, f_limit, stream);
+// ---- the fused ionise pass Z (c21hip_z_ionise_desc): which boxes each request is served on, and the entry.
+// Every predicate is z_fused_select's answer plus what its route needs beyond the fused kernel.
+static bool z_fused_serves(int nx, int ny, int nz, ZFusedWant w) {
+    return z_fused_select(nz, (long)nx * ny, w, false).fn != nullptr;
 }
-
-// The same with the filtered x_e spectrum of a spin-temperature run as a third grid
-// (xe_work == NULL: two grids).  512- and 1024-point z-lines only.
-static int z_ionise_stars(const float *delta_work, const float *stars_work, const float *xe_work,
-                          unsigned char *first_cross, unsigned *cross_bits, double *partials,
-                          double *sum_out, int nx, int ny, int nz, int r_index, double rhocrit_omb,
-                          double ion_eff, int mass_dep_zeta, double f_limit, void *stream) {
-    const long nlines = (long)nx * ny;
-    ZFusedArgs a{};
-    a.ny = ny;
-    a.lb = split_xb_log2(nx);
-    a.d_main = reinterpret_cast<const float2 *>(delta_work);
-    a.d_nyq = a.d_main + nlines * (nz / 2);
-    a.s_main = reinterpret_cast<const float2 *>(stars_work);
-    a.s_nyq = a.s_main + nlines * (nz / 2);
-    if (xe_work) {
-        a.x_main = reinterpret_cast<const float2 *>(xe_work);
-        a.x_nyq = a.x_main + nlines * (nz / 2);
-    }
-    a.first_cross = first_cross;
-    a.cross_bits = cross_bits;
-    a.partials = partials;
-    a.rhocrit_omb = rhocrit_omb;
-    a.ion_eff = ion_eff;
-    a.f_limit = f_limit;
-    a.mass_dep_zeta = mass_dep_zeta;
-    a.r_index = r_index;
-    static const int store_all = [] {
-        const char *e = getenv("C21CM_MASK_STORE_ALL");
-        return (e && e[0] == '1') ? 1 : 0;
-    }();
-    a.store_all = store_all;
-    static const int reverse = [] {
-        const char *e = getenv("C21CM_ZREV");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    a.reverse = reverse;
-    int n_partials = 0;
-    int st = dispatch_z_fused(nz, a, nlines, (hipStream_t)stream, &n_partials);
-    if (st) return st;
-    if (!sum_out) return 0;  // deferred: the caller reduces the partials of all radii at once
-    return c21hip_reduce_sum(partials, n_partials, sum_out, stream);
+// 1: the fused pass Z takes an x_e grid here (whole workgroups of the 256- / 512- / 1024-point wave kernels)
+extern "C" int c21hip_z_ionise_xe_supported(int nx, int ny, int nz) {
+    return zw_lines_of(nz, (long)nx * ny) != 0 && z_fused_serves(nx, ny, nz, {true, false, false, false});
 }
-
-extern "C" int c21hip_split_z_ionise_stars_xe(const float *delta_work, const float *stars_work,
-                                              const float *xe_work, unsigned char *first_cross,
-                                              double *partials, double *sum_out, int nx, int ny,
-                                              int nz, int r_index, double rhocrit_omb,
-                                              double ion_eff, int mass_dep_zeta, double f_limit,
-                                              void *stream) {
-    return z_ionise_stars(delta_work, stars_work, xe_work, first_cross, nullptr, partials, sum_out, nx,
-                          ny, nz, r_index, rhocrit_omb, ion_eff, mass_dep_zeta, f_limit, stream);
-}
-
-// Does the two-grid fused pass Z of this grid write crossing bits (c21hip_split_z_ionise_stars_bits)?
-// 512-point z-lines on the wave-level kernel; C21CM_CROSS_BITS=0 keeps the uint8 mask.
+// 1: the two-grid fused pass Z of this grid writes crossing bits: 512-point z-lines on the wave-level kernel;
+// C21CM_CROSS_BITS=0 keeps the uint8 mask
 extern "C" int c21hip_z_cross_bits_supported(int nx, int ny, int nz) {
     static const int on = [] {
         const char *e = getenv("C21CM_CROSS_BITS");
         return (e && e[0] == '0') ? 0 : 1;
     }();
-    return on && nz == 512 && zw_lines_of(nz, (long)nx * ny) != 0;
+    return on && z_fused_serves(nx, ny, nz, {false, false, false, true});
+}
+// 1: the recombination barrier; its route follows every radius with c21hip_split_z_sfr_gamma12 (nz <= 512) ...
+extern "C" int c21hip_z_ionise_recomb_supported(int nx, int ny, int nz) {
+    return nz <= 512 && z_fused_serves(nx, ny, nz, {false, true, false, false});
+}
+// ... also with a third spectrum, the x_e grid of a spin-temperature run or the filtered N_rec (16 points per
+// lane: 256- / 512-point z-lines) ...
+extern "C" int c21hip_z_ionise_recomb_xe_supported(int nx, int ny, int nz) {
+    return nz <= 512 && z_fused_serves(nx, ny, nz, {true, true, false, false});
+}
+// ... and with both (four spectra, 512-point z-lines)
+extern "C" int c21hip_z_ionise_recomb_xe_nrec_supported(int nx, int ny, int nz) {
+    return nz <= 512 && z_fused_serves(nx, ny, nz, {true, true, true, false});
+}
+// workgroup partials the fused pass Z writes for an nx x ny x nz grid
+extern "C" int c21hip_z_ionise_partials(int nx, int ny, int nz) {
+    const long nlines = (long)nx * ny;
+    return (int)(nlines / z_fused_select(nz, nlines, {}, false).lines);
 }
 
-// The two-grid fused pass Z with the barrier's outcome as this radius' plane of crossing bits
-// (cross_plane: nx*ny*nz/8 bytes, every word written, nothing read; ZFusedArgs::cross_bits) instead
-// of the read-modify-write of the uint8 mask.  c21hip_resolve_crossings turns the planes into the mask.
-extern "C" int c21hip_split_z_ionise_stars_bits(const float *delta_work, const float *stars_work,
-                                                unsigned *cross_plane, double *partials,
-                                                double *sum_out, int nx, int ny, int nz, int r_index,
-                                                double rhocrit_omb, double ion_eff,
-                                                int mass_dep_zeta, double f_limit, void *stream) {
-    if (!cross_plane || !c21hip_z_cross_bits_supported(nx, ny, nz)) {
+// Fused pass Z of the filtered density and emissivity spectra (+ x_e, + the filtered N_rec): sum(stars) partials
+// and the ionisation barrier of radius index r_index > 0 in one kernel; see c21hip_z_ionise_desc (c21hip.h).
+// reference: IonisationBox.c:634-638,821-837,1054-1151
+extern "C" int c21hip_split_z_ionise(const c21hip_z_ionise_desc *d, void *stream) {
+    if (!d || d->size != sizeof(*d)) {
+        c21hip_set_error("fused pass Z: the descriptor's size member is not sizeof(c21hip_z_ionise_desc)");
+        return C21CM_VALUE_ERROR;
+    }
+    if (d->cross_plane && !c21hip_z_cross_bits_supported(d->nx, d->ny, d->nz)) {
         c21hip_set_error("fused pass Z: crossing bits are not available for this grid");
         return C21CM_VALUE_ERROR;
     }
-    return z_ionise_stars(delta_work, stars_work, nullptr, nullptr, cross_plane, partials, sum_out, nx,
-                          ny, nz, r_index, rhocrit_omb, ion_eff, mass_dep_zeta, f_limit, stream);
+    const long nlines = (long)d->nx * d->ny;
+    const long n_main = nlines * (d->nz / 2);  // float2 of a spectrum's main block; its Nyquist plane follows
+    const ZFusedWant w{d->xe_work != nullptr, d->recomb != 0, d->recomb && d->nrec_work, d->cross_plane != nullptr};
+    ZFusedArgs a{};
+    a.ny = d->ny;
+    a.lb = split_xb_log2(d->nx);
+    a.d_main = reinterpret_cast<const float2 *>(d->delta_work);
+    a.d_nyq = a.d_main + n_main;
+    a.s_main = reinterpret_cast<const float2 *>(d->stars_work);
+    a.s_nyq = a.s_main + n_main;
+    // the third line of the barrier kernel: x_e, or the filtered N_rec where there is no x_e grid (x_is_nrec);
+    // with both, the filtered N_rec is a fourth spectrum (n_main)
+    const float *third = w.xe ? d->xe_work : (w.nrec ? d->nrec_work : nullptr);
+    if (third) {
+        a.x_main = reinterpret_cast<const float2 *>(third);
+        a.x_nyq = a.x_main + n_main;
+    }
+    if (w.xe && w.nrec) {
+        a.n_main = reinterpret_cast<const float2 *>(d->nrec_work);
+        a.n_nyq = a.n_main + n_main;
+    } else
+        a.x_is_nrec = w.nrec;
+    a.first_cross = d->first_cross;
+    a.cross_bits = d->cross_plane;
+    a.partials = d->partials;
+    a.rhocrit_omb = d->rhocrit_omb;
+    a.ion_eff = d->ion_eff;
+    a.f_limit = d->f_limit;
+    a.mass_dep_zeta = d->mass_dep_zeta;
+    a.r_index = d->r_index;
+    if (w.rc) {  // walks the lines backwards, stores first crossings only, never reduces
+#ifdef C21CM_DIAG_BUILD  // (make EXTRA=-DC21CM_DIAG_BUILD: timing diagnostics that change results)
+        a.rc = getenv("C21CM_DIAG_RC_NOSTORE") ? 2 : 1;  // (2: no Gamma_12 stores)
+#else
+        a.rc = 1;
+#endif
+        a.g12 = d->g12;
+        if (!w.nrec) {  // the cell's own previous N_rec (NULL: the homogeneous model's one number)
+            a.nrec = d->nrec;
+            a.rec0 = d->rec0;
+        }
+        a.reverse = 1;
+    } else {
+        static const int store_all = [] {
+            const char *e = getenv("C21CM_MASK_STORE_ALL");
+            return (e && e[0] == '1') ? 1 : 0;
+        }();
+        a.store_all = store_all;
+        static const int reverse = [] {
+            const char *e = getenv("C21CM_ZREV");
+            return (e && e[0] == '0') ? 0 : 1;
+        }();
+        a.reverse = reverse;
+    }
+    int n_partials = 0;
+    const int st = dispatch_z_fused(d->nz, a, w, nlines, (hipStream_t)stream, &n_partials);
+    if (st || w.rc || !d->sum_out) return st;  // sum_out NULL: the caller reduces the partials of all radii at once
+    return c21hip_reduce_sum(d->partials, n_partials, d->sum_out, stream);
 }
 
-// The same with a recombination model (CELL_RECOMB): sfr_work = passes X, Y of HaloBox.whalo_sfr;
-// nrec: the previous box's cumulative_recombinations (dense; NULL: homogeneous, rec0), g12: dense
-// Gamma_12 grid written at first crossings.
-extern "C" int c21hip_split_z_ionise_recomb_xe(const float *delta_work, const float *stars_work,
-                                               const float *xe_work, const float *nrec, double rec0,
-                                               float *g12, unsigned char *first_cross, double *partials,
-                                               int nx, int ny, int nz, int r_index, double rhocrit_omb,
-                                               double ion_eff, int mass_dep_zeta, double f_limit,
-                                               void *stream);
-extern "C" int c21hip_split_z_ionise_recomb(const float *delta_work, const float *stars_work,
-                                            const float *nrec, double rec0, float *g12,
-                                            unsigned char *first_cross,
-                                            double *partials, int nx, int ny, int nz, int r_index,
-                                            double rhocrit_omb, double ion_eff, int mass_dep_zeta,
-                                            double f_limit, void *stream) {
-    return c21hip_split_z_ionise_recomb_xe(delta_work, stars_work, nullptr, nrec, rec0, g12, first_cross,
-                                           partials, nx, ny, nz, r_index, rhocrit_omb, ion_eff,
-                                           mass_dep_zeta, f_limit, stream);
-}
-// ... with the filtered x_e spectrum of a spin-temperature run as a third line of the barrier kernel
-// (xe_work == NULL: none): f zeta > (1 - x_e)(1 + rec), IonisationBox.c:1084-1118
-extern "C" int c21hip_split_z_ionise_recomb_xe(const float *delta_work, const float *stars_work,
-                                               const float *xe_work, const float *nrec, double rec0,
-                                               float *g12, unsigned char *first_cross, double *partials,
-                                               int nx, int ny, int nz, int r_index, double rhocrit_omb,
-                                               double ion_eff, int mass_dep_zeta, double f_limit,
-                                               void *stream) {
-    const long nlines = (long)nx * ny;
-    ZFusedArgs a{};
-    if (xe_work) {
-        a.x_main = reinterpret_cast<const float2 *>(xe_work);
-        a.x_nyq = a.x_main + nlines * (nz / 2);
-    }
-    a.ny = ny;
-    a.lb = split_xb_log2(nx);
-    a.d_main = reinterpret_cast<const float2 *>(delta_work);
-    a.d_nyq = a.d_main + nlines * (nz / 2);
-    a.s_main = reinterpret_cast<const float2 *>(stars_work);
-    a.s_nyq = a.s_main + nlines * (nz / 2);
-    a.first_cross = first_cross;
-    a.partials = partials;
-    a.rhocrit_omb = rhocrit_omb;
-    a.ion_eff = ion_eff;
-    a.f_limit = f_limit;
-    a.mass_dep_zeta = mass_dep_zeta;
-    a.r_index = r_index;
-#ifdef C21CM_DIAG_BUILD  // (make EXTRA=-DC21CM_DIAG_BUILD: timing diagnostics that change results)
-    a.rc = getenv("C21CM_DIAG_RC_NOSTORE") ? 2 : 1;  // (2: no Gamma_12 stores)
-#else
-    a.rc = 1;
-#endif
-    a.nrec = nrec;
-    a.rec0 = rec0;
-    a.g12 = g12;
-    a.reverse = 1;
-    int n_partials = 0;
-    return dispatch_z_fused(nz, a, nlines, (hipStream_t)stream, &n_partials);
-}
-// ... with the previous snapshot's N_rec FILTERED at this radius (CELL_RECOMB = false) as the third line
-// instead of a dense per-cell N_rec: f zeta > 1 + max(N_rec(R), 0) / (1 + delta_R)
-extern "C" int c21hip_split_z_ionise_recomb_nrec(const float *delta_work, const float *stars_work,
-                                                 const float *nrec_work, float *g12,
-                                                 unsigned char *first_cross, double *partials, int nx,
-                                                 int ny, int nz, int r_index, double rhocrit_omb,
-                                                 double ion_eff, int mass_dep_zeta, double f_limit,
-                                                 void *stream) {
-    const long nlines = (long)nx * ny;
-    ZFusedArgs a{};
-    a.x_main = reinterpret_cast<const float2 *>(nrec_work);
-    a.x_nyq = a.x_main + nlines * (nz / 2);
-    a.x_is_nrec = 1;
-    a.ny = ny;
-    a.lb = split_xb_log2(nx);
-    a.d_main = reinterpret_cast<const float2 *>(delta_work);
-    a.d_nyq = a.d_main + nlines * (nz / 2);
-    a.s_main = reinterpret_cast<const float2 *>(stars_work);
-    a.s_nyq = a.s_main + nlines * (nz / 2);
-    a.first_cross = first_cross;
-    a.partials = partials;
-    a.rhocrit_omb = rhocrit_omb;
-    a.ion_eff = ion_eff;
-    a.f_limit = f_limit;
-    a.mass_dep_zeta = mass_dep_zeta;
-    a.r_index = r_index;
-    a.rc = 1;
-    a.g12 = g12;
-    a.reverse = 1;
-    int n_partials = 0;
-    return dispatch_z_fused(nz, a, nlines, (hipStream_t)stream, &n_partials);
-}
 // Pass Z of the filtered whalo_sfr of radius r_index: where the first-crossing mask holds r_index,
-// g12 (which holds delta_R there, left by c21hip_split_z_ionise_recomb) becomes Gamma_12.
+// g12 (which holds delta_R there, left by c21hip_split_z_ionise with `recomb`) becomes Gamma_12.
 extern "C" int c21hip_split_z_sfr_gamma12(const float *sfr_work, const unsigned char *first_cross,
                                           float *g12, int nx, int ny, int nz, int r_index,
                                           double g12_scale, void *stream) {
     const long nlines = (long)nx * ny;
     const int zwl = zw_lines_of(nz, nlines);
     if (!zwl || zw3_selected(nz, nlines) || nz > 512) return C21CM_VALUE_ERROR;
-    const float2 *twH = twiddles(nz / 2);
-    const float2 *twN = twiddles(nz);
-    if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(sfr_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out = g12;
-    z.out_zstride = nz;
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(sfr_work, g12, nz, nx, ny, nz);
     z.const_factor = g12_scale;
     z.mask = first_cross;
     z.r_index = r_index;
-    const dim3 grid((unsigned)(nlines / zwl));
-    if (nz == 256)
-        hipLaunchKernelGGL((zw_c2r_kernel<16, 4, 8>), grid, dim3(kBlock), 0, (hipStream_t)stream, z, twH, twN);
-    else
-        hipLaunchKernelGGL((zw_c2r_kernel<16, 4, 16>), grid, dim3(kBlock), 0, (hipStream_t)stream, z, twH, twN);
-    LAUNCH_CHECK();
-    return 0;
+    // (<16, 4, 8> on 256-point lines: an instantiation dispatch_z_c2r does not pick)
+    return launch_z(nz == 256 ? zw_c2r_kernel<16, 4, 8> : zw_c2r_kernel<16, 4, 16>, nz, nlines / zwl, kBlock, 0, z,
+                    (hipStream_t)stream);
 }
 // Pass Z of the filtered x_e grid of an Eulerian source model with the barrier of the radius fused
 // in (EPI 5): f_coll zeta > 1 - x_e(R) into the first-crossing mask; x_e(R) is not written.
@@ -4859,16 +4676,7 @@ extern "C" int c21hip_split_z_xe_mask(const float *xe_work, const float *nion_de
     if (!c21hip_z_xe_mask_supported(nx, ny, nz)) return C21CM_VALUE_ERROR;
     const long nlines = (long)nx * ny;
     const int zwl = zw_lines_of(nz, nlines);
-    const float2 *twH = twiddles(nz / 2);
-    const float2 *twN = twiddles(nz);
-    if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(xe_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out_zstride = nz;
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(xe_work, nullptr, nz, nx, ny, nz);
     z.f_out = const_cast<float *>(nion_dense);
     z.mask_rw = first_cross;
     z.mean_dev = mean_dev;
@@ -4879,15 +4687,8 @@ extern "C" int c21hip_split_z_xe_mask(const float *xe_work, const float *nion_de
     z.ion_eff = ion_eff;
     z.r_index = r_index;
     KTimeScope kt(11, (hipStream_t)stream);
-    const dim3 grid((unsigned)(nlines / zwl));
-    if (nz == 256)
-        hipLaunchKernelGGL((zw_c2r_kernel<16, 5, 8>), grid, dim3(kBlock), 0, (hipStream_t)stream, z, twH, twN);
-    else if (nz == 512)
-        hipLaunchKernelGGL((zw_c2r_kernel<16, 5, 16>), grid, dim3(kBlock), 0, (hipStream_t)stream, z, twH, twN);
-    else
-        return C21CM_VALUE_ERROR;
-    LAUNCH_CHECK();
-    return 0;
+    return launch_z(nz == 256 ? zw_c2r_kernel<16, 5, 8> : zw_c2r_kernel<16, 5, 16>, nz, nlines / zwl, kBlock, 0, z,
+                    (hipStream_t)stream);
 }
 // Eulerian table models with an x_e grid, banded barrier (EPI 8): pass Z of the filtered x_e + the table
 // sweep of the radius' dense filtered density + the barrier, in one launch.  band_dev = [mf_lo, mf_hi] of
@@ -4911,16 +4712,7 @@ extern "C" int c21hip_split_z_xe_fcoll_band(const float *xe_work, const float *d
     }
     const long nlines = (long)nx * ny;
     const int zwl = zw_lines_of(nz, nlines);
-    const float2 *twH = twiddles(nz / 2);
-    const float2 *twN = twiddles(nz);
-    if (!twH || !twN) return C21CM_MEMORY_ALLOC_ERROR;
-    ZPassArgs z{};
-    z.ny = ny;
-    z.lb = split_xb_log2(nx);
-    z.main = reinterpret_cast<const float2 *>(xe_work);
-    z.nyq = z.main + nlines * (nz / 2);
-    z.out_zstride = delta_zstride;
-    z.out_scale = 1.0f;
+    ZPassArgs z = z_pass_base(xe_work, nullptr, delta_zstride, nx, ny, nz);
     z.delta_fil = delta_fil;
     z.table = table_dev;
     z.tab_min = tab_min;
@@ -4939,65 +4731,7 @@ extern "C" int c21hip_split_z_xe_fcoll_band(const float *xe_work, const float *d
     z.p0 = partials;
     KTimeScope kt(11, (hipStream_t)stream);
     z.reverse = zw_reverse_default();
-    hipLaunchKernelGGL((zw_c2r_kernel<16, 8, 16>), dim3((unsigned)(nlines / zwl)), dim3(kBlock), 0,
-                       (hipStream_t)stream, z, twH, twN);
-    LAUNCH_CHECK();
-    return 0;
-}
-// ... and with BOTH: the x_e grid of a spin-temperature run and the filtered N_rec of CELL_RECOMB = false
-// (four spectra; 512-point z-lines)
-extern "C" int c21hip_split_z_ionise_recomb_xe_nrec(const float *delta_work, const float *stars_work,
-                                                    const float *xe_work, const float *nrec_work, float *g12,
-                                                    unsigned char *first_cross, double *partials, int nx,
-                                                    int ny, int nz, int r_index, double rhocrit_omb,
-                                                    double ion_eff, int mass_dep_zeta, double f_limit,
-                                                    void *stream) {
-    if (nz != 512) {
-        c21hip_set_error("fused pass Z with an x_e grid and a filtered N_rec: 512-point z-lines only");
-        return C21CM_VALUE_ERROR;
-    }
-    const long nlines = (long)nx * ny;
-    ZFusedArgs a{};
-    a.x_main = reinterpret_cast<const float2 *>(xe_work);
-    a.x_nyq = a.x_main + nlines * (nz / 2);
-    a.n_main = reinterpret_cast<const float2 *>(nrec_work);
-    a.n_nyq = a.n_main + nlines * (nz / 2);
-    a.ny = ny;
-    a.lb = split_xb_log2(nx);
-    a.d_main = reinterpret_cast<const float2 *>(delta_work);
-    a.d_nyq = a.d_main + nlines * (nz / 2);
-    a.s_main = reinterpret_cast<const float2 *>(stars_work);
-    a.s_nyq = a.s_main + nlines * (nz / 2);
-    a.first_cross = first_cross;
-    a.partials = partials;
-    a.rhocrit_omb = rhocrit_omb;
-    a.ion_eff = ion_eff;
-    a.f_limit = f_limit;
-    a.mass_dep_zeta = mass_dep_zeta;
-    a.r_index = r_index;
-    a.rc = 1;
-    a.g12 = g12;
-    a.reverse = 1;
-    int n_partials = 0;
-    return dispatch_z_fused(nz, a, nlines, (hipStream_t)stream, &n_partials);
-}
-extern "C" int c21hip_z_ionise_recomb_xe_nrec_supported(int nx, int ny, int nz) {
-    const long nlines = (long)nx * ny;
-    return nz == 512 && zw_lines_of(nz, nlines) != 0 && !zw3_selected(nz, nlines);
-}
-extern "C" int c21hip_z_ionise_recomb_supported(int nx, int ny, int nz) {
-    const long nlines = (long)nx * ny;
-    return zw_lines_of(nz, nlines) != 0 && !zw3_selected(nz, nlines) && nz <= 512;
-}
-
-// 1: ... also with the x_e grid of a spin-temperature run (16 points per lane: 256- / 512-point z-lines)
-extern "C" int c21hip_z_ionise_recomb_xe_supported(int nx, int ny, int nz) {
-    return c21hip_z_ionise_recomb_supported(nx, ny, nz) && (nz == 256 || nz == 512);
-}
-
-// 1: the fused pass Z can take an x_e grid at this z-line length
-extern "C" int c21hip_z_ionise_xe_supported(int nx, int ny, int nz) {
-    return zw_lines_of(nz, (long)nx * ny) != 0;
+    return launch_z(zw_c2r_kernel<16, 8, 16>, nz, nlines / zwl, kBlock, 0, z, (hipStream_t)stream);
 }
 
 // Passes X, Y of ONE grid with window a of the tables built for a two-grid radius
@@ -5054,14 +4788,6 @@ extern "C" int c21hip_batched_stats(const double *partials, long stride, int nb,
                        partials, stride, nb, stats_out);
     LAUNCH_CHECK();
     return 0;
-}
-
-// workgroup partials the fused pass Z writes for an nx x ny x nz grid
-extern "C" int c21hip_z_ionise_partials(int nx, int ny, int nz) {
-    const long nlines = (long)nx * ny;
-    if (zw3_selected(nz, nlines)) return (int)(nlines / (kBlock / 64));
-    if (const int zwl = zw_lines_of(nz, nlines)) return (int)(nlines / (nz == 512 ? C21X_ZW_BLOCK / 16 : zwl));
-    return (int)(nlines / LZ_FUSED);
 }
 
 // The f_coll sums of `count` radii in ONE launch: block i reduces the n_partials doubles at
@@ -5143,7 +4869,6 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
     hipLaunchKernelGGL(pattern_fill_kernel, dim3(2048), dim3(kBlock), 0, stream, a, nf);
     hipLaunchKernelGGL(pattern_fill_kernel, dim3(2048), dim3(kBlock), 0, stream, b, nf);
     (void)hipMemsetAsync(mask, 0, (size_t)n * n * n, stream);
-    const int H = n / 2;
     const long nlines = (long)n * n;
     const float *src[2] = {a, b};
     float *work[2] = {real, real2};
@@ -5195,24 +4920,26 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
                                 stream_);
         else if (kind == 5)  // pass X without a window (diagnostic)
             st = filter_xy(src, work, 2, n, n, n, box_len, box_len, ft, R, rp, 0, stream_, 2);
-        else if (kind == 2 && c21hip_z_cross_bits_supported(n, n, n))  // what the loop launches: one plane
-            st = c21hip_split_z_ionise_stars_bits(a, b, reinterpret_cast<unsigned *>(mask), partials,
-                                                  partials + nlines / 4 + 40, n, n, n, 5, 6.2e9, 1.0, 1,
-                                                  1e-9, stream);
-        else if (kind == 2)
-            st = c21hip_split_z_ionise_stars(a, b, mask, partials, partials + nlines / 4 + 40,
-                                             n, n, n, 5, 6.2e9, 1.0, 1, 1e-9, stream);
-        else {
-            ZPassArgs z{};
-            z.ny = n;
-            z.lb = split_xb_log2(n);
-            z.main = reinterpret_cast<const float2 *>(a);
-            z.nyq = z.main + nlines * H;
-            z.out = real;
-            z.out_zstride = n + 2;
-            z.out_scale = 1.0f;
-            st = dispatch_z_c2r(n, z, nlines, stream);
-        }
+        else if (kind == 2) {
+            c21hip_z_ionise_desc d{};
+            d.size = sizeof(d);
+            d.delta_work = a;
+            d.stars_work = b;
+            if (c21hip_z_cross_bits_supported(n, n, n))  // what the loop launches: one plane
+                d.cross_plane = reinterpret_cast<unsigned *>(mask);
+            else
+                d.first_cross = mask;
+            d.partials = partials;
+            d.sum_out = partials + nlines / 4 + 40;
+            d.nx = d.ny = d.nz = n;
+            d.r_index = 5;
+            d.rhocrit_omb = 6.2e9;
+            d.ion_eff = 1.0;
+            d.mass_dep_zeta = 1;
+            d.f_limit = 1e-9;
+            st = c21hip_split_z_ionise(&d, stream);
+        } else
+            st = dispatch_z_c2r(n, z_pass_base(a, real, n + 2, n, n, n), nlines, stream);
     }
     (void)hipEventRecord(e1, stream);
     (void)hipEventSynchronize(e1);

@@ -313,6 +313,33 @@ static int r0_direct(void);
 static int g_loop_flags;
 int c21cm_ionize_last_loop_flags(void) { return g_loop_flags; }
 
+/* Does this spec take the fused recombination loop?  The one decision behind ctx_setup (single pass, rc shard
+ * phases) and c21cm_ionize_shard_rc_supported.  Lagrangian grids on the native passes with the evaluated windows
+ * (whalo_sfr takes window b alone); C21CM_RECOMB_FUSED=0: the unfused per-radius sequence. */
+static int fused_rc_route(const c21cm_ionize_spec *s) {
+    if (s->recomb_model == C21CM_RECOMB_NONE || s->use_mini_halos || s->ionise_entire_sphere || s->r_lowest != 0 ||
+        s->fcoll_mode != C21CM_FCOLL_STARS_GRID)
+        return 0;
+    const char *e = getenv("C21CM_RECOMB_FUSED");
+    if (e && e[0] == '0') return 0;
+    const int nx = s->hii_dim, ny = s->hii_dim, nz = s->hii_dim_z;
+    if (s->use_ts_fluct) { /* the x_e grid of a spin-temperature run: a third line of the barrier kernel;
+                            * C21CM_RECOMB_FUSED_TS=0 keeps such runs on the unfused sequence */
+        const char *et = getenv("C21CM_RECOMB_FUSED_TS");
+        if ((et && et[0] == '0') || !r0_direct() || !c21hip_z_ionise_recomb_xe_supported(nx, ny, nz)) return 0;
+    }
+    if (!s->cell_recomb) { /* N_rec of the previous snapshot filtered at the radius is the third line where the x_e
+                            * grid would be, or the fourth beside it; C21CM_RECOMB_FUSED_NREC=0: unfused */
+        const char *en = getenv("C21CM_RECOMB_FUSED_NREC");
+        if ((en && en[0] == '0') || s->recomb_model != C21CM_RECOMB_INHOMOGENEOUS) return 0;
+        if (!(s->use_ts_fluct ? c21hip_z_ionise_recomb_xe_nrec_supported(nx, ny, nz)
+                              : c21hip_z_ionise_recomb_xe_supported(nx, ny, nz)))
+            return 0;
+    }
+    return c21hip_fft_is_native(nx, ny, nz) && c21hip_z_ionise_recomb_supported(nx, ny, nz) &&
+           c21hip_wev_applicable(s->hii_filter, s->stars_filter, 2, nx, ny, nz);
+}
+
 /* fused_rc_ok: the caller can finish what the fused recombination loop leaves (first crossings with
  * Gamma_12): the single pass and the rc shard phases; the other shard phases keep such runs off it */
 static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedField *pf,
@@ -378,35 +405,14 @@ static int ctx_setup(ion_ctx *c, const c21cm_ionize_spec *s, const PerturbedFiel
      * filtered whalo_sfr is a third spectrum of passes X / Y and of the wave-level pass Z, the
      * barrier gains (1 + N_rec / (1 + delta)), Gamma_12 is written at first crossings and the
      * mean free path follows from the first-crossing index; the cell-scale radius and the
-     * post-loop stay on the general kernels.  Needs the evaluated windows (whalo_sfr takes window
-     * b alone).  C21CM_RECOMB_FUSED=0: the unfused per-radius sequence. */
+     * post-loop stay on the general kernels.  Which specs: fused_rc_route. */
     c->fused_rc = 0;
-    /* (round 4, late: CELL_RECOMB = false without an x_e grid as well -- N_rec filtered at the radius is
-     * the barrier kernel's third line where the x_e grid would be; single pass and rc shard phases.
-     * C21CM_RECOMB_FUSED_NREC=0 keeps such runs on the unfused sequence) */
-    const char *e_nr = getenv("C21CM_RECOMB_FUSED_NREC");
-    const int nrec_ok = s->cell_recomb ||
-                        (c->inhomo && fused_rc_ok && !(e_nr && e_nr[0] == '0') &&
-                         (s->use_ts_fluct ? c21hip_z_ionise_recomb_xe_nrec_supported(c->nx, c->ny, c->nz)
-                                          : c21hip_z_ionise_recomb_xe_supported(c->nx, c->ny, c->nz)));
     c->x3_on = c->x3_nrec = 0;
     c->x3_unf = c->x3_work = c->x3_work2 = NULL;
     c->x4_on = 0;
     c->x4_unf = c->x4_work = c->x4_work2 = NULL;
     c->cur_x4 = NULL;
-    if (c->native && c->lagrangian && c->recomb && nrec_ok &&
-        !s->use_mini_halos && !s->ionise_entire_sphere && s->r_lowest == 0 &&
-        fused_rc_ok) {
-        /* (round 4: with the x_e grid of a spin-temperature run too -- a third line of the barrier
-         * kernel; C21CM_RECOMB_FUSED_TS=0 keeps such runs on the unfused sequence) */
-        const char *e = getenv("C21CM_RECOMB_FUSED"), *et = getenv("C21CM_RECOMB_FUSED_TS");
-        const int ts_ok = !s->use_ts_fluct ||
-                          (!(et && et[0] == '0') && r0_direct() &&
-                           c21hip_z_ionise_recomb_xe_supported(c->nx, c->ny, c->nz));
-        if (!(e && e[0] == '0') && ts_ok && c21hip_z_ionise_recomb_supported(c->nx, c->ny, c->nz) &&
-            c21hip_wev_applicable(s->hii_filter, s->stars_filter, 2, c->nx, c->ny, c->nz))
-            c->fused_rc = c->fused = 1;
-    }
+    if (fused_rc_ok && fused_rc_route(s)) c->fused_rc = c->fused = 1;
     c->eul_pend = -1;
     c->eul_pend_buf = 0;
     c->eul_pend_mask = NULL;
@@ -747,85 +753,61 @@ static int flush_deferred(ion_ctx *c) {
     return st;
 }
 
+/* Radius R_ct joins the run of deferred f_coll sums (radii def_first, def_first - def_step, ...); a radius that
+ * does not continue the run has it reduced first. */
+static int defer_radius(ion_ctx *c, int R_ct) {
+    if (c->def_count == 1)
+        c->def_step = c->def_first - R_ct;
+    else if (c->def_count > 1 && R_ct != c->def_first - c->def_count * c->def_step) {
+        const int st = flush_deferred(c);
+        if (st) return st;
+    }
+    if (c->def_count == 0) c->def_first = R_ct;
+    c->def_count++;
+    return 0;
+}
+
 /* Fused pass Z of one radius (density + emissivity [+ x_e] spectra after passes X, Y): barrier
  * test into the mask, f_coll sum deferred or reduced now. */
 static int z_ionise_radius(ion_ctx *c, int R_ct, const float *dwork, const float *swork,
                            const float *xwork, unsigned char *first_cross) {
     int status = 0;
     const c21cm_ionize_spec *s = c->s;
-    /* crossing bits: this radius' plane instead of the mask (two grids only, see cross_bits_begin) */
-    unsigned *plane = c->cross_bits ? c->cross_bits + (size_t)(R_ct - 1) * (c->ntot / 32) : NULL;
-    if (c->fused_rc) { /* xwork: the filtered whalo_sfr; sums always deferred or reduced below */
-        double *part = c->def_partials ? c->def_partials + (long)R_ct * c->def_stride : c->partials;
-        if (c->def_partials) {
-            if (c->def_count == 0)
-                c->def_first = R_ct;
-            else if (c->def_count == 1)
-                c->def_step = c->def_first - R_ct;
-            else if (R_ct != c->def_first - c->def_count * c->def_step)
-                TRY(flush_deferred(c));
-            if (c->def_count == 0) c->def_first = R_ct;
-            c->def_count++;
+    double *sum_dev = c->scalars + SC_SUMS + R_ct;
+    c21hip_z_ionise_desc d = {.size = sizeof(d), .delta_work = dwork, .stars_work = swork,
+                              .recomb = c->fused_rc, .first_cross = first_cross, .partials = c->partials,
+                              .nx = c->nx, .ny = c->ny, .nz = c->nz, .r_index = R_ct,
+                              .rhocrit_omb = s->rhocrit_omb, .ion_eff = s->ion_eff_factor,
+                              .mass_dep_zeta = s->mass_dep_zeta, .f_limit = s->f_limit_acg};
+    if (c->def_partials) { /* no kernel of this loop reads a radius' mean: reduce all of them at the end */
+        TRY(defer_radius(c, R_ct));
+        d.partials = c->def_partials + (long)R_ct * c->def_stride;
+    } else if (!c->fused_rc)
+        d.sum_out = sum_dev;
+    if (c->fused_rc) { /* xwork: the filtered whalo_sfr, for the Gamma_12 pass below */
+        d.g12 = c->G12;
+        if (c->x4_on) { /* CELL_RECOMB = false with an x_e grid: four spectra */
+            d.xe_work = c->cur_xe;
+            d.nrec_work = c->cur_x4;
+        } else if (c->x3_nrec) /* CELL_RECOMB = false: N_rec filtered at the radius is the third line */
+            d.nrec_work = c->cur_xe;
+        else {
+            d.xe_work = s->use_ts_fluct ? c->cur_xe : NULL;
+            d.nrec = c->inhomo ? c->prev_nrec : NULL;
+            d.rec0 = c->rec0;
         }
-        if (c->x4_on) /* CELL_RECOMB = false with an x_e grid: four spectra */
-            TRY(c21hip_split_z_ionise_recomb_xe_nrec(dwork, swork, c->cur_xe, c->cur_x4, c->G12, first_cross,
-                                                     part, c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
-                                                     s->ion_eff_factor, s->mass_dep_zeta, s->f_limit_acg,
-                                                     c->stream));
-        else if (c->x3_nrec) /* CELL_RECOMB = false: N_rec filtered at the radius is the third line */
-            TRY(c21hip_split_z_ionise_recomb_nrec(dwork, swork, c->cur_xe, c->G12, first_cross, part, c->nx,
-                                                  c->ny, c->nz, R_ct, s->rhocrit_omb, s->ion_eff_factor,
-                                                  s->mass_dep_zeta, s->f_limit_acg, c->stream));
-        else
-        TRY(c21hip_split_z_ionise_recomb_xe(dwork, swork, s->use_ts_fluct ? c->cur_xe : NULL,
-                                            c->inhomo ? c->prev_nrec : NULL, c->rec0, c->G12, first_cross,
-                                            part, c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
-                                            s->ion_eff_factor, s->mass_dep_zeta, s->f_limit_acg, c->stream));
+    } else if (c->cross_bits) { /* this radius' plane instead of the mask (two grids only, see cross_bits_begin) */
+        d.first_cross = NULL;
+        d.cross_plane = c->cross_bits + (size_t)(R_ct - 1) * (c->ntot / 32);
+    } else
+        d.xe_work = xwork;
+    TRY(c21hip_split_z_ionise(&d, c->stream));
+    if (c->fused_rc)
         TRY(c21hip_split_z_sfr_gamma12(xwork, first_cross, c->G12, c->nx, c->ny, c->nz, R_ct,
                                        s->R[R_ct] * s->gamma_prefactor, c->stream));
-        if (!c->def_partials) {
-            double *sum_dev = c->scalars + SC_SUMS + R_ct;
-            TRY(c21hip_reduce_sum(part, c21hip_z_ionise_partials(c->nx, c->ny, c->nz), sum_dev, c->stream));
-            TRY(c21hip_finish_mean(sum_dev, (double)c->ntot, s->mass_dep_zeta, s->f_limit_acg,
-                                   c->scalars + SC_MEANS + R_ct, c->stream));
-        }
-        goto done;
-    }
-    if (c->def_partials) {
-        /* no kernel of this loop reads a radius' mean: reduce all of them at the end */
-        if (c->def_count == 0)
-            c->def_first = R_ct;
-        else if (c->def_count == 1)
-            c->def_step = c->def_first - R_ct;
-        else if (R_ct != c->def_first - c->def_count * c->def_step)
-            TRY(flush_deferred(c));
-        if (c->def_count == 0) c->def_first = R_ct;
-        c->def_count++;
-        if (plane)
-            TRY(c21hip_split_z_ionise_stars_bits(dwork, swork, plane,
-                                                 c->def_partials + (long)R_ct * c->def_stride, NULL,
-                                                 c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
-                                                 s->ion_eff_factor, s->mass_dep_zeta, s->f_limit_acg,
-                                                 c->stream));
-        else
-        TRY(c21hip_split_z_ionise_stars_xe(dwork, swork, xwork, first_cross,
-                                           c->def_partials + (long)R_ct * c->def_stride, NULL,
-                                           c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
-                                           s->ion_eff_factor, s->mass_dep_zeta, s->f_limit_acg,
-                                           c->stream));
-        goto done;
-    }
-    {
-        double *sum_dev = c->scalars + SC_SUMS + R_ct;
-        if (plane)
-            TRY(c21hip_split_z_ionise_stars_bits(dwork, swork, plane, c->partials, sum_dev, c->nx, c->ny,
-                                                 c->nz, R_ct, s->rhocrit_omb, s->ion_eff_factor,
-                                                 s->mass_dep_zeta, s->f_limit_acg, c->stream));
-        else
-        TRY(c21hip_split_z_ionise_stars_xe(dwork, swork, xwork, first_cross, c->partials, sum_dev,
-                                           c->nx, c->ny, c->nz, R_ct, s->rhocrit_omb,
-                                           s->ion_eff_factor, s->mass_dep_zeta, s->f_limit_acg,
-                                           c->stream));
+    if (!c->def_partials) {
+        if (c->fused_rc) /* (the recombination pass leaves its partials unreduced) */
+            TRY(c21hip_reduce_sum(d.partials, c21hip_z_ionise_partials(c->nx, c->ny, c->nz), sum_dev, c->stream));
         TRY(c21hip_finish_mean(sum_dev, (double)c->ntot, s->mass_dep_zeta, s->f_limit_acg,
                                c->scalars + SC_MEANS + R_ct, c->stream));
     }
@@ -2732,29 +2714,7 @@ done:
  * radius, the post-loop.  c21cm_ionize_shard_rc_supported tells whether a spec takes this route;
  * everything else with a recombination model keeps the 64-bit keys above.
  * reference: src/py21cmfast/src/IonisationBox.c:1084-1140,1531-1588 */
-int c21cm_ionize_shard_rc_supported(const c21cm_ionize_spec *s) {
-    if (!s || s->recomb_model == C21CM_RECOMB_NONE ||
-        s->use_mini_halos || s->ionise_entire_sphere || s->r_lowest != 0 ||
-        s->fcoll_mode != C21CM_FCOLL_STARS_GRID)
-        return 0;
-    const char *e = getenv("C21CM_RECOMB_FUSED");
-    if (e && e[0] == '0') return 0;
-    const int nx = s->hii_dim, ny = s->hii_dim, nz = s->hii_dim_z;
-    if (s->use_ts_fluct) { /* round 5: with the x_e grid of a spin-temperature run too (the same conditions
-                            * as the single pass: ctx_setup) */
-        const char *et = getenv("C21CM_RECOMB_FUSED_TS");
-        if ((et && et[0] == '0') || !r0_direct() || !c21hip_z_ionise_recomb_xe_supported(nx, ny, nz)) return 0;
-    }
-    if (!s->cell_recomb) { /* round 5: the filtered N_rec of the previous snapshot is an input every rank holds */
-        const char *en = getenv("C21CM_RECOMB_FUSED_NREC");
-        if ((en && en[0] == '0') || s->recomb_model != C21CM_RECOMB_INHOMOGENEOUS) return 0;
-        if (!(s->use_ts_fluct ? c21hip_z_ionise_recomb_xe_nrec_supported(nx, ny, nz)
-                              : c21hip_z_ionise_recomb_xe_supported(nx, ny, nz)))
-            return 0;
-    }
-    return c21hip_fft_is_native(nx, ny, nz) && c21hip_z_ionise_recomb_supported(nx, ny, nz) &&
-           c21hip_wev_applicable(s->hii_filter, s->stars_filter, 2, nx, ny, nz);
-}
+int c21cm_ionize_shard_rc_supported(const c21cm_ionize_spec *s) { return s && fused_rc_route(s); }
 
 int c21cm_ionize_shard_radii_rc(const c21cm_ionize_spec *spec, int rank, int world,
                                 const PerturbedField *perturbed_field,

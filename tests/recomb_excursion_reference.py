@@ -514,7 +514,7 @@ def recomb_line(name, ref, e, fig):
 # r1 - r4 are the smallest boxes that reach each fused pass-Z kernel (nx >= 128, 256- or 512-point z-lines);
 # test_excursion_reference_host.py holds every box to the caps.
 CASES = {
-    "r1": (128, 256, 2, 1, False, True, 20.0, 77),   # c21hip_split_z_ionise_recomb, dense N_rec rows
+    "r1": (128, 256, 2, 1, False, True, 20.0, 77),   # c21hip_split_z_ionise with recomb, dense N_rec rows
     "r2": (128, 256, 2, 0, False, True, 10.0, 77),   # ..._recomb_nrec: the filtered N_rec as third spectrum
     "r3": (128, 256, 1, 1, True, True, 10.0, 77),    # ..._recomb_xe, homogeneous N = 0.25
     "r4": (128, 512, 2, 0, True, True, 8.0, 77),     # ..._recomb_xe_nrec: four spectra

@@ -239,6 +239,16 @@ def test_resolver_against_numpy(gpu_lib, r_hi, r_lo, nlines):
 XB = (1024, 16, 512)  # the mapping depends on nx alone; 16384 lines = 1024 workgroups
 
 
+class ZIoniseDesc(C.Structure):
+    """c21hip_z_ionise_desc (c21hip.h); a mirror whose size differs from the library's is refused by the entry."""
+    _fields_ = [("size", C.c_size_t), ("delta_work", C.c_void_p), ("stars_work", C.c_void_p),
+                ("xe_work", C.c_void_p), ("nrec_work", C.c_void_p), ("nrec", C.c_void_p), ("rec0", C.c_double),
+                ("recomb", C.c_int), ("g12", C.c_void_p), ("first_cross", C.c_void_p), ("cross_plane", C.c_void_p),
+                ("partials", C.c_void_p), ("sum_out", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("r_index", C.c_int), ("rhocrit_omb", C.c_double), ("ion_eff", C.c_double),
+                ("mass_dep_zeta", C.c_int), ("f_limit", C.c_double)]
+
+
 def kernel_level_xblocked(lib):
     """Both two-grid pass-Z kernels on the same random spectra of a 1024 x 16 x 512 grid, three radii
     visited 3, 2, 1 with fresh emissivity spectra each: the mask kernel updates one uint8 mask, the bits
@@ -253,10 +263,8 @@ def kernel_level_xblocked(lib):
     assert nf == 2 * (nlines * H + nlines)
     lib.c21hip_z_ionise_partials.restype = C.c_int
     n_part = lib.c21hip_z_ionise_partials(nx, ny, nz)
-    args_tail = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_void_p]
-    for f in (lib.c21hip_split_z_ionise_stars, lib.c21hip_split_z_ionise_stars_bits):
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p] * 5 + args_tail
+    lib.c21hip_split_z_ionise.restype = C.c_int
+    lib.c21hip_split_z_ionise.argtypes = [C.POINTER(ZIoniseDesc), C.c_void_p]
     lib.c21hip_resolve_crossings.restype = C.c_int
     lib.c21hip_resolve_crossings.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
 
@@ -274,12 +282,14 @@ def kernel_level_xblocked(lib):
     for r in (3, 2, 1):
         stars = 0.01 * torch.randn(nf, generator=g, device="cuda", dtype=torch.float32)
         stars[0:2 * nlines * H:2 * H] = 1.0  # DC: the emissivity averages to the barrier of delta = 0
-        common = (nx, ny, nz, r, 1.0, 1.2 - 0.1 * r, 1, 1e-9, None)  # zeta 0.9, 1.0, 1.1: about 41, 29, 17 % first crossings
-        assert lib.c21hip_split_z_ionise_stars(delta.data_ptr(), stars.data_ptr(), mask.data_ptr(),
-                                               part_m[r - 1].data_ptr(), None, *common) == 0
+        common = dict(size=C.sizeof(ZIoniseDesc), delta_work=delta.data_ptr(), stars_work=stars.data_ptr(),
+                      nx=nx, ny=ny, nz=nz, r_index=r, rhocrit_omb=1.0, ion_eff=1.2 - 0.1 * r, mass_dep_zeta=1,
+                      f_limit=1e-9)  # zeta 0.9, 1.0, 1.1: about 41, 29, 17 % first crossings; sum_out NULL
+        assert lib.c21hip_split_z_ionise(ZIoniseDesc(first_cross=mask.data_ptr(), partials=part_m[r - 1].data_ptr(),
+                                                     **common), None) == 0
         plane = planes.data_ptr() + 4 * (r - 1) * plane_words
-        assert lib.c21hip_split_z_ionise_stars_bits(delta.data_ptr(), stars.data_ptr(), plane,
-                                                    part_b[r - 1].data_ptr(), None, *common) == 0
+        assert lib.c21hip_split_z_ionise(ZIoniseDesc(cross_plane=plane, partials=part_b[r - 1].data_ptr(),
+                                                     **common), None) == 0
         torch.cuda.synchronize()
     resolved = torch.full((nlines * nz,), 0xAB, dtype=torch.uint8, device="cuda")
     assert lib.c21hip_resolve_crossings(planes.data_ptr(), 3, 1, resolved.data_ptr(), nlines, None) == 0

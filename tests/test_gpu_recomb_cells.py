@@ -49,7 +49,7 @@ SIX = ("neutral_fraction", "z_reion", "kinetic_temperature", "ionisation_rate_G1
 # grid_api.ionize_last_loop_flags: 2 fused recombination loop, 4 third spectrum in the barrier kernel, 8 ...
 # which is the filtered N_rec, 16 a fourth spectrum, 32 two radii per sweep.
 ROUTES = {
-    "r1": (True, True),    # c21hip_split_z_ionise_recomb: whalo_sfr as third spectrum, dense N_rec rows
+    "r1": (True, True),    # c21hip_split_z_ionise with recomb: whalo_sfr as third spectrum, dense N_rec rows
     "r2": (True, True),    # ..._recomb_nrec
     "r3": (True, True),    # ..._recomb_xe, homogeneous
     "r4": (True, True),    # ..._recomb_xe_nrec: four spectra, 512-point z-lines
