@@ -91,6 +91,11 @@ def _declare(lib):
         lib.c21cm_bispectrum_grids.restype = i32
         lib.c21cm_bispectrum_grids.argtypes = [vp, i32, i32, i32, i32, C.c_longlong, vp, f64, f64, f64,
                                                P(S.BispecBins), vp, vp, vp]
+    if hasattr(lib, "c21cm_bubble_sizes_grids"):
+        lib.c21cm_bubble_sizes_grids.restype = i32
+        lib.c21cm_bubble_sizes_grids.argtypes = [vp, i32, i32, i32, i32, C.c_longlong, vp, f64, f64, f64, f64, i32,
+                                                 C.c_longlong, C.c_ulonglong, i32, i32, f64, i32, vp, vp, vp, vp, vp,
+                                                 vp, vp]
     for name, argt in (("compute_mu_for_multiple_scattering", [f64]),
                        ("compute_eta_for_multiple_scattering", [f64]),
                        ("hyper_2F3", [f64, f64, f64])):

@@ -892,6 +892,38 @@ int c21hip_bispec_finish(const double *partials, int n_batch, int n_slabs, int n
                          double scale, double n_cells, const long long *counts_in, double *out_b,
                          long long *counts_out, void *stream);
 
+/* ---- bubble_kernels.hip : mean-free-path bubble sizes of boxes and lightcone chunks (bubble_driver.c) ---- */
+#define C21HIP_BUBBLE_MAX_BINS 4096 /* edges (fp64) and counters (32 bits) of one workgroup: 48 KiB of LDS */
+#define C21HIP_BUBBLE_CHUNK 64      /* mask words per chunk: one pack workgroup, one lane each in the prefix pass */
+/* The mask of box b: nx ny rows of W = (nz + 63) / 64 words, bit l & 63 of word l >> 6 of a row set where the cell
+ * is selected ((double)v < threshold, or >= with select_below = 0), the padding bits zero.  chunk_sum[b][c] = the
+ * set bits of words [64 c, 64 c + 64) of the box; *bad |= 1 on a non-finite value */
+int c21hip_bubble_pack(const float *in, int nx, int ny, int nz, long long row_pitch, const long long *offsets,
+                       int n_batch, double threshold, int select_below, unsigned long long *mask, int *chunk_sum,
+                       int *bad, void *stream);
+/* prefix[b][w] = the set bits of the box's words before w (chunk_off: n_batch x chunks of scratch, the exclusive scan
+ * of chunk_sum), stats[b][0] = the set bits of box b */
+int c21hip_bubble_rank(const unsigned long long *mask, const int *chunk_sum, int nx, int ny, int nz, int n_batch,
+                       long long *chunk_off, long long *prefix, long long *stats, void *stream);
+typedef struct c21hip_bubble_walk_args {
+    const unsigned long long *mask; /* device, as c21hip_bubble_pack wrote it */
+    const long long *prefix;
+    int nx, ny, nz, n_batch;
+    double cell[3], max_length;
+    int periodic[3], los;
+    long long n_rays, max_steps;
+    unsigned long long seed;
+    int n_bins;
+    const double *edges;         /* device, n_bins + 1 */
+    unsigned long long *hist;    /* [n_batch][n_bins], zeroed by the caller */
+    long long *stats;            /* [n_batch][4]: n_sel as c21hip_bubble_rank left it, the other three zeroed */
+    double *lengths;             /* [n_batch][n_rays] or NULL */
+    unsigned char *flags;        /* [n_batch][n_rays] or NULL */
+    long long *starts;           /* [n_batch][n_rays] or NULL */
+} c21hip_bubble_walk_args;
+/* the rays of every box: the estimator of c21cm_bubble_sizes_grids (include/c21cm_grid.h) */
+int c21hip_bubble_walk(const c21hip_bubble_walk_args *a, void *stream);
+
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */
 typedef struct c21hip_ts_args { /* the scalars of c21cm_ts_spec, passed by value */

@@ -402,6 +402,13 @@ enum c21_ws_slot {
     WS_BS_STACK, /* one padded box per shell: float, or double in the indicator pass */
     WS_BS_SUMS,  /* row sums and means of the pack, products partials, outputs */
     WS_BS_FLAG,
+    /* ---- bubble_driver.c ---- */
+    WS_BU_TAB,    /* histogram edges, batch offsets */
+    WS_BU_IN,     /* staged host field */
+    WS_BU_MASK,   /* one bit per cell, rows padded to whole 64-bit words */
+    WS_BU_PREFIX, /* set bits per chunk of words, their exclusive scan, set bits before every word */
+    WS_BU_OUT,    /* histogram, counts, and the per-ray outputs that were asked for */
+    WS_BU_FLAG,
 
     WS_COUNT
 };

@@ -1466,3 +1466,59 @@ def bispectrum(field, shape, lengths, edges, triangles, *, offsets=(0,), row_pit
                                      Lx, Ly, Lz, C.byref(bins), _vptr(out), _vptr(counts), _stream(stream)),
           "c21cm_bispectrum_grids")
     return out, counts
+
+
+def bubble_sizes(field, shape, lengths, edges, *, threshold=0.5, select_below=True, n_rays=1_000_000, seed=0,
+                 los=False, periodic=(True, True, True), max_length=None, offsets=(0,), row_pitch=None,
+                 return_rays=False, stream=None):
+    """Mean-free-path bubble sizes of ``len(offsets)`` boxes of ``shape`` = (nx, ny, nz) cells and ``lengths`` (Lx,
+    Ly, Lz) read from the float32 array ``field`` (the layout of ``power_spectrum``).  ``n_rays`` rays per box start
+    in cells with ``v < threshold`` (``select_below``) or ``v >= threshold`` and run, isotropically or (``los``)
+    along +-z, to the first cell that is not selected; ``edges``: the n_bins + 1 histogram edges in length.  Returns
+    ``(hist, stats)``, int64 (n_batch, n_bins) and (n_batch, 4) = n_selected, n_ended, n_capped, n_escaped, and with
+    ``return_rays`` also ``(lengths, flags, starts)``: float64, uint8 and int64 (n_batch, n_rays).  numpy for numpy
+    input, torch on the field's device for a torch CUDA field.  The estimator is written down at
+    ``c21cm_bubble_sizes_grids`` (include/c21cm_grid.h)."""
+    nx, ny, nz = (int(x) for x in shape)
+    row_pitch = nz if row_pitch is None else int(row_pitch)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_batch = len(offsets)
+    _f32_dense(field, "field")
+    size = int(np.prod(field.shape, dtype=np.int64))
+    if n_batch < 1 or offsets.min() < 0 or offsets.max() + (nx * ny - 1) * row_pitch + nz > size:
+        raise ValueError("the boxes do not lie inside the field")
+    edges = np.ascontiguousarray(edges, np.float64)
+    if edges.ndim != 1 or edges.size < 2:
+        raise ValueError("edges must be a 1-D array of at least 2 values")
+    n_bins = len(edges) - 1
+    n_rays = int(n_rays)
+    if not 1 <= n_rays <= 2**31 - 1:
+        raise ValueError("n_rays must be in [1, 2^31 - 1]")
+    seed = int(seed)
+    if not 0 <= seed < 2**64:
+        raise ValueError("seed must be in [0, 2^64)")
+    Lx, Ly, Lz = (float(x) for x in lengths)
+    max_length = max(Lx, Ly, Lz) if max_length is None else float(max_length)
+    px, py, pz = (bool(p) for p in periodic)
+    lengths_out = flags = starts = None
+    if _is_torch(field):
+        import torch
+
+        def empty(shape_, dtype):
+            return torch.empty(shape_, dtype=getattr(torch, dtype), device=field.device)
+    else:
+        def empty(shape_, dtype):
+            return np.empty(shape_, dtype)
+    hist, stats = empty((n_batch, n_bins), "int64"), empty((n_batch, 4), "int64")
+    if return_rays:
+        lengths_out, flags = empty((n_batch, n_rays), "float64"), empty((n_batch, n_rays), "uint8")
+        starts = empty((n_batch, n_rays), "int64")
+    lib = load()
+    check(lib.c21cm_bubble_sizes_grids(
+        _vptr(field), nx, ny, nz, n_batch, row_pitch, offsets.ctypes.data_as(C.c_void_p), Lx, Ly, Lz,
+        float(threshold), int(bool(select_below)), n_rays, seed, int(bool(los)), px | (py << 1) | (pz << 2),
+        max_length, n_bins, edges.ctypes.data_as(C.c_void_p), _vptr(hist), _vptr(stats), _vptr(lengths_out),
+        _vptr(flags), _vptr(starts), _stream(stream)), "c21cm_bubble_sizes_grids")
+    if return_rays:
+        return hist, stats, lengths_out, flags, starts
+    return hist, stats

@@ -18,7 +18,9 @@ the field before the transform, f' = (f - mean) wx[i] wy[j] wz[l], the power div
 ``get_pdf`` and ``lightcone_moments`` are the one-point statistics of a box or of the chunks of a
 lightcone (``csrc/hip/moments_kernels.hip``).  ``get_bispectrum`` and ``lightcone_bispectra`` are the three-point
 statistic, the FFT estimator over shells in |k| (``csrc/hip/bispectrum_kernels.hip``; its spec is
-``tests/bispectrum_reference.py``).
+``tests/bispectrum_reference.py``).  ``get_bubble_sizes`` and ``lightcone_bubble_sizes`` are the morphological
+statistic, the mean-free-path bubble size distribution traced ray by ray (``csrc/hip/bubble_kernels.hip``; its
+spec is ``tests/bubble_reference.py``).
 
 Arrays may be numpy (results are numpy) or torch CUDA tensors (results are torch tensors on the same
 device; the field never visits the host).  Argument errors are ``ValueError``; a non-finite field value
@@ -682,5 +684,176 @@ def lightcone_bispectra(lightcone, cell_size, *, chunk_length=None, chunk_starts
     edges = bispectrum_edges(shape, L, bins, log_bins)
     tri = _check_triangles(triangles, edges)
     res = _bispectrum_result(_f32(lightcone), shape, L, edges, tri, starts, ns, reduced)
+    res.chunk_starts, res.redshifts = starts, z
+    return res
+
+
+BUBBLE_MAX_BINS = 4096
+
+
+def bubble_edges(shape, boxlength, bins=64, log_bins=True, max_length=None) -> np.ndarray:
+    """The length edges ``get_bubble_sizes`` uses for a grid of ``shape``: an int gives ``np.geomspace(cell_min,
+    max_length, bins + 1)`` (``np.linspace`` without ``log_bins``) from the smallest cell size to ``max_length``
+    (default: the largest box length); an array is taken as the edges.  Checked either way: 1 to 4096 bins, finite
+    and increasing, the first edge >= 0."""
+    L = _lengths(boxlength, len(shape))
+    cell_min = min(l / int(n) for l, n in zip(L, shape))
+    top = max(L) if max_length is None else float(max_length)
+    e = make_edges(bins, cell_min, top, cell_min, log_bins)
+    if not 1 <= len(e) - 1 <= BUBBLE_MAX_BINS:
+        raise ValueError(f"a bubble size distribution takes 1 to {BUBBLE_MAX_BINS} bins, got {len(e) - 1}")
+    if e[0] < 0:
+        raise ValueError("the first edge must be >= 0")
+    return e
+
+
+@dataclass
+class BubbleSizes:
+    """What ``get_bubble_sizes`` and ``lightcone_bubble_sizes`` return (the latter with a leading chunk axis on
+    everything but ``edges`` and ``r``): ``edges`` (n_bins + 1,) in length; ``r`` (n_bins,) the geometric bin centres
+    sqrt(e_i e_{i+1}); ``hist`` int64 ended rays per bin; ``pdf`` dP/dlnR = hist / (n_ended ln(e_{i+1} / e_i)), NaN
+    where no ray ended; ``n_selected`` cells, ``n_ended`` / ``n_capped`` / ``n_escaped`` rays; ``filling_fraction`` =
+    n_selected / cells; ``mean_free_path`` the mean of the ended lengths (NaN where no ray ended); with
+    ``return_rays`` per ray ``lengths``, ``flags`` (0 ended, 1 capped, 2 escaped; 255 without a selected cell) and
+    ``starts`` (flat cell index in the box); for a lightcone ``chunk_starts`` and ``redshifts``."""
+
+    edges: object
+    r: object
+    hist: object
+    pdf: object
+    n_selected: object
+    n_ended: object
+    n_capped: object
+    n_escaped: object
+    filling_fraction: object
+    mean_free_path: object = None
+    lengths: object = None
+    flags: object = None
+    starts: object = None
+    chunk_starts: np.ndarray | None = None
+    redshifts: np.ndarray | None = None
+
+
+def _bubble_args(threshold, select, n_rays, seed, directions, periodic, max_length, L):
+    if select not in ("below", "above"):
+        raise ValueError("select must be 'below' (v < threshold) or 'above' (v >= threshold)")
+    if directions not in ("isotropic", "los"):
+        raise ValueError("directions must be 'isotropic' or 'los'")
+    if isinstance(threshold, (bool, np.bool_)) or np.ndim(threshold) != 0 or not np.isfinite(float(threshold)):
+        raise ValueError("threshold must be a finite number")
+    if isinstance(n_rays, (bool, np.bool_)) or int(n_rays) != n_rays or not 1 <= int(n_rays) <= 2**31 - 1:
+        raise ValueError("n_rays must be an integer in [1, 2^31 - 1]")
+    if isinstance(seed, (bool, np.bool_)) or int(seed) != seed or not 0 <= int(seed) < 2**64:
+        raise ValueError("seed must be an integer in [0, 2^64)")
+    if np.ndim(periodic) == 0:
+        periodic = (bool(periodic),) * 3
+    else:
+        periodic = tuple(bool(p) for p in periodic)
+        if len(periodic) != 3:
+            raise ValueError("periodic must be a bool or three bools")
+    max_length = max(L) if max_length is None else float(max_length)
+    if not (np.isfinite(max_length) and max_length > 0):
+        raise ValueError("max_length must be positive and finite")
+    return dict(threshold=float(threshold), select_below=select == "below", n_rays=int(n_rays), seed=int(seed),
+                los=directions == "los", periodic=periodic, max_length=max_length)
+
+
+def _bubble_result(f, shape, L, edges, args, offsets, row_pitch, return_rays):
+    out = api.bubble_sizes(f, shape, L, edges, offsets=offsets, row_pitch=row_pitch, return_rays=True, **args)
+    hist, stats = out[:2]
+    n_cells = float(int(shape[0]) * int(shape[1]) * int(shape[2]))
+    e = _edges_like(edges, hist)
+    dlnr = _edges_like(np.log(edges[1:] / edges[:-1]) if edges[0] > 0 else
+                       np.concatenate([[np.inf], np.log(edges[2:] / edges[1:-1])]), hist)
+    r = _edges_like(np.sqrt(edges[:-1] * edges[1:]), hist)
+    n_sel, n_end = stats[:, 0], stats[:, 1]
+    if _is_torch(hist):
+        import torch
+
+        f64 = torch.float64
+        pdf = hist.to(f64) / n_end.to(f64)[:, None] / dlnr[None]  # 0 / 0 = NaN where no ray ended
+        # a tensor divisor: by a Python scalar torch multiplies with the reciprocal, which is not n_sel / cells
+        fill = n_sel.to(f64) / torch.full((), n_cells, dtype=f64, device=hist.device)
+    else:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            pdf = hist / n_end.astype(np.float64)[:, None] / dlnr[None]
+        fill = n_sel / n_cells
+    res = BubbleSizes(edges=e, r=r, hist=hist, pdf=pdf, n_selected=n_sel, n_ended=n_end, n_capped=stats[:, 2],
+                      n_escaped=stats[:, 3], filling_fraction=fill)
+    # the mean free path is the mean of the ended lengths, so the lengths are always asked for
+    lengths, flags, starts = out[2:]
+    ended = flags == 0
+    if _is_torch(hist):
+        zero = torch.zeros((), dtype=torch.float64, device=hist.device)
+        res.mean_free_path = torch.where(ended, lengths, zero).sum(dim=1) / n_end.to(torch.float64)
+    else:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            res.mean_free_path = np.where(ended, lengths, 0.0).sum(axis=1) / n_end
+    if return_rays:
+        res.lengths, res.flags, res.starts = lengths, flags, starts
+    return res
+
+
+_BUBBLE_PER_BOX = ("hist", "pdf", "n_selected", "n_ended", "n_capped", "n_escaped", "filling_fraction",
+                   "mean_free_path", "lengths", "flags", "starts")
+
+
+def get_bubble_sizes(field, boxlength, *, threshold=0.5, select="below", n_rays=1_000_000, seed=0, bins=64,
+                     log_bins=True, max_length=None, directions="isotropic", periodic=True,
+                     return_rays=False) -> BubbleSizes:
+    """The mean-free-path bubble size distribution (Mesinger & Furlanetto 2007) of the 3-D ``field`` in a box of
+    ``boxlength`` (a scalar or 3 lengths): ``n_rays`` rays start at random points of the selected phase -- cells with
+    ``v < threshold`` (``select="below"``: for a neutral fraction the ionised phase) or ``v >= threshold``
+    (``"above"``), every selected cell equally likely -- run in random directions (``directions="isotropic"``, or
+    ``"los"``: along +-z) and end at the first cell that is not selected; their lengths are histogrammed into
+    ``bins`` (``bubble_edges``: by default 64 log-spaced bins from the smallest cell size to ``max_length``, itself
+    by default the largest box length) as dP/dlnR.  A ray that reaches ``max_length`` is capped, and one that leaves
+    through an axis that is not ``periodic`` (a bool or three) has escaped; neither is in the histogram.  Rays are
+    drawn from ``seed`` with a counter-based generator: ray i is the same whatever ``n_rays``, and two calls give
+    the same bytes.  ``return_rays`` adds the per-ray lengths, flags and start cells.  A field without a selected
+    cell gives zeros and a NaN pdf."""
+    _check_bubble_field(field)
+    shape = _shape(field)
+    L = _lengths(boxlength)
+    args = _bubble_args(threshold, select, n_rays, seed, directions, periodic, max_length, L)
+    edges = bubble_edges(shape, L, bins, log_bins, args["max_length"])
+    res = _bubble_result(_f32(field), shape, L, edges, args, (0,), None, return_rays)
+    for name in _BUBBLE_PER_BOX:
+        v = getattr(res, name)
+        if v is not None:
+            setattr(res, name, v[0])
+    return res
+
+
+def _check_bubble_field(field, what="field"):
+    if field.ndim != 3:
+        raise ValueError(f"{what} must be a 3-D array, got {field.ndim} dimensions")
+
+
+def lightcone_bubble_sizes(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None,
+                           **kw) -> BubbleSizes:
+    """Bubble size distributions of the chunks of a rectilinear ``lightcone`` (nx, ny, n_slices) of cells of
+    ``cell_size`` [Mpc], chunked as ``lightcone_power_spectra`` chunks it and with its central-redshift rule; all
+    chunks go through one library call and share the edges.  The transverse axes are periodic and the line of sight
+    is not (a ray that leaves a chunk along it has escaped), so ``periodic`` is not a keyword here; the others are
+    those of ``get_bubble_sizes``.  Every per-box entry carries a leading chunk axis."""
+    _check_bubble_field(lightcone, "lightcone")
+    if "periodic" in kw:
+        raise ValueError("periodic is fixed for a lightcone: the transverse axes are, the line of sight is not")
+    unknown = set(kw) - {"threshold", "select", "n_rays", "seed", "bins", "log_bins", "max_length", "directions",
+                         "return_rays"}
+    if unknown:
+        raise ValueError(f"unknown keywords: {sorted(unknown)}")
+    nx, ny, ns = _shape(lightcone)
+    dx = float(cell_size)
+    if not (np.isfinite(dx) and dx > 0):
+        raise ValueError("cell_size must be positive and finite")
+    n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
+    shape, L = (nx, ny, n), (nx * dx, ny * dx, n * dx)
+    args = _bubble_args(kw.get("threshold", 0.5), kw.get("select", "below"), kw.get("n_rays", 1_000_000),
+                        kw.get("seed", 0), kw.get("directions", "isotropic"), (True, True, False),
+                        kw.get("max_length"), L)
+    edges = bubble_edges(shape, L, kw.get("bins", 64), kw.get("log_bins", True), args["max_length"])
+    res = _bubble_result(_f32(lightcone), shape, L, edges, args, starts, ns, kw.get("return_rays", False))
     res.chunk_starts, res.redshifts = starts, z
     return res

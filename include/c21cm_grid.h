@@ -1059,6 +1059,40 @@ int c21cm_bispectrum_grids(const float *field, int nx, int ny, int nz, int n_bat
                            const long long *batch_offsets, double Lx, double Ly, double Lz,
                            const c21cm_bispec_bins *bins, double *bispectrum, long long *n_triangles, void *stream);
 
+/* ---- Mean-free-path bubble size distributions of boxes and lightcone chunks (Mesinger & Furlanetto 2007; DESIGN
+ * 4.11; the spec is tests/bubble_reference.py) ----
+ * The layout of c21cm_power_spectrum_grids; the cells measure cell_a = L_a / n_a.  All arithmetic below is fp64 + - *
+ * /, sqrt and one sincos per ray, without contraction.
+ * Selection: a cell is selected iff (double)v < threshold (select_below = 1) or >= threshold (0).
+ * Draws: ray r of box b takes the Philox-4x32-10 blocks with counter (r, p, b, 0) and key `seed`, p = 0, 1, 2, each
+ *   turned into two uniforms on (0, 1) with 53 bits (philox_uniform_pair): p = 0 (u_cell, u_x), p = 1 (u_y, u_z),
+ *   p = 2 (u_mu, u_phi).  A ray is a function of (seed, b, r) and the box alone.
+ * Start: with n_sel selected cells in the box, the k-th of them in C order, k = min((long long)(u_cell (double)n_sel),
+ *   n_sel - 1), cell (idx_x, idx_y, idx_z); the point p0_a = ((double)idx_a + u_a) cell_a.
+ * Direction: isotropic (directions = 0): c = 2 u_mu - 1, s = sqrt(1 - c c), d = (s cos(2 pi u_phi), s sin(2 pi
+ *   u_phi), c); along the line of sight (directions = 1): d = (0, 0, +1) if u_mu >= 0.5, else (0, 0, -1).
+ * Walk (Amanatides & Woo, started in idx): tmax_a = (((double)(idx_a + (d_a > 0))) cell_a - p0_a) / d_a, tdel_a =
+ *   cell_a / |d_a|, both +inf where d_a == 0.  Repeat: a = 0; if (tmax[1] < tmax[a]) a = 1; if (tmax[2] < tmax[a])
+ *   a = 2; t = tmax[a]; if !(t < max_length) the ray is capped; the index steps along a; outside the box it wraps
+ *   where bit a of periodic_mask is set, otherwise the ray has escaped at t; if the entered cell is not selected the
+ *   ray has ended with length t; otherwise tmax[a] += tdel[a].  At most ceil(max_length / cell_x) + ceil(max_length
+ *   / cell_y) + ceil(max_length / cell_z) + 3 steps (which must stay below 2^31), after which a ray counts as capped.
+ * Outputs (host or device): hist[n_batch][n_bins] = the ended rays with np.digitize(t, edges) - 1 == i (half-open
+ *   bins, other lengths dropped; at most 4096 bins); stats[n_batch][4] = {n_sel, n_ended, n_capped, n_escaped}; and
+ *   where not NULL lengths[n_batch][n_rays] (t; max_length for a capped ray), flags[n_batch][n_rays] (0 ended, 1
+ *   capped, 2 escaped), starts[n_batch][n_rays] (the flat index of the start cell in its box).  A box without a
+ *   selected cell is no error: zeros, and NaN / 255 / -1 per ray.  Counts are integers summed with integer atomics:
+ *   two calls give the same bytes, and a ray's result does not depend on n_rays.
+ * Errors: C21CM_VALUE_ERROR with a message (n_rays outside [1, 2^31 - 1]; edges not finite and increasing, or
+ *   edges[0] < 0; max_length not positive and finite; a threshold that is not finite; a NULL required array; a bad
+ *   shape); a non-finite field value is C21CM_INFINITY_OR_NAN_ERROR.  Nothing is written on an error. */
+int c21cm_bubble_sizes_grids(const float *field, int nx, int ny, int nz, int n_batch, long long row_pitch,
+                             const long long *batch_offsets, double Lx, double Ly, double Lz, double threshold,
+                             int select_below, long long n_rays, unsigned long long seed, int directions,
+                             int periodic_mask, double max_length, int n_bins, const double *edges, long long *hist,
+                             long long *stats, double *lengths, unsigned char *flags, long long *starts,
+                             void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
