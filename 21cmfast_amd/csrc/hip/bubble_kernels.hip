@@ -25,6 +25,7 @@
 #include "c21hip.h"
 #include "c21cm_abi.h"
 #include "philox.h"
+#include "wave_bits.h"
 
 namespace {
 constexpr int kBlock = 256;
@@ -96,15 +97,6 @@ __global__ __launch_bounds__(kBlock) void bubble_pack_kernel(const float *__rest
     }
 }
 
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ int wave_inclusive(int v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(v, d, 64);
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
 // one workgroup per box: chunk_off[b][c] = the set bits of the chunks before c, stats[b][0] = all of them.  A tile
 // of 1024 chunks holds at most 1024 x 4096 bits, so the scan inside a tile is in 32 bits and the carry in 64
 __global__ __launch_bounds__(kScanBlock) void bubble_scan_kernel(const int *__restrict__ chunk_sum, int n_chunks,
@@ -147,24 +139,6 @@ __global__ __launch_bounds__(kBlock) void bubble_prefix_kernel(const unsigned lo
     const int v = in ? __popcll(mask[(long long)b * words_per_box + g]) : 0;
     const int incl = wave_inclusive(v, lane);
     if (in) prefix[(long long)b * words_per_box + g] = chunk_off[(long long)b * n_chunks + c] + (incl - v);
-}
-
-// the position of the j-th set bit of x (0 <= j < popcount(x))
-__device__ __forceinline__ int select_bit(unsigned long long x, int j) {
-    int pos = 0;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned long long lo = x & ((1ull << s) - 1ull);
-        const int c = __popcll(lo);
-        if (j >= c) {
-            j -= c;
-            x >>= s;
-            pos += s;
-        } else {
-            x = lo;
-        }
-    }
-    return pos;
 }
 
 // One wave owns a contiguous run of rays and hands them to its lanes as they fall idle: ray lengths differ by orders

@@ -924,6 +924,34 @@ typedef struct c21hip_bubble_walk_args {
 /* the rays of every box: the estimator of c21cm_bubble_sizes_grids (include/c21cm_grid.h) */
 int c21hip_bubble_walk(const c21hip_bubble_walk_args *a, void *stream);
 
+/* ---- cluster_kernels.hip : friends-of-friends clusters of boxes and lightcone chunks (cluster_driver.c) ---- */
+/* From the mask of c21hip_bubble_pack: label[b][c] = the smallest flat index of the cluster of cell c (adjacency as
+ * c21cm_bubble_clusters_grids writes it down), -1 where c is not selected; size[b][r] = the cells of the cluster with
+ * root r, 0 at every other cell.  nx ny nz < 2^31.  Three launches: init, merge, count (which flattens) */
+int c21hip_cluster_label(const unsigned long long *mask, int nx, int ny, int nz, int n_batch, int connectivity,
+                         int periodic_mask, int *label, int *size, void *stream);
+/* root_mask: the layout of the pack's mask, a bit set where label[b][c] == c; chunk_sum as the pack leaves it, so
+ * that c21hip_bubble_rank counts and ranks the roots */
+int c21hip_cluster_roots(const int *label, int nx, int ny, int nz, int n_batch, unsigned long long *root_mask,
+                         int *chunk_sum, void *stream);
+typedef struct c21hip_cluster_emit_args {
+    const unsigned long long *root_mask;
+    const long long *prefix;     /* of root_mask, by c21hip_bubble_rank */
+    const long long *n_clusters; /* [n_batch][4], entry 0 as c21hip_bubble_rank left it for root_mask */
+    const int *size;
+    int nx, ny, nz, n_batch;
+    int n_bins;
+    const long long *edges;         /* device, n_bins + 1 */
+    unsigned long long *hist_n;     /* [n_batch][n_bins], zeroed by the caller */
+    unsigned long long *hist_cells; /* [n_batch][n_bins], zeroed by the caller */
+    unsigned long long *best;       /* [n_batch], zeroed by the caller */
+    long long *stats;               /* [n_batch][4]: n_sel as c21hip_bubble_rank left it; the other three are written */
+    long long max_clusters;
+    long long *roots, *sizes; /* [n_batch][max_clusters], filled with -1 / 0 by the caller; or both NULL */
+} c21hip_cluster_emit_args;
+/* (root, size) of the clusters in ascending root, the two histograms, the four stats */
+int c21hip_cluster_emit(const c21hip_cluster_emit_args *a, void *stream);
+
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */
 typedef struct c21hip_ts_args { /* the scalars of c21cm_ts_spec, passed by value */

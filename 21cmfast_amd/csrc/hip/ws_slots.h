@@ -409,6 +409,15 @@ enum c21_ws_slot {
     WS_BU_PREFIX, /* set bits per chunk of words, their exclusive scan, set bits before every word */
     WS_BU_OUT,    /* histogram, counts, and the per-ray outputs that were asked for */
     WS_BU_FLAG,
+    /* ---- cluster_driver.c ---- */
+    WS_BC_TAB,    /* histogram edges, batch offsets */
+    WS_BC_IN,     /* staged host field */
+    WS_BC_MASK,   /* the selection mask and the root mask, one bit per cell each */
+    WS_BC_PREFIX, /* set bits per chunk of words, their exclusive scan, set bits before every word */
+    WS_BC_LABEL,  /* int32 per cell: the root of its cluster */
+    WS_BC_SIZE,   /* int32 per cell: the cells of the cluster rooted there */
+    WS_BC_OUT,    /* stats, histograms, root counts, largest-cluster keys, and the cluster lists that were asked for */
+    WS_BC_FLAG,
 
     WS_COUNT
 };

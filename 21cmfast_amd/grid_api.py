@@ -1522,3 +1522,67 @@ def bubble_sizes(field, shape, lengths, edges, *, threshold=0.5, select_below=Tr
     if return_rays:
         return hist, stats, lengths_out, flags, starts
     return hist, stats
+
+
+def bubble_clusters(field, shape, edges, *, threshold=0.5, select_below=True, connectivity=1,
+                    periodic=(True, True, True), offsets=(0,), row_pitch=None, return_labels=False, max_clusters=0,
+                    stream=None):
+    """Friends-of-friends clusters of the selected cells of ``len(offsets)`` boxes of ``shape`` = (nx, ny, nz) cells
+    read from the float32 array ``field`` (the layout of ``power_spectrum``).  Cells with ``v < threshold``
+    (``select_below``) or ``v >= threshold`` are joined to their neighbours: ``connectivity`` 1, 2, 3 = faces, and
+    edges, and corners (6, 18, 26 neighbours), wrapping on the ``periodic`` axes.  ``edges``: the n_bins + 1 integer
+    histogram edges in cells, the first >= 1.  Returns ``(hist_n, hist_cells, stats)``: int64 (n_batch, n_bins) the
+    clusters per size bin and their cells, and (n_batch, 4) = n_selected, n_clusters, the cells of the largest cluster,
+    its root (the smallest flat index of a cluster's cells; -1 without a selected cell); with ``return_labels`` also
+    ``labels`` int32 (n_batch, nx ny nz), the root of every cell's cluster or -1; with ``max_clusters`` > 0 also
+    ``(roots, sizes)`` int64 (n_batch, max_clusters), the first clusters in ascending root, padded with -1 / 0
+    (``stats`` keeps the true count).  numpy for numpy input, torch on the field's device for a torch CUDA field.
+    The estimator is written down at ``c21cm_bubble_clusters_grids`` (include/c21cm_grid.h)."""
+    nx, ny, nz = (int(x) for x in shape)
+    row_pitch = nz if row_pitch is None else int(row_pitch)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_batch = len(offsets)
+    _f32_dense(field, "field")
+    size = int(np.prod(field.shape, dtype=np.int64))
+    if n_batch < 1 or offsets.min() < 0 or offsets.max() + (nx * ny - 1) * row_pitch + nz > size:
+        raise ValueError("the boxes do not lie inside the field")
+    if nx * ny * nz >= 2**31:
+        raise ValueError("a box must have fewer than 2^31 cells")
+    edges = np.ascontiguousarray(edges, np.int64)
+    if edges.ndim != 1 or edges.size < 2:
+        raise ValueError("edges must be a 1-D array of at least 2 values")
+    n_bins = len(edges) - 1
+    connectivity = int(connectivity)
+    if connectivity not in (1, 2, 3):
+        raise ValueError("connectivity must be 1, 2 or 3")
+    max_clusters = int(max_clusters)
+    if max_clusters < 0:
+        raise ValueError("max_clusters must be >= 0")
+    px, py, pz = (bool(p) for p in periodic)
+    labels = roots = sizes = None
+    if _is_torch(field):
+        import torch
+
+        def empty(shape_, dtype):
+            return torch.empty(shape_, dtype=getattr(torch, dtype), device=field.device)
+    else:
+        def empty(shape_, dtype):
+            return np.empty(shape_, dtype)
+    hist_n, hist_cells = empty((n_batch, n_bins), "int64"), empty((n_batch, n_bins), "int64")
+    stats = empty((n_batch, 4), "int64")
+    if return_labels:
+        labels = empty((n_batch, nx * ny * nz), "int32")
+    if max_clusters:
+        roots, sizes = empty((n_batch, max_clusters), "int64"), empty((n_batch, max_clusters), "int64")
+    lib = load()
+    check(lib.c21cm_bubble_clusters_grids(
+        _vptr(field), nx, ny, nz, n_batch, row_pitch, offsets.ctypes.data_as(C.c_void_p), float(threshold),
+        int(bool(select_below)), connectivity, px | (py << 1) | (pz << 2), n_bins, edges.ctypes.data_as(C.c_void_p),
+        _vptr(hist_n), _vptr(hist_cells), _vptr(stats), _vptr(labels), max_clusters, _vptr(roots), _vptr(sizes),
+        _stream(stream)), "c21cm_bubble_clusters_grids")
+    out = (hist_n, hist_cells, stats)
+    if return_labels:
+        out += (labels,)
+    if max_clusters:
+        out += (roots, sizes)
+    return out

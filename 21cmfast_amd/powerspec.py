@@ -20,7 +20,8 @@ lightcone (``csrc/hip/moments_kernels.hip``).  ``get_bispectrum`` and ``lightcon
 statistic, the FFT estimator over shells in |k| (``csrc/hip/bispectrum_kernels.hip``; its spec is
 ``tests/bispectrum_reference.py``).  ``get_bubble_sizes`` and ``lightcone_bubble_sizes`` are the morphological
 statistic, the mean-free-path bubble size distribution traced ray by ray (``csrc/hip/bubble_kernels.hip``; its
-spec is ``tests/bubble_reference.py``).
+spec is ``tests/bubble_reference.py``); ``get_bubble_clusters`` and ``lightcone_bubble_clusters`` label its
+friends-of-friends clusters (``csrc/hip/cluster_kernels.hip``; spec ``tests/cluster_reference.py``).
 
 Arrays may be numpy (results are numpy) or torch CUDA tensors (results are torch tensors on the same
 device; the field never visits the host).  Argument errors are ``ValueError``; a non-finite field value
@@ -855,5 +856,221 @@ def lightcone_bubble_sizes(lightcone, cell_size, *, chunk_length=None, chunk_sta
                         kw.get("max_length"), L)
     edges = bubble_edges(shape, L, kw.get("bins", 64), kw.get("log_bins", True), args["max_length"])
     res = _bubble_result(_f32(lightcone), shape, L, edges, args, starts, ns, kw.get("return_rays", False))
+    res.chunk_starts, res.redshifts = starts, z
+    return res
+
+
+CLUSTER_DEFAULT_CAPACITY = 2**20  # clusters per box the first call of get_bubble_clusters makes room for
+
+
+def cluster_edges(shape, bins=32, log_bins=True) -> np.ndarray:
+    """The size edges, in cells, ``get_bubble_clusters`` uses for a grid of ``shape`` with N cells: an int gives
+    ``np.unique(np.ceil(np.geomspace(1, N + 1, bins + 1)))`` (``np.linspace`` without ``log_bins``) as int64, so a
+    small box may get fewer bins than asked for; an array is taken as integer edges.  Checked either way: increasing,
+    the first edge >= 1, 1 to 4096 bins."""
+    n_cells = int(np.prod([int(n) for n in shape], dtype=np.int64))
+    if np.ndim(bins) == 0:
+        if isinstance(bins, (bool, np.bool_)) or int(bins) != bins:
+            raise ValueError("bins must be an integer or an array of edges")
+        if int(bins) < 1:
+            raise ValueError(f"bins must be >= 1, got {int(bins)}")
+        space = np.geomspace if log_bins else np.linspace
+        e = np.unique(np.ceil(space(1, n_cells + 1, int(bins) + 1))).astype(np.int64)
+    else:
+        raw = np.asarray(bins)
+        if raw.ndim != 1 or raw.size < 2:
+            raise ValueError("bins must be a 1-D array of at least 2 edges")
+        if raw.dtype.kind not in "iu" and not (np.all(np.isfinite(raw)) and np.all(raw == np.round(raw))):
+            raise ValueError("cluster size edges must be integers (cells)")
+        e = raw.astype(np.int64)
+        if np.any(np.diff(e) <= 0):
+            raise ValueError("bins must be increasing")
+    if not 1 <= len(e) - 1 <= BUBBLE_MAX_BINS:
+        raise ValueError(f"a cluster size distribution takes 1 to {BUBBLE_MAX_BINS} bins, got {len(e) - 1}")
+    if e[0] < 1:
+        raise ValueError("the first edge must be >= 1")
+    return e
+
+
+@dataclass
+class BubbleClusters:
+    """What ``get_bubble_clusters`` and ``lightcone_bubble_clusters`` return (the latter with a leading chunk axis on
+    everything but the edges and ``r_eff``): ``edges`` (n_bins + 1,) int64 in cells; ``volume_edges`` = edges V_cell;
+    ``r_eff`` (n_bins,) the radius of the sphere with the volume sqrt(e_i e_{i+1}) V_cell; ``hist_n`` int64 clusters
+    per bin and ``hist_cells`` their cells; ``volume_fraction`` = hist_cells / n_selected (NaN without a selected
+    cell); ``n_selected`` cells, ``n_clusters``; ``largest_cells``, ``largest_root`` (flat cell index, -1 without a
+    selected cell) and ``largest_fraction`` = largest_cells / n_selected, the percolation order parameter;
+    ``filling_fraction`` = n_selected / cells; ``mean_volume`` = n_selected V_cell / n_clusters; with
+    ``return_labels`` ``labels`` int32 shaped as the box, the root of every cell's cluster or -1; with
+    ``return_clusters`` ``roots``, ``sizes`` (cells) and ``volumes`` = sizes V_cell in ascending root; for a
+    lightcone ``chunk_starts`` and ``redshifts``."""
+
+    edges: object
+    volume_edges: object
+    r_eff: object
+    hist_n: object
+    hist_cells: object
+    volume_fraction: object
+    n_selected: object
+    n_clusters: object
+    largest_cells: object
+    largest_root: object
+    largest_fraction: object
+    filling_fraction: object
+    mean_volume: object
+    labels: object = None
+    roots: object = None
+    volumes: object = None
+    sizes: object = None
+    chunk_starts: np.ndarray | None = None
+    redshifts: np.ndarray | None = None
+
+
+def _cluster_args(threshold, select, connectivity, periodic, return_clusters, max_clusters):
+    if select not in ("below", "above"):
+        raise ValueError("select must be 'below' (v < threshold) or 'above' (v >= threshold)")
+    if isinstance(threshold, (bool, np.bool_)) or np.ndim(threshold) != 0 or not np.isfinite(float(threshold)):
+        raise ValueError("threshold must be a finite number")
+    if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (6, 18, 26):
+        raise ValueError("connectivity must be 6 (faces), 18 (and edges) or 26 (and corners)")
+    if np.ndim(periodic) == 0:
+        periodic = (bool(periodic),) * 3
+    else:
+        periodic = tuple(bool(p) for p in periodic)
+        if len(periodic) != 3:
+            raise ValueError("periodic must be a bool or three bools")
+    if max_clusters is not None:
+        if isinstance(max_clusters, (bool, np.bool_)) or int(max_clusters) != max_clusters or int(max_clusters) < 1:
+            raise ValueError("max_clusters must be None or an integer >= 1")
+        max_clusters = int(max_clusters)
+    return dict(threshold=float(threshold), select_below=select == "below",
+                connectivity={6: 1, 18: 2, 26: 3}[connectivity], periodic=periodic), bool(return_clusters), max_clusters
+
+
+def _cluster_result(f, shape, cell_volume, edges, args, offsets, row_pitch, return_labels, return_clusters,
+                    max_clusters):
+    def call(capacity):
+        return api.bubble_clusters(f, shape, edges, offsets=offsets, row_pitch=row_pitch,
+                                   return_labels=return_labels, max_clusters=capacity, **args)
+
+    capacity = 0
+    if return_clusters:
+        capacity = CLUSTER_DEFAULT_CAPACITY if max_clusters is None else max_clusters
+    out = call(capacity)
+    stats = out[2]
+    most = int(stats[:, 1].max())
+    if return_clusters and max_clusters is None and most > capacity:
+        capacity = most
+        out = call(capacity)
+        stats = out[2]
+    hist_n, hist_cells = out[:2]
+    n_cells = float(int(shape[0]) * int(shape[1]) * int(shape[2]))
+    centre = np.sqrt(edges[:-1].astype(np.float64) * edges[1:].astype(np.float64)) * cell_volume
+    n_sel, n_cl, big = stats[:, 0], stats[:, 1], stats[:, 2]
+    if _is_torch(hist_n):
+        import torch
+
+        f64 = torch.float64
+
+        def const(v):
+            # a tensor divisor or factor: by a Python scalar torch may multiply with the reciprocal
+            return torch.full((), v, dtype=f64, device=hist_n.device)
+
+        def div(a, b):
+            return a.to(f64) / b.to(f64)  # 0 / 0 = NaN
+
+        def as_int(e):
+            return torch.from_numpy(np.asarray(e, np.int64)).to(hist_n.device)
+    else:
+        def const(v):
+            return np.float64(v)
+
+        def div(a, b):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return a.astype(np.float64) / b.astype(np.float64)
+
+        def as_int(e):
+            return np.asarray(e, np.int64)
+
+    def f64_of(a):
+        return a.to(f64) if _is_torch(a) else a.astype(np.float64)
+
+    res = BubbleClusters(
+        edges=as_int(edges), volume_edges=_edges_like(edges.astype(np.float64) * cell_volume, hist_n),
+        r_eff=_edges_like(np.cbrt(3.0 * centre / (4.0 * np.pi)), hist_n), hist_n=hist_n, hist_cells=hist_cells,
+        volume_fraction=div(hist_cells, n_sel[:, None]), n_selected=n_sel, n_clusters=n_cl, largest_cells=big,
+        largest_root=stats[:, 3], largest_fraction=div(big, n_sel), filling_fraction=f64_of(n_sel) / const(n_cells),
+        mean_volume=div(n_sel, n_cl) * const(cell_volume))
+    rest = list(out[3:])
+    if return_labels:
+        res.labels = rest.pop(0).reshape((len(offsets),) + tuple(int(n) for n in shape))
+    if return_clusters:
+        keep = min(most, capacity)  # the largest count over the boxes: shorter lists stay padded with -1 / 0
+        res.roots, res.sizes = rest[0][:, :keep], rest[1][:, :keep]
+        res.volumes = f64_of(res.sizes) * const(cell_volume)
+    return res
+
+
+_CLUSTER_PER_BOX = ("hist_n", "hist_cells", "volume_fraction", "n_selected", "n_clusters", "largest_cells",
+                    "largest_root", "largest_fraction", "filling_fraction", "mean_volume", "labels", "roots",
+                    "volumes", "sizes")
+
+
+def get_bubble_clusters(field, boxlength, *, threshold=0.5, select="below", connectivity=6, periodic=True, bins=32,
+                        log_bins=True, return_labels=False, return_clusters=False,
+                        max_clusters=None) -> BubbleClusters:
+    """The friends-of-friends clusters (Friedrich et al. 2011) of the 3-D ``field`` in a box of ``boxlength`` (a
+    scalar or 3 lengths): the cells with ``v < threshold`` (``select="below"``: for a neutral fraction the ionised
+    phase) or ``v >= threshold`` (``"above"``) are joined to their selected neighbours -- ``connectivity`` 6 (faces),
+    18 (and edges) or 26 (and corners), across the faces of the ``periodic`` axes (a bool or three) -- and the
+    clusters are counted by size into ``bins`` (``cluster_edges``: by default up to 32 log-spaced bins in cells), with
+    the number of clusters, the largest one and its share of the selected cells (the percolation order parameter).
+    A cluster is named by its root, the smallest flat index of its cells.  ``return_labels`` adds the root of every
+    cell's cluster (-1 where the cell is not selected); ``return_clusters`` adds the roots, sizes and volumes of the
+    clusters in ascending root: all of them with ``max_clusters=None`` (one call with room for 2^20 clusters and, if
+    the box has more, one more with the count), or the first ``max_clusters``.  Every count is an integer fixed by
+    the mask: two calls give the same bytes.  A field without a selected cell gives zeros, -1 and NaN fractions."""
+    _check_bubble_field(field)
+    shape = _shape(field)
+    L = _lengths(boxlength)
+    args, return_clusters, max_clusters = _cluster_args(threshold, select, connectivity, periodic, return_clusters,
+                                                        max_clusters)
+    edges = cluster_edges(shape, bins, log_bins)
+    cell_volume = float(np.prod([l / n for l, n in zip(L, shape)]))
+    res = _cluster_result(_f32(field), shape, cell_volume, edges, args, (0,), None, return_labels, return_clusters,
+                          max_clusters)
+    for name in _CLUSTER_PER_BOX:
+        v = getattr(res, name)
+        if v is not None:
+            setattr(res, name, v[0])
+    return res
+
+
+def lightcone_bubble_clusters(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None,
+                              **kw) -> BubbleClusters:
+    """Friends-of-friends clusters of the chunks of a rectilinear ``lightcone`` (nx, ny, n_slices) of cells of
+    ``cell_size`` [Mpc], chunked as ``lightcone_bubble_sizes`` chunks it; all chunks go through one library call and
+    share the edges.  The transverse axes are periodic and the line of sight is open, so ``periodic`` is not a
+    keyword here; the others are those of ``get_bubble_clusters``.  Every per-box entry carries a leading chunk
+    axis; the cluster lists are padded with -1 / 0 to the largest count over the chunks."""
+    _check_bubble_field(lightcone, "lightcone")
+    if "periodic" in kw:
+        raise ValueError("periodic is fixed for a lightcone: the transverse axes are, the line of sight is not")
+    unknown = set(kw) - {"threshold", "select", "connectivity", "bins", "log_bins", "return_labels", "return_clusters",
+                         "max_clusters"}
+    if unknown:
+        raise ValueError(f"unknown keywords: {sorted(unknown)}")
+    nx, ny, ns = _shape(lightcone)
+    dx = float(cell_size)
+    if not (np.isfinite(dx) and dx > 0):
+        raise ValueError("cell_size must be positive and finite")
+    n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
+    shape = (nx, ny, n)
+    args, return_clusters, max_clusters = _cluster_args(
+        kw.get("threshold", 0.5), kw.get("select", "below"), kw.get("connectivity", 6), (True, True, False),
+        kw.get("return_clusters", False), kw.get("max_clusters"))
+    edges = cluster_edges(shape, kw.get("bins", 32), kw.get("log_bins", True))
+    res = _cluster_result(_f32(lightcone), shape, dx ** 3, edges, args, starts, ns, kw.get("return_labels", False),
+                          return_clusters, max_clusters)
     res.chunk_starts, res.redshifts = starts, z
     return res

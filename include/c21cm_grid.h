@@ -1093,6 +1093,38 @@ int c21cm_bubble_sizes_grids(const float *field, int nx, int ny, int nz, int n_b
                              long long *stats, double *lengths, unsigned char *flags, long long *starts,
                              void *stream);
 
+/* ---- Friends-of-friends clusters of boxes and lightcone chunks (Friedrich et al. 2011; the spec is
+ * tests/cluster_reference.py) ----
+ * The layout of c21cm_bubble_sizes_grids: n_batch boxes of nx x ny x nz float32 cells read at batch_offsets[b] with
+ * row_pitch, z fastest.  Everything below is an integer and a function of the mask alone.
+ * Selection: a cell is selected iff (double)v < threshold (select_below = 1) or >= threshold (0).
+ * Adjacency: cells p and q of one box are adjacent iff q = p + o for an offset o in {-1, 0, 1}^3, o != 0, with at
+ *   most `connectivity` non-zero components: connectivity 1, 2, 3 gives 6, 18, 26 neighbours.  On an axis a whose bit
+ *   is set in periodic_mask (bit 0 x, 1 y, 2 z) the sum wraps modulo n_a; through an open face there is no neighbour.
+ *   On a periodic axis with n_a = 1 the neighbour is the cell itself, with n_a = 2 both sides are the same cell.
+ * Clusters: a cluster is a class of the transitive closure of adjacency over the selected cells of a box.  Its root
+ *   is the smallest flat index (ix ny + iy) nz + iz among its cells, its size its number of cells; the clusters of a
+ *   box are numbered in ascending root.
+ * Outputs (host or device): stats[n_batch][4] = {n_selected, n_clusters, the size of the largest cluster, its root}
+ *   (ties take the smallest root; without a selected cell 0, 0, 0, -1); hist_n[n_batch][n_bins] = the clusters with
+ *   edges[i] <= size < edges[i + 1] and hist_cells[n_batch][n_bins] = the cells of those clusters (edges: host,
+ *   n_bins + 1 values, increasing, edges[0] >= 1; 1 to 4096 bins); where not NULL labels[n_batch][nx ny nz] (int32,
+ *   dense, C order) = the root of the cell's cluster, -1 where the cell is not selected; and, given as both or
+ *   neither, cluster_roots / cluster_sizes [n_batch][max_clusters]: the first min(n_clusters, max_clusters) clusters
+ *   in ascending root, the remaining entries -1 / 0.  n_clusters in stats is always the true count, so a caller sees
+ *   that its capacity was too small.  Sums are integer atomics: two calls give the same bytes.
+ * Errors: C21CM_VALUE_ERROR with a message (a NULL required pointer; a bad shape; nx ny nz >= 2^31; n_batch outside
+ *   [1, 65535]; row_pitch < nz; a negative offset; a threshold that is not finite; connectivity outside 1..3;
+ *   periodic_mask outside 0..7; n_bins outside [1, 4096]; edges not increasing or edges[0] < 1; only one of the
+ *   cluster arrays; max_clusters < 1 with them), all before any array but edges and batch_offsets is touched; a
+ *   non-finite field value is C21CM_INFINITY_OR_NAN_ERROR.  Nothing is written on an error. */
+int c21cm_bubble_clusters_grids(const float *field, int nx, int ny, int nz, int n_batch, long long row_pitch,
+                                const long long *batch_offsets, double threshold, int select_below,
+                                int connectivity, int periodic_mask, int n_bins, const long long *edges,
+                                long long *hist_n, long long *hist_cells, long long *stats, int *labels,
+                                long long max_clusters, long long *cluster_roots, long long *cluster_sizes,
+                                void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
