@@ -309,7 +309,9 @@ typedef struct {
 static int r0_direct(void);
 
 /* which R loop the last context set up (tests, timing tools): 1 fused, 2 fused recombination loop, 4 third
- * spectrum, 8 ... which is N_rec, 16 fourth spectrum (x_e + N_rec), 32 two radii per sweep */
+ * spectrum, 8 ... which is N_rec, 16 fourth spectrum (x_e + N_rec), 32 two radii per sweep; and, set by the
+ * finish of that call, 64: the Eulerian loops' cell-scale radius and post-loop ran as one sweep (eul_r0_fused).
+ * Written for the tests to read, never read by the library. */
 static int g_loop_flags;
 int c21cm_ionize_last_loop_flags(void) { return g_loop_flags; }
 
@@ -2184,6 +2186,7 @@ static int finish_first_cross(ion_ctx *c, const unsigned char *mask, int stars_r
     const c21cm_ionize_spec *s = c->s;
     if (c->fused && s->r_lowest == 0 && !c->sphere) return final_step(c, mask, stars_ready);
     if (eul_r0_fused(c)) { /* one sweep: mask + cell-scale radius + post-loop (one_radius) */
+        g_loop_flags |= 64;
         c->r0_mask = mask;
         return one_radius(c, 0, NULL, -1);
     }

@@ -386,7 +386,8 @@ def ionize_shard_finish_keys(spec, cross_keys, density, n_ion=None, xe=None, Tne
 def ionize_last_loop_flags() -> int:
     """Which R loop the last ionisation call set up (c21cm_ionize_last_loop_flags): 1 fused, 2 fused
     recombination loop, 4 third spectrum in the barrier kernel, 8 ... which is the filtered N_rec, 16 a
-    fourth spectrum (x_e and filtered N_rec), 32 two radii per sweep."""
+    fourth spectrum (x_e and filtered N_rec), 32 two radii per sweep, 64 the Eulerian loops' cell-scale radius and
+    post-loop ran as one sweep (set by the finish of that call)."""
     lib = load()
     lib.c21cm_ionize_last_loop_flags.restype = C.c_int
     return int(lib.c21cm_ionize_last_loop_flags())

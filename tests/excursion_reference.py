@@ -1,13 +1,17 @@
 """The excursion-set radius loop of ComputeIonizedBox in plain numpy float64, cell by cell.
 
 Restated from oracle/oracle_ionize.c (the radius loop :414-672, copy_filter_c2r :303-317, the clips
-:438-501, the barrier :621, the partial ionisation :649-669) for the three modes the loop's own kernels
-serve without a recombination model, mini-halos or a table:
+:438-501, the barrier :621, the partial ionisation :649-669) for the four modes the loop's own kernels
+serve without a recombination model or mini-halos:
 
   (a) Lagrangian two-grid: top-hat delta, exp-MFP n_ion, mass_dep_zeta floor at f_limit_acg;
   (b) the same with an x_e grid (use_ts_fluct): x_e filtered like delta, clipped to [0, 0.999],
       barrier f zeta > 1 - x_e, x_HI = 1 - f zeta - x_e;
-  (c) Eulerian closed form (FCOLL_ERFC): one sharp-k grid, erfc per cell, fix_mean.
+  (c) Eulerian closed form (FCOLL_ERFC): one sharp-k grid, erfc per cell, fix_mean;
+  (t) Eulerian with a per-radius table (FCOLL_TABLE_LINEAR, FCOLL_TABLE_EXP; :437-481, :551-556), with or
+      without an x_e grid: the extrema of the filtered delta BEFORE its clips, the table of the case over
+      those extrema -/+ 0.001, eval_table_f (:105-110) per cell and an exp for the ln-tables; everything
+      after f is mode (c)'s.  See "Tables" below.
 
 Transforms are np.fft.rfftn / irfftn on float64; the windows and |k| come from window_reference, which
 keeps the reference's float narrowings of k, R and kR.  Scalars that the reference holds in `float`
@@ -18,7 +22,8 @@ What the loop decides is stated through the MARGIN of a cell at a radius,
     m = f zeta - (1 - x_e),      the barrier (:621) is m > 0,
 
 with f = max(s, 0) / (rho_crit Omega_b (1 + delta)) floored at f_limit_acg in modes (a), (b) and
-f = erfc(...) mean_f_coll / <erfc(...)> in mode (c).  The radii are streamed from the largest down and
+f = erfc(...) mean_f_coll / <erfc(...)> in mode (c), f = table(delta) mean_f_coll / <table(delta)> floored
+at f_limit_acg under mass_dep_zeta in mode (t).  The radii are streamed from the largest down and
 only running results are kept, never one grid per radius.
 
 Radius 0 is where this module departs from the oracle on purpose: no window is applied there, and where the
@@ -32,8 +37,20 @@ margin by.  A cell whose margins stay clear of 0 by t = FACTOR * E32 at the radi
 every correct float32 implementation gives it the same flag and the same first-crossing radius.  The
 rest -- a sliver that this module alone names -- may take either of two candidates, nothing else.
 
+Tables.  The table of a case is a plain function (mode, r_index, dmin, dmax) -> float32[NDELTA_TABLE]
+(Inputs.table): install_table() wraps it as the callback the library and the oracle call, and both chains here
+call it with their own extrema.  The float32 chain keeps the filtered delta and the stored f as float32, takes
+its extrema from its own float32 delta and evaluates the exponential of the ln-tables in float32: the library
+evaluates that exponential to float accuracy by design (exp_f32acc) and upstream stores f in a float grid.
+The per-radius mean of a ln-table is therefore granted FACTOR * E32(mean) + 2^-23: the second term is the worst
+case of a one-sided float-accuracy error in every exponential -- derived, not measured.  smooth_table() is
+the table of every case: smooth and analytic, WITHOUT the -40 floor of the real ln-tables.  A cell on such a
+cliff moves by the whole step under a float32 change of delta, which inflates E32 for the whole box until
+t = FACTOR * E32 decides nothing and the accounting stops meaning anything.
+
 check_outputs() is the cell-by-cell accounting both test_excursion_reference_host.py (on the float32
-chain's own outputs and on corrupted copies) and test_gpu_excursion_cells.py (on the device's) apply.
+chain's own outputs and on corrupted copies) and test_gpu_excursion_cells.py / test_gpu_table_cells.py (on
+the device's) apply.
 """
 
 import math
@@ -46,7 +63,10 @@ F32 = np.float32
 FRACT_FLOAT_ERR = 1e-7  # Constants.h
 FACTOR = 4  # what test_gpu_pass_x_windows.py grants a device over numpy's float32 chain
 FLAG_CAP, RADIUS_CAP = 1e-4, 1e-3  # largest shares of cells the accounting may leave undecided
-FCOLL_STARS, FCOLL_ERFC = 0, 1
+FCOLL_STARS, FCOLL_ERFC, FCOLL_TABLE_LINEAR, FCOLL_TABLE_EXP = 0, 1, 2, 3
+TABLE_MODES = (FCOLL_TABLE_LINEAR, FCOLL_TABLE_EXP)
+NDELTA_TABLE = 400  # include/c21cm_grid.h
+EXP_F32ACC = 2.0 ** -23  # a one-sided float-accuracy error in every exponential, as a relative error of their mean
 
 
 def _f(x):
@@ -75,6 +95,45 @@ def fgtrm_bias_fast(spec, r, dens, narrow):
     return f.astype(F32).astype(np.float64) if narrow else f
 
 
+def smooth_table(mode, r_index, dmin, dmax):
+    """The table of every case here: 0.03 (1 + max(x, -0.999))^1.5 / (1 + 0.05 r) at NDELTA_TABLE knots from
+    dmin to dmax (the one of test_gpu_ionize.py's banded tests), its logarithm for FCOLL_TABLE_EXP; knots
+    narrowed to float, as the library's table buffer holds them.  Smooth on purpose: no floor, no cliff
+    (module docstring, "Tables")."""
+    x = dmin + (dmax - dmin) / (NDELTA_TABLE - 1.0) * np.arange(NDELTA_TABLE)
+    y = 0.03 * (1 + np.maximum(x, -0.999)) ** 1.5 / (1 + 0.05 * r_index)
+    return (np.log(y) if mode == FCOLL_TABLE_EXP else y).astype(F32)
+
+
+def eval_table_f(x, x_min, x_width, y):
+    """oracle_ionize.c:105-110 on an array of doubles: the (float)idx in the knot position, the float knots
+    read as doubles."""
+    idx = np.floor((x - x_min) / x_width).astype(np.int64)
+    assert idx.min() >= 0 and idx.max() < NDELTA_TABLE - 1, (idx.min(), idx.max())
+    point = (x - (x_min + x_width * idx.astype(F32).astype(np.float64))) / x_width
+    y = y.astype(np.float64)
+    return y[idx] * (1 - point) + y[idx + 1] * point
+
+
+def install_table(spec, inp, structs, calls=None):
+    """spec.table_fn = the case's table as the callback the library and the oracle call; `calls` collects
+    (r_index, dmin, dmax) of every call.  The callback object is kept on the spec, which points at it."""
+    mode = spec.fcoll_mode
+
+    def table_fn(r_index, dmin, dmax, table, user):
+        y = inp.table(mode, r_index, dmin, dmax)
+        assert y.dtype == F32 and y.shape == (NDELTA_TABLE,)
+        for i in range(NDELTA_TABLE):
+            table[i] = y[i]
+        if calls is not None:
+            calls.append((r_index, dmin, dmax))
+        return 0
+
+    assert structs.NDELTA_TABLE == NDELTA_TABLE
+    spec._table_cb = structs.TABLE_FN(table_fn)
+    spec.table_fn = spec._table_cb
+
+
 _NUMPY_KEEPS_FLOAT32 = np.fft.rfftn(np.zeros((2, 2, 2), F32)).dtype == np.complex64
 
 
@@ -97,10 +156,11 @@ def _irfftn(A, shape):
 
 
 class Inputs:
-    """density, n_ion (modes a, b), xe and Tneutral (mode b): float32 grids, read only."""
+    """density, n_ion (modes a, b), xe and Tneutral (mode b, mode t with an x_e grid): float32 grids, read
+    only; table (mode t): the function (mode, r_index, dmin, dmax) -> float32[NDELTA_TABLE]."""
 
-    def __init__(self, density, n_ion=None, xe=None, Tneutral=None):
-        self.density, self.n_ion, self.xe, self.Tneutral = density, n_ion, xe, Tneutral
+    def __init__(self, density, n_ion=None, xe=None, Tneutral=None, table=None):
+        self.density, self.n_ion, self.xe, self.Tneutral, self.table = density, n_ion, xe, Tneutral, table
         for a in (density, n_ion, xe, Tneutral):
             if a is not None:
                 assert a.dtype == F32 and a.shape == density.shape
@@ -113,9 +173,10 @@ class Inputs:
 
 def _supported(spec, inp):
     lag = spec.fcoll_mode == FCOLL_STARS
-    assert lag or spec.fcoll_mode == FCOLL_ERFC
+    assert lag or spec.fcoll_mode == FCOLL_ERFC or spec.fcoll_mode in TABLE_MODES
     assert not (spec.recomb_model or spec.use_mini_halos or spec.ionise_entire_sphere or spec.r_lowest)
     assert spec.first_snapshot and (inp.n_ion is not None) == lag
+    assert (inp.table is not None) == (spec.fcoll_mode in TABLE_MODES)
     assert bool(spec.use_ts_fluct) == (inp.xe is not None)
     assert inp.density.shape == (spec.hii_dim, spec.hii_dim, spec.hii_dim_z)
     return lag
@@ -129,6 +190,7 @@ class _Chain:
         self.lag = _supported(spec, inp)
         self.real = F32 if f32 else np.float64
         self.shape = inp.density.shape
+        self.table_range = {}  # Eulerian modes: radius index -> (min - 0.001, max + 0.001) of the filtered delta
         # prepare_box, :285-301: scale, clip, transform (the 1 / N is numpy's irfftn's)
         self.delta0 = np.clip(inp.density.astype(np.float64) * spec.photoncons_adjustment_factor, -1.0, 1e6)
         self.grids = {"delta": self.delta0}
@@ -149,19 +211,40 @@ class _Chain:
         assert g.dtype == self.real
         return g.astype(np.float64)
 
+    def table_f(self, r, delta, table_range=None):
+        """f_coll of a table mode over the clipped `delta` (doubles holding this chain's grid values): the
+        case's table over this chain's own extrema -/+ 0.001, eval_table_f, and for a ln-table the
+        exponential -- of a double in the float64 chain, of a float in float32 in the float32 chain."""
+        lo, hi = table_range or self.table_range[r]
+        y = self.inp.table(self.spec.fcoll_mode, r, lo, hi)
+        assert y.dtype == F32 and y.shape == (NDELTA_TABLE,)
+        f = eval_table_f(delta, lo, (hi - lo) / (NDELTA_TABLE - 1.0), y)
+        if self.spec.fcoll_mode == FCOLL_TABLE_EXP:
+            f = np.exp(f.astype(F32)).astype(np.float64) if self.f32 else np.exp(f)
+        return f
+
     def radius(self, r, W_hii, W_stars):
         """(margin, f_coll_grid_mean after the floor, f zeta, x_e) of radius index r; the per-cell
         arithmetic is the oracle's: double expressions of float grids."""
         s = self.spec
         delta = self.filtered("delta", r, W_hii)
         if not self.lag:
-            delta = np.clip(delta, -1.0, 1e6)  # clip_and_get_extrema, :438-448
+            # clip_and_get_extrema, :438-449: the extrema of the grid as filtered, then the clip
+            self.table_range[r] = (float(delta.min()) - 0.001, float(delta.max()) + 0.001)
+            delta = np.clip(delta, -1.0, 1e6)
         delta = np.maximum(delta, _f(-1.0 + FRACT_FLOAT_ERR) if self.f32 else -1.0 + FRACT_FLOAT_ERR)  # :492
         if self.lag:
             f = np.maximum(self.filtered("stars", r, W_stars), 0.0)  # :500
-        else:
+            total = f.sum(dtype=np.float64)
+        elif s.fcoll_mode == FCOLL_ERFC:
             f = fgtrm_bias_fast(s, r, delta, self.f32)  # :547-549, stored as float at :556
-        mean = float(f.sum(dtype=np.float64)) / f.size
+            total = f.sum(dtype=np.float64)
+        else:
+            f = self.table_f(r, delta)  # :476-479, :551-554
+            total = f.sum(dtype=np.float64)  # :558 adds the double, :556 stores a float
+            if self.f32:
+                f = f.astype(F32).astype(np.float64)
+        mean = float(total) / f.size
         mean = max(mean, s.f_limit_acg if s.mass_dep_zeta else FRACT_FLOAT_ERR)  # :573-578
         if s.fix_mean:
             f = (s.mean_f_coll / mean) * f  # :586, :602
@@ -178,11 +261,15 @@ class _Chain:
         return fz - (1.0 - xe), mean, fz, xe
 
 
-def radius_loop(spec, inp, with_f32=False):
+def radius_loop(spec, inp, with_f32=False, table_range=None):
     """Radius indices from the largest down to 0: yields (r, float64 results, float32 results or None),
-    each the tuple of _Chain.radius.  The windows are formed once per radius for both chains."""
+    each the tuple of _Chain.radius.  The windows are formed once per radius for both chains.
+    `table_range`: a dict that the float64 chain fills, radius index -> (min - 0.001, max + 0.001) of its
+    filtered delta (the Eulerian modes)."""
     c64 = _Chain(spec, inp, False)
     c32 = _Chain(spec, inp, True) if with_f32 else None
+    if table_range is not None:
+        c64.table_range = table_range
     k = WR.k_magnitude(c64.shape, spec.box_len, spec.box_len_z)
     for r in range(spec.n_radii - 1, -1, -1):
         W_hii = W_stars = None
@@ -232,13 +319,13 @@ def e32(spec, inp):
 def xhi_float32_bound(spec, inp, mean0):
     """The largest deviation, over the box, of a float32 numpy evaluation of the radius-0 neutral fraction
     from the float64 one: the same expression of the inputs, no transform (radius 0 applies no window).
-    `mean0`: the float64 f_coll_grid_mean of radius 0, which the mean fix of mode (c) divides by."""
+    `mean0`: the float64 f_coll_grid_mean of radius 0, which the mean fix of modes (c) and (t) divides by."""
     d64 = inp.density.astype(np.float64) * spec.photoncons_adjustment_factor
     d32 = inp.density * F32(spec.photoncons_adjustment_factor)
     if spec.fcoll_mode == FCOLL_STARS:
         f64 = np.clip(inp.n_ion.astype(np.float64), 0, 1e20) / (spec.rhocrit_omb * (1 + d64))
         f32 = np.clip(inp.n_ion, 0, F32(1e20)) / (F32(spec.rhocrit_omb) * (F32(1) + d32))
-    else:
+    elif spec.fcoll_mode == FCOLL_ERFC:
         scale = 1 / _f(spec.growth_factor) / (math.sqrt(2) * math.sqrt(float(
             F32(spec.sigma_minmass) ** 2 - F32(spec.sigma_maxmass[0]) ** 2)))
         lo = -1.0 + FRACT_FLOAT_ERR
@@ -247,6 +334,23 @@ def xhi_float32_bound(spec, inp, mean0):
         fix = spec.mean_f_coll / mean0 if spec.fix_mean else 1.0
         f64 = np.where(x64 < 0, 1.0, erfcc(np.maximum(x64, 0.0))) * fix
         f32 = np.where(x32 < 0, F32(1), erfcc(np.maximum(x32, F32(0)))) * F32(fix)
+    else:
+        # mode (t): the table of radius 0 over the extrema of the clipped input (no window, no transform), the
+        # lookup and the exponential; in float32: knot position, weight, interpolation and exponential alike
+        lo = -1.0 + FRACT_FLOAT_ERR
+        x64 = np.clip(d64, -1.0, 1e6)
+        t_min, t_max = float(x64.min()) - 0.001, float(x64.max()) + 0.001
+        width = (t_max - t_min) / (NDELTA_TABLE - 1.0)
+        y = inp.table(spec.fcoll_mode, 0, t_min, t_max)
+        f64 = eval_table_f(np.maximum(x64, lo), t_min, width, y)
+        x32 = np.maximum(np.clip(d32, F32(-1), F32(1e6)), F32(lo))
+        idx = np.clip(np.floor((x32 - F32(t_min)) / F32(width)).astype(np.int64), 0, NDELTA_TABLE - 2)
+        point = (x32 - (F32(t_min) + F32(width) * idx.astype(F32))) / F32(width)
+        f32 = y[idx] * (F32(1) - point) + y[idx + 1] * point
+        if spec.fcoll_mode == FCOLL_TABLE_EXP:
+            f64, f32 = np.exp(f64), np.exp(f32)
+        fix = spec.mean_f_coll / mean0 if spec.fix_mean else 1.0
+        f64, f32 = f64 * fix, f32 * F32(fix)
     if spec.mass_dep_zeta:
         f64, f32 = np.maximum(f64, spec.f_limit_acg), np.maximum(f32, F32(spec.f_limit_acg))
     x64, x32 = 1.0 - f64 * spec.ion_eff_factor, F32(1) - f32 * F32(spec.ion_eff_factor)
@@ -266,9 +370,12 @@ class Restatement:
         hi = np.zeros(inp.density.shape, np.uint8)  # first crossing under m > +t
         lo = np.zeros(inp.density.shape, np.uint8)  # ... under m > -t
         self.f_coll_grid_mean = np.zeros(spec.n_radii)
-        for r, (m, mean, fz, xe), _ in radius_loop(spec, inp):
+        self.table_range = {}  # Eulerian modes: what the table callback of radius r is called with
+        self.margin_at_cross = np.zeros(inp.density.shape)  # the margin at the first crossing under m > +t
+        for r, (m, mean, fz, xe), _ in radius_loop(spec, inp, table_range=self.table_range):
             if on_margin is not None:
                 on_margin(r, m)
+            self.margin_at_cross = np.where((hi == 0) & (m > t), m, self.margin_at_cross)
             hi, lo = _cross(hi, m, r, t), _cross(lo, m, r, -t)
             self.f_coll_grid_mean[r] = mean
         self.cross_hi, self.cross_lo = hi, lo
@@ -292,7 +399,8 @@ class Restatement:
 def restate(spec, inp):
     """E32, then the restatement at t = FACTOR * E32.  Returns (Restatement, the dict of e32())."""
     e = e32(spec, inp)
-    ref = Restatement(spec, inp, FACTOR * e["margin"], FACTOR * e["mean"])
+    mean_tol = FACTOR * e["mean"] + (EXP_F32ACC if spec.fcoll_mode == FCOLL_TABLE_EXP else 0.0)
+    ref = Restatement(spec, inp, FACTOR * e["margin"], mean_tol)
     ref.xhi_tol = FACTOR * xhi_float32_bound(spec, inp, ref.f_coll_grid_mean[0])
     return ref, e
 
@@ -330,6 +438,68 @@ def make_case(workloads, mode, n, nz, r_max, seed):
     return workloads.ionize_spec(n, hii_dim_z=nz, r_bubble_max=r_max, use_ts_fluct=1), Inputs(density, n_ion, xe, Tn)
 
 
+# ---- mode (t): the boxes of test_gpu_table_cells.py, the smallest on which each kernel family of the table
+#      loops runs; test_excursion_reference_host.py holds each to the caps
+#      name: (table mode, nx = ny, nz, r_bubble_max, seed of the density, x_e grid, mass_dep_zeta)
+TABLE_CASES = {
+    "l-64": (FCOLL_TABLE_LINEAR, 64, 64, 20.0, 21, False, False),
+    "e-64": (FCOLL_TABLE_EXP, 64, 64, 20.0, 21, False, False),
+    "l-50": (FCOLL_TABLE_LINEAR, 50, 50, 20.0, 21, False, False),
+    "e-64x512": (FCOLL_TABLE_EXP, 64, 512, 9.0, 21, False, False),
+    "l-64x512": (FCOLL_TABLE_LINEAR, 64, 512, 9.0, 21, False, False),
+    # (32 x 32 lines are no box of the native passes: this one runs the library's transform route on long
+    # lines, the next one the 1024-point pass Z with the table sweep)
+    "e-32x1024": (FCOLL_TABLE_EXP, 32, 1024, 9.0, 21, False, False),
+    "e-64x1024": (FCOLL_TABLE_EXP, 64, 1024, 9.0, 21, False, False),
+    "ex-64x512": (FCOLL_TABLE_EXP, 64, 512, 9.0, 21, True, False),
+    "lx-64": (FCOLL_TABLE_LINEAR, 64, 64, 20.0, 21, True, False),
+    "em-64x512": (FCOLL_TABLE_EXP, 64, 512, 9.0, 21, False, True),
+}
+TABLE_MEAN_F_COLL_FACTOR = 1.6  # the mean fix rescales the table: this sets the ionised share
+TABLE_F_LIMIT_ACG = 1e-4  # with mass_dep_zeta
+
+
+def make_table_case(workloads, fmode, n, nz, r_max, seed, with_xe=False, mass_dep_zeta=False):
+    """(spec, Inputs) of a table box: the spec, table, x_e and T_k inputs of test_gpu_ionize.py's banded
+    table tests (x_e = 0.3 u^2, rng seed 5).  The spec carries no callback yet: install_table()."""
+    shape = (n, n, nz)
+    spec = workloads.ionize_spec(n, hii_dim_z=nz, mode=fmode, r_bubble_max=r_max, use_ts_fluct=int(with_xe))
+    spec.mean_f_coll *= TABLE_MEAN_F_COLL_FACTOR
+    if mass_dep_zeta:
+        spec.mass_dep_zeta = 1
+        spec.f_limit_acg = TABLE_F_LIMIT_ACG
+    density = workloads.density_field_numpy(shape, seed=seed)
+    xe = Tn = None
+    if with_xe:
+        rng = np.random.default_rng(5)
+        xe = (0.3 * rng.random(shape) ** 2).astype(F32)
+        Tn = (50 + 10 * rng.random(shape)).astype(F32)
+    return spec, Inputs(density, xe=xe, Tneutral=Tn, table=smooth_table)
+
+
+_restated_tables = {}
+
+
+def restated_table(workloads, key):
+    """A box of TABLE_CASES (by name) or any make_table_case() tuple, restated once per process:
+    (spec, Inputs, Restatement, e32 dict), shared by test_excursion_reference_host.py and
+    test_gpu_table_cells.py and read only -- but for spec.table_fn, which install_table() sets anew per use."""
+    if key not in _restated_tables:
+        spec, inp = make_table_case(workloads, *TABLE_CASES.get(key, key))
+        _restated_tables[key] = (spec, inp) + restate(spec, inp)
+    return _restated_tables[key]
+
+
+def table_caps_line(name, spec, ref, e):
+    fmode, n, nz, r_max, seed, with_xe, mdz = TABLE_CASES.get(name, name)
+    return (f"TABLE-CAPS {name}: {n}x{n}x{nz} {'ln-table' if fmode == FCOLL_TABLE_EXP else 'linear table'} x_e "
+            f"{'yes' if with_xe else 'no'} mass_dep_zeta {int(mdz)} r_bubble_max {r_max:g} seed {seed} n_radii "
+            f"{spec.n_radii}, E32 margin {e['margin']:.2e} mean {e['mean']:.2e}, flag-undecided "
+            f"{ref.flag_undecided_share:.2e}, radius-undecided {ref.radius_undecided_share:.2e}, ionised "
+            f"{float(ref.decided_flag.mean()):.2f}, crossings at {len(np.unique(ref.cross_hi))} radius indices, "
+            f"bounds: mean {ref.mean_tol:.2e}, x_HI {ref.xhi_tol:.2e}")
+
+
 def check_outputs(ref, out):
     """The cell-by-cell accounting.  `out`: neutral_fraction, z_reion (the single pass), first_cross,
     shard_neutral_fraction, shard_z_reion (shard_radii + shard_finish with world = 1), f_coll_grid_mean.
@@ -341,6 +511,8 @@ def check_outputs(ref, out):
         n = int(mask.sum())
         assert n == 0, f"{what}: {n} cells, first at {np.argwhere(mask)[:5].tolist()}"
 
+    # the banded sweeps of the Eulerian loops park 255 in an undecided cell until the next sweep settles it
+    bad("first_cross holds a marker (255)", fc == 255)
     # the single pass and the shard pair: cell for cell
     bad("single pass and shard pair differ in neutral_fraction", xhi != out["shard_neutral_fraction"])
     bad("single pass and shard pair differ in z_reion", zre != out["shard_z_reion"])

@@ -5,6 +5,9 @@ The three corruptions of test_accounting_bites_where_compare_does_not and the ol
   * 20 flipped flags at 64^3 (7.6e-5 of the cells) pass compare() -- asserted here;
   * a cleared z-line and a shifted 16 x 16 tile of the first-crossing grid never reach compare(): it takes
     no first-crossing grid, so it lets both through as well.
+
+The table modes (mode (t)) have their own three tests below: the oracle pin with the callback's extrema, the
+caps of every box of test_gpu_table_cells.py, and four single-cell or single-number corruptions of e-64x512.
 """
 
 import importlib
@@ -126,6 +129,123 @@ def test_accounting_bites_where_compare_does_not(oracle, restated):
     shifted = _corrupt(good, first_cross=(tile, np.where(fc[tile] > 0, fc[tile] + 1, 0)))
     with pytest.raises(AssertionError, match="decided cells with the wrong first-crossing radius"):
         X.check_outputs(ref, shifted)
+
+
+# ---- the table loops: mode (t) of tests/excursion_reference.py ------------------------------------------------
+
+S = importlib.import_module("21cmfast_amd.structs")
+
+
+def _oracle_run(oracle, spec, inp, calls=None):
+    X.install_table(spec, inp, S, calls)
+    return oracle.ionize_grids(spec, inp.density, need_nion=True, **inp.kwargs())
+
+
+@pytest.mark.parametrize("n", [32, 35])
+@pytest.mark.parametrize("with_xe", [False, True], ids=["", "xe"])
+@pytest.mark.parametrize("fmode", [X.FCOLL_TABLE_LINEAR, X.FCOLL_TABLE_EXP], ids=["linear", "exp"])
+def test_table_modes_pinned_to_the_oracle(oracle, fmode, with_xe, n):
+    """test_pinned_to_the_oracle for the table modes, with and without an x_e grid: flags on every
+    flag-decided cell, z_reion, the per-radius means within the bound of the restatement (radius 0 keeps the
+    documented departure: the oracle's grid has been through a transform pair there) -- and what the oracle
+    hands its table callback, (r_index, dmin, dmax), against the restatement's own extrema -/+ 0.001 at the
+    atol of 2e-5 that test_gpu_ionize.py::test_table_modes_parity grants the device."""
+    spec, inp, ref, e = X.restated_table(W, (fmode, n, n, 12.0, 4242, with_xe, False))
+    calls = []
+    out = _oracle_run(oracle, spec, inp, calls)
+    flag = out["neutral_fraction"] == 0
+    print(f"oracle pin table mode {fmode} x_e {with_xe} {n}^3: E32 {e['margin']:.2e}, mean deviation "
+          f"{e['mean']:.2e}, flag-undecided {ref.flag_undecided_share:.2e}, ionised {flag.mean():.3f}")
+    assert 0.05 < flag.mean() < 0.95
+    wrong = ref.flag_decided & (flag != ref.decided_flag)
+    assert not wrong.any(), np.argwhere(wrong)[:5]
+    np.testing.assert_array_equal(out["z_reion"][ref.flag_decided],
+                                  np.where(ref.decided_flag, X.F32(spec.redshift), X.F32(-1))[ref.flag_decided])
+    means = np.array(out["report"].f_coll_grid_mean[:spec.n_radii])
+    dev = np.abs(means - ref.f_coll_grid_mean) / ref.f_coll_grid_mean
+    print(f"oracle mean deviation table mode {fmode} x_e {with_xe} {n}^3: {dev.max() / e['mean']:.2f} x the "
+          f"measured one, at radius {int(np.argmax(dev))} (bound {ref.mean_tol / e['mean']:.2f} x)")
+    assert ref.mean_tol == X.FACTOR * e["mean"] + (X.EXP_F32ACC if fmode == X.FCOLL_TABLE_EXP else 0.0)
+    assert dev.max() <= ref.mean_tol, (dev.max(), ref.mean_tol)
+    # the callback: every radius once, from the largest down, over the restatement's extrema
+    assert [c[0] for c in calls] == list(range(spec.n_radii - 1, -1, -1))
+    np.testing.assert_allclose([c[1:] for c in calls], [ref.table_range[c[0]] for c in calls], rtol=0, atol=2e-5)
+    # the float32 chain's own outputs pass the accounting
+    X.check_outputs(ref, e["outputs"])
+
+
+@pytest.mark.parametrize("name", list(X.TABLE_CASES))
+def test_table_caps_hold(name):
+    """test_caps_hold on every box of test_gpu_table_cells.py; one TABLE-CAPS line per box (DESIGN.md,
+    Appendix C.1-T).  The caps are those of the other modes, unchanged."""
+    spec, inp, ref, e = X.restated_table(W, name)
+    fig = X.check_outputs(ref, e["outputs"])
+    print(X.table_caps_line(name, spec, ref, e))
+    print(X.excursion_line(name + " (float32 chain on the host)", ref, e, fig))
+    assert ref.flag_undecided_share <= X.FLAG_CAP
+    assert ref.radius_undecided_share <= X.RADIUS_CAP
+    assert 0.02 < ref.decided_flag.mean() < 0.98  # both flags occur
+    assert len(np.unique(ref.cross_hi)) > spec.n_radii // 2  # the crossings spread over the radii
+
+
+def test_table_accounting_bites_where_compare_does_not(oracle):
+    """Four corruptions of the float32 chain's own outputs of e-64x512, each no larger than what a slip in the
+    marker, pending or rewind bookkeeping of the banded sweeps would leave; each must raise, by name.  The
+    first two pass test_gpu_ionize.compare against the oracle, the only outside reference these loops had:
+    the gap this accounting closes, kept on record."""
+    compare = importlib.import_module("test_gpu_ionize").compare
+    spec, inp, ref, e = X.restated_table(W, "e-64x512")
+    good = e["outputs"]
+    X.check_outputs(ref, good)
+    n_cells = ref.xhi.size
+    want = _oracle_run(oracle, spec, inp)
+    assert "first_cross" not in want  # compare() is handed no first-crossing grid
+
+    def accepted(got):
+        got = dict(got)
+        got["report"] = SimpleNamespace(f_coll_grid_mean=list(want["report"].f_coll_grid_mean),
+                                        global_xH=float(got["neutral_fraction"].mean(dtype=np.float64)))
+        return compare(got, want, spec)
+
+    # cells the banded sweeps defer: decided, crossing at a banded radius (index >= 2) with f mean_f_coll /
+    # mean zeta within 0.5 % of its threshold 1 (the least half-width of a band); no x_e grid here, so that
+    # is a margin below 0.005
+    decided = ref.flag_decided & ref.radius_decided
+    deferred = decided & (ref.cross_hi >= 3) & (ref.margin_at_cross < 0.005) & (ref.xhi > 0.01)
+    assert (ref.margin_at_cross[deferred] > ref.t).all() and deferred.sum() > 100
+    cells = np.argwhere(deferred)
+
+    # (1) one of them turned neutral, consistently in every output
+    one = tuple(cells[len(cells) // 2])
+    assert want["neutral_fraction"][one] == 0
+    flipped = _corrupt(good, neutral_fraction=(one, X.F32(ref.xhi[one])), z_reion=(one, X.F32(-1)),
+                       first_cross=(one, 0))
+    with pytest.raises(AssertionError, match="decided cells with the wrong flag: 1 cells"):
+        X.check_outputs(ref, flipped)
+    got = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in want.items()}
+    got["neutral_fraction"][one] = ref.xhi[one]
+    got["z_reion"][one] = -1
+    assert accepted(got) == 1 / n_cells
+
+    # (2) the first crossing of another moved to the next smaller radius
+    two = tuple(cells[len(cells) // 3])
+    assert good["first_cross"][two] == ref.cross_hi[two] - 1 >= 2
+    moved = _corrupt(good, first_cross=(two, good["first_cross"][two] - 1))
+    with pytest.raises(AssertionError, match="decided cells with the wrong first-crossing radius: 1 cells"):
+        X.check_outputs(ref, moved)
+    assert accepted(dict(want, first_cross=moved["first_cross"])) == 0  # ... which compare() never reads
+
+    # (3) a marker left behind
+    marked = _corrupt(good, first_cross=(tuple(cells[len(cells) // 4]), 255))
+    with pytest.raises(AssertionError, match=r"first_cross holds a marker \(255\): 1 cells"):
+        X.check_outputs(ref, marked)
+
+    # (4) one per-radius mean off by 1e-6 relative (compare() grants 1e-5)
+    r = spec.n_radii // 2
+    means = good["f_coll_grid_mean"].copy()
+    means[r] *= 1 + 1e-6
+    with pytest.raises(AssertionError, match=rf"f_coll_grid_mean\[{r}\]"):
+        X.check_outputs(ref, dict(good, f_coll_grid_mean=means))
 
 
 # ---- the recombination loop: tests/recomb_excursion_reference.py ---------------------------------------------
