@@ -952,6 +952,17 @@ typedef struct c21hip_cluster_emit_args {
 /* (root, size) of the clusters in ascending root, the two histograms, the four stats */
 int c21hip_cluster_emit(const c21hip_cluster_emit_args *a, void *stream);
 
+/* ---- minkowski_kernels.hip : Minkowski functionals of boxes and lightcone chunks (minkowski_driver.c) ---- */
+#define C21HIP_MINKOWSKI_MAX_THRESHOLDS 255 /* a level fits a byte; thresholds and counters of one workgroup: 10 KiB */
+/* The element counts of c21cm_minkowski_grids (include/c21cm_grid.h) for every threshold from one read of the boxes.
+ * thresholds: device, n_thresholds increasing values; offsets: device.  hist[n_batch][8][n_thresholds + 1] is zeroed
+ * by the caller and receives, per element kind, the elements by the largest level of their cells (the level of a
+ * cell: the thresholds <= v, or with select_below n_thresholds less that; bin 0 is not filled);
+ * counts[n_batch][n_thresholds][8] are its suffix sums.  *bad |= 1 on a non-finite value */
+int c21hip_minkowski(const float *in, int nx, int ny, int nz, long long row_pitch, const long long *offsets,
+                     int n_batch, int n_thresholds, const double *thresholds, int select_below, int periodic_mask,
+                     unsigned long long *hist, long long *counts, int *bad, void *stream);
+
 /* ---- ts_kernels.hip : per-cell part of ComputeTsBox (SpinTemperatureBox.c:892-927,1010-1086,
  * 1210-1383,1499-1848) ---- */
 typedef struct c21hip_ts_args { /* the scalars of c21cm_ts_spec, passed by value */

@@ -418,6 +418,11 @@ enum c21_ws_slot {
     WS_BC_SIZE,   /* int32 per cell: the cells of the cluster rooted there */
     WS_BC_OUT,    /* stats, histograms, root counts, largest-cluster keys, and the cluster lists that were asked for */
     WS_BC_FLAG,
+    /* ---- minkowski_driver.c ---- */
+    WS_MK_TAB,  /* thresholds (fp64), batch offsets */
+    WS_MK_IN,   /* staged host field */
+    WS_MK_OUT,  /* the level histograms of the 8 element kinds, then counts */
+    WS_MK_FLAG,
 
     WS_COUNT
 };

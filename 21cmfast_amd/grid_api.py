@@ -1587,3 +1587,46 @@ def bubble_clusters(field, shape, edges, *, threshold=0.5, select_below=True, co
     if max_clusters:
         out += (roots, sizes)
     return out
+
+
+MINKOWSKI_MAX_THRESHOLDS = 255  # C21HIP_MINKOWSKI_MAX_THRESHOLDS
+
+
+def minkowski(field, shape, thresholds, *, select_below=True, periodic=(True, True, True), offsets=(0,),
+              row_pitch=None, stream=None):
+    """The element counts behind the Minkowski functionals of the excursion sets of ``len(offsets)`` boxes of ``shape``
+    = (nx, ny, nz) cells read from the float32 array ``field`` (the layout of ``power_spectrum``), at every one of the
+    increasing ``thresholds`` (1 to 255 of them) from one read of the field.  At threshold t the cells with ``v < t``
+    (``select_below``) or ``v >= t`` are selected, and an element of the cubical complex of the box -- which wraps on
+    the ``periodic`` axes -- counts where a selected cell contains it.  Returns int64 (n_batch, n_thresholds, 8) =
+    n3 (cells), n2x, n2y, n2z (faces perpendicular to an axis), n1x, n1y, n1z (edges parallel to one), n0 (vertices):
+    numpy for numpy input, torch on the field's device for a torch CUDA field.  The estimator is written down at
+    ``c21cm_minkowski_grids`` (include/c21cm_grid.h)."""
+    nx, ny, nz = (int(x) for x in shape)
+    row_pitch = nz if row_pitch is None else int(row_pitch)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_batch = len(offsets)
+    _f32_dense(field, "field")
+    size = int(np.prod(field.shape, dtype=np.int64))
+    if n_batch < 1 or offsets.min() < 0 or offsets.max() + (nx * ny - 1) * row_pitch + nz > size:
+        raise ValueError("the boxes do not lie inside the field")
+    if nx * ny * nz >= 2**31:
+        raise ValueError("a box must have fewer than 2^31 cells")
+    thresholds = np.ascontiguousarray(thresholds, np.float64)
+    if thresholds.ndim != 1 or not 1 <= thresholds.size <= MINKOWSKI_MAX_THRESHOLDS:
+        raise ValueError(f"thresholds must be a 1-D array of 1 to {MINKOWSKI_MAX_THRESHOLDS} values")
+    if not np.all(np.isfinite(thresholds)) or np.any(np.diff(thresholds) <= 0):
+        raise ValueError("thresholds must be finite and strictly increasing")
+    px, py, pz = (bool(p) for p in periodic)
+    if _is_torch(field):
+        import torch
+
+        counts = torch.empty((n_batch, thresholds.size, 8), dtype=torch.int64, device=field.device)
+    else:
+        counts = np.empty((n_batch, thresholds.size, 8), np.int64)
+    lib = load()
+    check(lib.c21cm_minkowski_grids(
+        _vptr(field), nx, ny, nz, n_batch, row_pitch, offsets.ctypes.data_as(C.c_void_p), int(thresholds.size),
+        thresholds.ctypes.data_as(C.c_void_p), int(bool(select_below)), px | (py << 1) | (pz << 2), _vptr(counts),
+        _stream(stream)), "c21cm_minkowski_grids")
+    return counts

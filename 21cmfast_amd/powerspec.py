@@ -21,7 +21,10 @@ statistic, the FFT estimator over shells in |k| (``csrc/hip/bispectrum_kernels.h
 ``tests/bispectrum_reference.py``).  ``get_bubble_sizes`` and ``lightcone_bubble_sizes`` are the morphological
 statistic, the mean-free-path bubble size distribution traced ray by ray (``csrc/hip/bubble_kernels.hip``; its
 spec is ``tests/bubble_reference.py``); ``get_bubble_clusters`` and ``lightcone_bubble_clusters`` label its
-friends-of-friends clusters (``csrc/hip/cluster_kernels.hip``; spec ``tests/cluster_reference.py``).
+friends-of-friends clusters (``csrc/hip/cluster_kernels.hip``; spec ``tests/cluster_reference.py``);
+``get_minkowski_functionals`` and ``lightcone_minkowski_functionals`` count the Minkowski functionals of its
+excursion sets at every threshold from one read of the field (``csrc/hip/minkowski_kernels.hip``; spec
+``tests/minkowski_reference.py``).
 
 Arrays may be numpy (results are numpy) or torch CUDA tensors (results are torch tensors on the same
 device; the field never visits the host).  Argument errors are ``ValueError``; a non-finite field value
@@ -1072,5 +1075,164 @@ def lightcone_bubble_clusters(lightcone, cell_size, *, chunk_length=None, chunk_
     edges = cluster_edges(shape, kw.get("bins", 32), kw.get("log_bins", True))
     res = _cluster_result(_f32(lightcone), shape, dx ** 3, edges, args, starts, ns, kw.get("return_labels", False),
                           return_clusters, max_clusters)
+    res.chunk_starts, res.redshifts = starts, z
+    return res
+
+
+MINKOWSKI_MAX_THRESHOLDS = api.MINKOWSKI_MAX_THRESHOLDS
+
+
+def _min_max(field):
+    if _is_torch(field):
+        return float(field.min()), float(field.max())
+    a = np.asarray(field)
+    return float(a.min()), float(a.max())
+
+
+def minkowski_thresholds(field, n=32) -> np.ndarray:
+    """``n`` equally spaced thresholds strictly inside [min, max] of the whole ``field``:
+    ``np.linspace(min, max, n + 2)[1:-1]`` in fp64.  A constant (or non-finite) field has none."""
+    if isinstance(n, (bool, np.bool_)) or np.ndim(n) != 0 or int(n) != n:
+        raise ValueError("the number of thresholds must be an integer")
+    if not 1 <= int(n) <= MINKOWSKI_MAX_THRESHOLDS:
+        raise ValueError(f"Minkowski functionals take 1 to {MINKOWSKI_MAX_THRESHOLDS} thresholds, got {int(n)}")
+    lo, hi = _min_max(field)
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("the field has no finite range to space thresholds in")
+    if not hi > lo:
+        raise ValueError("a constant field has no thresholds strictly inside its range")
+    t = np.linspace(np.float64(lo), np.float64(hi), int(n) + 2)[1:-1]
+    if np.any(np.diff(t) <= 0):
+        raise ValueError(f"the range of the field is too narrow for {int(n)} distinct thresholds")
+    return t
+
+
+@dataclass
+class MinkowskiFunctionals:
+    """What ``get_minkowski_functionals`` and ``lightcone_minkowski_functionals`` return (the latter with a leading
+    chunk axis on everything but the thresholds).  A box of N cells of volume V_cell has the volume V = N V_cell; its
+    cells have the edge lengths l_a and the face areas A_a = V_cell / l_a.  ``thresholds`` (T,) fp64; ``counts`` int64
+    (T, 8) = n3 (selected cells), n2x, n2y, n2z (faces of the excursion set perpendicular to an axis), n1x, n1y, n1z
+    (edges parallel to one), n0 (vertices); ``n_cells`` = N; ``euler_characteristic`` int64 = n0 - sum n1a + sum n2a -
+    n3; ``genus`` = 1 - chi / 2; and the four functionals per unit volume, fp64 (T,): ``v0`` = n3 / N, ``v1`` = (2/9)
+    sum_a A_a (n2a - n3) / V, ``v2`` = (2/9) sum_a l_a (n1a - n2b - n2c + n3) / V with b, c the other two axes, ``v3``
+    = chi / V.  For cubic cells of edge a these are the Crofton estimators of Schmalzing & Buchert (1997), 2 (n2 - 3
+    n3) / (9 a N), 2 (n1 - 2 n2 + 3 n3) / (9 a^2 N) and (n0 - n1 + n2 - n3) / (a^3 N); the lattice correction 2/9 is
+    exact only for cubic cells.  For a lightcone also ``chunk_starts`` and ``redshifts``."""
+
+    thresholds: object
+    counts: object
+    n_cells: int
+    euler_characteristic: object
+    genus: object
+    v0: object
+    v1: object
+    v2: object
+    v3: object
+    chunk_starts: np.ndarray | None = None
+    redshifts: np.ndarray | None = None
+
+
+def _minkowski_args(thresholds, select, periodic, field):
+    if select not in ("below", "above"):
+        raise ValueError("select must be 'below' (v < threshold) or 'above' (v >= threshold)")
+    if np.ndim(periodic) == 0:
+        periodic = (bool(periodic),) * 3
+    else:
+        periodic = tuple(bool(p) for p in periodic)
+        if len(periodic) != 3:
+            raise ValueError("periodic must be a bool or three bools")
+    if np.ndim(thresholds) == 0:
+        t = minkowski_thresholds(field, thresholds)
+    else:
+        t = np.array(thresholds, np.float64)
+        if t.ndim != 1 or not 1 <= t.size <= MINKOWSKI_MAX_THRESHOLDS:
+            raise ValueError(f"thresholds must be an integer or a 1-D array of 1 to {MINKOWSKI_MAX_THRESHOLDS} values")
+        if not np.all(np.isfinite(t)) or np.any(np.diff(t) <= 0):
+            raise ValueError("thresholds must be finite and strictly increasing")
+    return t, dict(select_below=select == "below", periodic=periodic)
+
+
+def _minkowski_result(f, shape, cell, thresholds, args, offsets, row_pitch) -> MinkowskiFunctionals:
+    counts = api.minkowski(f, shape, thresholds, offsets=offsets, row_pitch=row_pitch, **args)
+    n_cells = int(shape[0]) * int(shape[1]) * int(shape[2])
+    cell_volume = float(np.prod(cell))
+    volume = n_cells * cell_volume
+    area = [cell_volume / l for l in cell]
+    if _is_torch(counts):
+        import torch
+
+        def const(v):
+            # a tensor divisor or factor: by a Python scalar torch may multiply with the reciprocal
+            return torch.full((), v, dtype=torch.float64, device=counts.device)
+
+        def f64_of(a):
+            return a.to(torch.float64)
+    else:
+        def const(v):
+            return np.float64(v)
+
+        def f64_of(a):
+            return a.astype(np.float64)
+
+    n3, n2, n1, n0 = counts[..., 0], counts[..., 1:4], counts[..., 4:7], counts[..., 7]
+    chi = n0 - n1.sum(-1) + n2.sum(-1) - n3
+    surface = sum(const(area[a]) * f64_of(n2[..., a] - n3) for a in range(3))
+    curvature = sum(const(cell[a]) * f64_of(n1[..., a] - n2[..., (a + 1) % 3] - n2[..., (a + 2) % 3] + n3)
+                    for a in range(3))
+    return MinkowskiFunctionals(
+        thresholds=thresholds, counts=counts, n_cells=n_cells, euler_characteristic=chi,
+        genus=const(1.0) - f64_of(chi) / const(2.0), v0=f64_of(n3) / const(float(n_cells)),
+        v1=const(2.0) * surface / const(9.0) / const(volume), v2=const(2.0) * curvature / const(9.0) / const(volume),
+        v3=f64_of(chi) / const(volume))
+
+
+_MINKOWSKI_PER_BOX = ("counts", "euler_characteristic", "genus", "v0", "v1", "v2", "v3")
+
+
+def get_minkowski_functionals(field, boxlength, *, thresholds=32, select="below",
+                              periodic=True) -> MinkowskiFunctionals:
+    """The Minkowski functionals (Schmalzing & Buchert 1997; for 21-cm fields Gleser et al. 2006, Friedrich et al.
+    2011, Yoshiura et al. 2017) of the excursion sets of the 3-D ``field`` in a box of ``boxlength`` (a scalar or 3
+    lengths): at every threshold t the cells with ``v < t`` (``select="below"``: for a neutral fraction the ionised
+    phase) or ``v >= t`` (``"above"``) form a set whose volume, surface, integrated mean curvature and Euler
+    characteristic are counted from the cells, faces, edges and vertices of the cubical complex of the box, which
+    wraps on the ``periodic`` axes (a bool or three).  ``thresholds``: an integer (``minkowski_thresholds``: that many
+    equally spaced values strictly inside the range of the field) or an increasing 1-D array of at most 255 values;
+    all of them are served by one read of the field.  The estimators are written down at ``MinkowskiFunctionals``; for
+    cubic cells they are the Crofton estimators of Schmalzing & Buchert, and their lattice correction 2/9 is exact
+    only for cubic cells.  Every count is an integer fixed by the field: two calls give the same bytes, and a
+    threshold's row does not depend on the other thresholds."""
+    _check_bubble_field(field)
+    shape = _shape(field)
+    L = _lengths(boxlength)
+    t, args = _minkowski_args(thresholds, select, periodic, field)
+    cell = [l / n for l, n in zip(L, shape)]
+    res = _minkowski_result(_f32(field), shape, cell, t, args, (0,), None)
+    for name in _MINKOWSKI_PER_BOX:
+        setattr(res, name, getattr(res, name)[0])
+    return res
+
+
+def lightcone_minkowski_functionals(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None,
+                                    **kw) -> MinkowskiFunctionals:
+    """Minkowski functionals of the chunks of a rectilinear ``lightcone`` (nx, ny, n_slices) of cells of ``cell_size``
+    [Mpc], chunked as ``lightcone_bubble_clusters`` chunks it; all chunks go through one library call.  The transverse
+    axes are periodic and the line of sight is open, so ``periodic`` is not a keyword here; the others (``thresholds``,
+    ``select``) are those of ``get_minkowski_functionals``.  An integer ``thresholds`` is resolved once over the whole
+    lightcone, so the chunks share their thresholds.  Every per-box entry carries a leading chunk axis."""
+    _check_bubble_field(lightcone, "lightcone")
+    if "periodic" in kw:
+        raise ValueError("periodic is fixed for a lightcone: the transverse axes are, the line of sight is not")
+    unknown = set(kw) - {"thresholds", "select"}
+    if unknown:
+        raise ValueError(f"unknown keywords: {sorted(unknown)}")
+    nx, ny, ns = _shape(lightcone)
+    dx = float(cell_size)
+    if not (np.isfinite(dx) and dx > 0):
+        raise ValueError("cell_size must be positive and finite")
+    n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
+    t, args = _minkowski_args(kw.get("thresholds", 32), kw.get("select", "below"), (True, True, False), lightcone)
+    res = _minkowski_result(_f32(lightcone), (nx, ny, n), [dx, dx, dx], t, args, starts, ns)
     res.chunk_starts, res.redshifts = starts, z
     return res

@@ -1126,6 +1126,31 @@ int c21cm_bubble_clusters_grids(const float *field, int nx, int ny, int nz, int 
                                 long long max_clusters, long long *cluster_roots, long long *cluster_sizes,
                                 void *stream);
 
+/* ---- Minkowski functionals of boxes and lightcone chunks (Schmalzing & Buchert 1997; Gleser et al. 2006;
+ * Friedrich et al. 2011; the spec is tests/minkowski_reference.py) ----
+ * Layout: as for c21cm_bubble_clusters_grids: n_batch boxes of nx x ny x nz float32 cells at batch_offsets[b], rows of
+ *   row_pitch, z fastest, host or device pointers.
+ * Thresholds: thresholds[n_thresholds] on the host, finite, strictly increasing, 1 <= n_thresholds <= 255.
+ * Selection: as everywhere in this module: at threshold t a cell is selected iff (double)v < t (select_below = 1) or
+ *   (double)v >= t (select_below = 0).
+ * The complex: a box is the cubical complex of its cells.  Each cell is a closed cube with 6 faces, 12 edges and 8
+ *   vertices, and neighbouring cells share elements.  On an axis whose bit is set in periodic_mask (bit 0 x, 1 y, 2 z)
+ *   the complex wraps: with n_a = 1 a cell's two faces across a are the same face, with n_a = 2 they are two faces.
+ *   Through an open face there is no cell; the elements on that face belong to the one cell inside.
+ * Counting: an element is in the set at t iff at least one cell that contains it is selected at t.  That cell can be
+ *   one of 1 cell for a cube, up to 2 for a face, 4 for an edge, 8 for a vertex.
+ * Outputs (host or device): counts[n_batch][n_thresholds][8], int64, = {n3, n2x, n2y, n2z, n1x, n1y, n1z, n0}: n3
+ *   selected cells; n2a faces perpendicular to axis a; n1a edges parallel to a; n0 vertices.  Everything is an
+ *   integer, summed with integer atomics or a fixed-order reduction: two calls give the same bytes, and a row does
+ *   not depend on which other thresholds were asked for.
+ * Errors, checked before any output is touched: C21CM_VALUE_ERROR with a message for a NULL required pointer, a bad
+ *   shape, nx ny nz >= 2^31, n_batch outside [1, 65535], row_pitch < nz, a negative offset, n_thresholds outside
+ *   [1, 255], thresholds not finite or not increasing, or periodic_mask outside 0..7; C21CM_INFINITY_OR_NAN_ERROR for
+ *   a non-finite field value.  Nothing is written. */
+int c21cm_minkowski_grids(const float *field, int nx, int ny, int nz, int n_batch, long long row_pitch,
+                          const long long *batch_offsets, int n_thresholds, const double *thresholds,
+                          int select_below, int periodic_mask, long long *counts, void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
