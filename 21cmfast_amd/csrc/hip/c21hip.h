@@ -952,6 +952,25 @@ typedef struct c21hip_cluster_emit_args {
 /* (root, size) of the clusters in ascending root, the two histograms, the four stats */
 int c21hip_cluster_emit(const c21hip_cluster_emit_args *a, void *stream);
 
+/* ---- granulometry_kernels.hip : distance transforms and granulometry of boxes and lightcone chunks
+ * (granulometry_driver.c) ---- */
+#define C21HIP_EDT_NONE (1 << 30)     /* D2 of a box without an unselected cell (C21CM_EDT_NONE) */
+#define C21HIP_GRAN_MAX_RADII 255     /* radii and erosion counters of one workgroup: 3 KiB of LDS */
+/* From the mask of c21hip_bubble_pack: dist2[b][c] = D2 of c21cm_granulometry_grids (include/c21cm_grid.h); where not
+ * NULL level[b][c] = -1 at unselected cells and 0 elsewhere; eroded[b][k] = the cells with D2 > radii2[k] (radii2:
+ * device, increasing); stats[b][1..3] = {max D2, its smallest flat index, n_unselected} beside stats[b][0] as
+ * c21hip_bubble_rank left it.  hist [n_batch][256] and key [n_batch] are zeroed by the caller; work_a and work_b are
+ * n_batch boxes of int32 each.  nx^2 + ny^2 + nz^2 < 2^30.  Four launches: z, y, x, finish */
+int c21hip_gran_edt(const unsigned long long *mask, int nx, int ny, int nz, int n_batch, int periodic_mask,
+                    int n_radii, const long long *radii2, int *work_a, int *work_b, int *dist2, int *level,
+                    unsigned long long *hist, unsigned long long *key, long long *eroded, long long *stats,
+                    void *stream);
+/* covered[b][k] += the cells of box b inside an inscribed ball with D2 > radius2 (zeroed by the caller), and level
+ * += 1 at those cells where not NULL; stats as c21hip_gran_edt left it.  Three launches: z, y, x */
+int c21hip_gran_cover(const int *dist2, int nx, int ny, int nz, int n_batch, int periodic_mask, int radius2, int k,
+                      int n_radii, const long long *stats, int *work_a, int *work_b, unsigned long long *covered,
+                      int *level, void *stream);
+
 /* ---- minkowski_kernels.hip : Minkowski functionals of boxes and lightcone chunks (minkowski_driver.c) ---- */
 #define C21HIP_MINKOWSKI_MAX_THRESHOLDS 255 /* a level fits a byte; thresholds and counters of one workgroup: 10 KiB */
 /* The element counts of c21cm_minkowski_grids (include/c21cm_grid.h) for every threshold from one read of the boxes.

@@ -423,6 +423,17 @@ enum c21_ws_slot {
     WS_MK_IN,   /* staged host field */
     WS_MK_OUT,  /* the level histograms of the 8 element kinds, then counts */
     WS_MK_FLAG,
+    /* ---- granulometry_driver.c ---- */
+    WS_GR_TAB,    /* squared radii, batch offsets */
+    WS_GR_IN,     /* staged host field */
+    WS_GR_MASK,   /* one bit per cell, rows padded to whole 64-bit words */
+    WS_GR_PREFIX, /* rank scratch of the mask: set bits per chunk, their scan, set bits before every word */
+    WS_GR_D2,     /* int32 per cell: the squared distance transform */
+    WS_GR_WORK_A, /* int32 per cell: the two boxes a three-pass transform goes through */
+    WS_GR_WORK_B,
+    WS_GR_LEVEL,  /* int32 per cell, where asked for */
+    WS_GR_OUT,    /* stats, covered, eroded, the erosion histogram, deepest-cell keys */
+    WS_GR_FLAG,
 
     WS_COUNT
 };

@@ -1630,3 +1630,69 @@ def minkowski(field, shape, thresholds, *, select_below=True, periodic=(True, Tr
         thresholds.ctypes.data_as(C.c_void_p), int(bool(select_below)), px | (py << 1) | (pz << 2), _vptr(counts),
         _stream(stream)), "c21cm_minkowski_grids")
     return counts
+
+
+GRANULOMETRY_MAX_RADII = 255  # C21HIP_GRAN_MAX_RADII
+EDT_NONE = 2**30  # C21CM_EDT_NONE: D2 of a box without an unselected cell
+
+
+def granulometry(field, shape, radii2, *, threshold=0.5, select_below=True, periodic=(True, True, True), offsets=(0,),
+                 row_pitch=None, return_dist2=False, return_level=False, stream=None):
+    """The squared Euclidean distance transform and the granulometry of the selected cells of ``len(offsets)`` boxes of
+    ``shape`` = (nx, ny, nz) cells read from the float32 array ``field`` (the layout of ``power_spectrum``).  Cells
+    with ``v < threshold`` (``select_below``) or ``v >= threshold`` are selected; D2 of a cell is its squared distance,
+    in cells and with the minimum image on the ``periodic`` axes, to the nearest unselected cell of its box (0 at
+    unselected cells, ``EDT_NONE`` = 2^30 in a box without one).  ``radii2``: 0 to 255 increasing integer squared radii
+    s >= 0.  Returns ``(covered, eroded, stats)``: int64 (n_batch, n_radii) the cells inside an inscribed ball with
+    D2 > s and the cells with D2 > s, and (n_batch, 4) = n_selected, the largest D2 of a selected cell (0 without
+    one), the smallest flat index attaining it (-1), n_unselected; with ``return_dist2`` also ``dist2`` int32
+    (n_batch, nx ny nz); with ``return_level`` also ``level`` int32 (n_batch, nx ny nz), the number of radii at which
+    the cell is covered, -1 at unselected cells.  numpy for numpy input, torch on the field's device for a torch CUDA
+    field.  The estimator is written down at ``c21cm_granulometry_grids`` (include/c21cm_grid.h)."""
+    nx, ny, nz = (int(x) for x in shape)
+    row_pitch = nz if row_pitch is None else int(row_pitch)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_batch = len(offsets)
+    _f32_dense(field, "field")
+    size = int(np.prod(field.shape, dtype=np.int64))
+    if n_batch < 1 or offsets.min() < 0 or offsets.max() + (nx * ny - 1) * row_pitch + nz > size:
+        raise ValueError("the boxes do not lie inside the field")
+    if nx * ny * nz >= 2**31:
+        raise ValueError("a box must have fewer than 2^31 cells")
+    if nx * nx + ny * ny + nz * nz >= EDT_NONE:
+        raise ValueError("nx^2 + ny^2 + nz^2 must be below 2^30")
+    raw = np.asarray(radii2)
+    if raw.ndim != 1 or raw.size > GRANULOMETRY_MAX_RADII:
+        raise ValueError(f"radii2 must be a 1-D array of at most {GRANULOMETRY_MAX_RADII} values")
+    if raw.size and raw.dtype.kind not in "iu" and not (np.all(np.isfinite(raw)) and np.all(raw == np.round(raw))):
+        raise ValueError("squared radii must be integers (cells^2)")
+    radii2 = np.ascontiguousarray(raw, np.int64)
+    if np.any(radii2 < 0) or np.any(np.diff(radii2) <= 0):
+        raise ValueError("squared radii must be >= 0 and strictly increasing")
+    n_radii = int(radii2.size)
+    px, py, pz = (bool(p) for p in periodic)
+    if _is_torch(field):
+        import torch
+
+        def empty(shape_, dtype):
+            return torch.empty(shape_, dtype=getattr(torch, dtype), device=field.device)
+    else:
+        def empty(shape_, dtype):
+            return np.empty(shape_, dtype)
+    covered, eroded = empty((n_batch, n_radii), "int64"), empty((n_batch, n_radii), "int64")
+    stats = empty((n_batch, 4), "int64")
+    dist2 = empty((n_batch, nx * ny * nz), "int32") if return_dist2 else None
+    level = empty((n_batch, nx * ny * nz), "int32") if return_level else None
+    lib = load()
+    check(lib.c21cm_granulometry_grids(
+        _vptr(field), nx, ny, nz, n_batch, row_pitch, offsets.ctypes.data_as(C.c_void_p), float(threshold),
+        int(bool(select_below)), px | (py << 1) | (pz << 2), n_radii,
+        radii2.ctypes.data_as(C.c_void_p) if n_radii else None, _vptr(covered) if n_radii else None,
+        _vptr(eroded) if n_radii else None, _vptr(stats), _vptr(dist2), _vptr(level), _stream(stream)),
+        "c21cm_granulometry_grids")
+    out = (covered, eroded, stats)
+    if return_dist2:
+        out += (dist2,)
+    if return_level:
+        out += (level,)
+    return out

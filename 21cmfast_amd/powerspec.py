@@ -24,7 +24,9 @@ spec is ``tests/bubble_reference.py``); ``get_bubble_clusters`` and ``lightcone_
 friends-of-friends clusters (``csrc/hip/cluster_kernels.hip``; spec ``tests/cluster_reference.py``);
 ``get_minkowski_functionals`` and ``lightcone_minkowski_functionals`` count the Minkowski functionals of its
 excursion sets at every threshold from one read of the field (``csrc/hip/minkowski_kernels.hip``; spec
-``tests/minkowski_reference.py``).
+``tests/minkowski_reference.py``); ``get_distance_transform``, ``get_granulometry`` and ``lightcone_granulometry``
+are its exact Euclidean distance transform and the granulometry size distribution built on it
+(``csrc/hip/granulometry_kernels.hip``; spec ``tests/granulometry_reference.py``).
 
 Arrays may be numpy (results are numpy) or torch CUDA tensors (results are torch tensors on the same
 device; the field never visits the host).  Argument errors are ``ValueError``; a non-finite field value
@@ -1234,5 +1236,215 @@ def lightcone_minkowski_functionals(lightcone, cell_size, *, chunk_length=None, 
     n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
     t, args = _minkowski_args(kw.get("thresholds", 32), kw.get("select", "below"), (True, True, False), lightcone)
     res = _minkowski_result(_f32(lightcone), (nx, ny, n), [dx, dx, dx], t, args, starts, ns)
+    res.chunk_starts, res.redshifts = starts, z
+    return res
+
+
+GRANULOMETRY_MAX_RADII = api.GRANULOMETRY_MAX_RADII
+EDT_NONE = api.EDT_NONE
+
+
+def _periodic3(periodic) -> tuple:
+    if np.ndim(periodic) == 0:
+        return (bool(periodic),) * 3
+    periodic = tuple(bool(p) for p in periodic)
+    if len(periodic) != 3:
+        raise ValueError("periodic must be a bool or three bools")
+    return periodic
+
+
+def granulometry_radii(shape, n=32, periodic=True) -> np.ndarray:
+    """The squared radii, in cells^2, ``get_granulometry`` uses for a grid of ``shape``: the distinct ``floor(r^2)``
+    (int64) of ``n`` radii r log-spaced from 1 to the smallest reach of an axis, half its length where it is
+    ``periodic`` and its length where it is open.  A small box gets fewer radii than asked for."""
+    if isinstance(n, (bool, np.bool_)) or np.ndim(n) != 0 or int(n) != n:
+        raise ValueError("the number of radii must be an integer")
+    if not 1 <= int(n) <= GRANULOMETRY_MAX_RADII:
+        raise ValueError(f"a granulometry takes 1 to {GRANULOMETRY_MAX_RADII} radii, got {int(n)}")
+    per = _periodic3(periodic)
+    reach = min(int(m) / 2.0 if p else float(int(m)) for m, p in zip(shape, per))
+    r = np.geomspace(1.0, max(reach, 1.0), int(n))
+    return np.unique(np.floor(r * r).astype(np.int64))
+
+
+@dataclass
+class Granulometry:
+    """What ``get_granulometry`` and ``lightcone_granulometry`` return (the latter with a leading chunk axis on
+    everything but the radii).  ``radii2`` (K,) int64 the squared radii s in cells^2 and ``radii`` = sqrt(s) cell;
+    ``covered`` int64 (K,) the cells inside an inscribed ball with D2 > s and ``eroded`` the cells with D2 > s
+    (``c21cm_granulometry_grids``); ``n_selected``; ``filling_fraction`` = n_selected / cells; ``cumulative`` F =
+    covered / n_selected, the share of the selected volume that fits a sphere of that radius (NaN without a selected
+    cell); ``pdf`` (K - 1,) = (F_k - F_{k+1}) / (ln r_{k+1} - ln r_k) at ``r_mid`` = sqrt(r_k r_{k+1}) (0 at a pair
+    that starts at r = 0); ``mean_radius`` = (sum_k (F_k - F_{k+1}) r_mid_k + F_{K-1} r_{K-1}) / F_0;
+    ``max_distance`` = sqrt(max D2) cell, the radius of the largest inscribed ball (inf in a box without an unselected
+    cell); with ``return_sizes`` ``sizes`` float32 shaped as the box: the largest asked radius at which the cell is
+    covered, 0 where it is covered at none, NaN where it is not selected; for a lightcone ``chunk_starts`` and
+    ``redshifts``."""
+
+    radii2: object
+    radii: object
+    r_mid: object
+    covered: object
+    eroded: object
+    n_selected: object
+    filling_fraction: object
+    cumulative: object
+    pdf: object
+    mean_radius: object
+    max_distance: object
+    sizes: object = None
+    chunk_starts: np.ndarray | None = None
+    redshifts: np.ndarray | None = None
+
+
+def _cubic_cell(L, shape) -> float:
+    cell = [l / n for l, n in zip(L, shape)]
+    if any(abs(c - cell[0]) > 1e-9 * cell[0] for c in cell[1:]):
+        raise ValueError(f"distance transforms and granulometry need cubic cells, got cells of {cell}")
+    return float(cell[0])
+
+
+def _granulometry_args(threshold, select, periodic):
+    if select not in ("below", "above"):
+        raise ValueError("select must be 'below' (v < threshold) or 'above' (v >= threshold)")
+    if isinstance(threshold, (bool, np.bool_)) or np.ndim(threshold) != 0 or not np.isfinite(float(threshold)):
+        raise ValueError("threshold must be a finite number")
+    return dict(threshold=float(threshold), select_below=select == "below", periodic=_periodic3(periodic))
+
+
+def _granulometry_radii2(radii, shape, periodic, cell) -> np.ndarray:
+    if np.ndim(radii) == 0:
+        return granulometry_radii(shape, radii, periodic)
+    r = np.asarray(radii, np.float64)
+    if r.ndim != 1 or r.size < 1 or not np.all(np.isfinite(r)) or np.any(r < 0):
+        raise ValueError("radii must be an integer or a 1-D array of finite lengths >= 0")
+    s = np.unique(np.floor((r / cell) ** 2).astype(np.int64))
+    if s.size > GRANULOMETRY_MAX_RADII:
+        raise ValueError(f"a granulometry takes at most {GRANULOMETRY_MAX_RADII} distinct radii, got {s.size}")
+    return s
+
+
+def _granulometry_result(f, shape, cell, radii2, args, offsets, row_pitch, return_sizes) -> Granulometry:
+    out = api.granulometry(f, shape, radii2, offsets=offsets, row_pitch=row_pitch, return_level=return_sizes, **args)
+    covered, eroded, stats = out[:3]
+    n_cells = float(int(shape[0]) * int(shape[1]) * int(shape[2]))
+    r = np.sqrt(radii2.astype(np.float64)) * cell
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dln = np.diff(np.log(r))
+    r_mid = np.sqrt(r[:-1] * r[1:])
+    table = np.concatenate(([np.nan, 0.0], r)).astype(np.float32)  # by level + 1
+    if _is_torch(covered):
+        import torch
+
+        def dev(a, dtype=np.float64):
+            return torch.from_numpy(np.asarray(a, dtype)).to(covered.device)
+
+        def f64_of(a):
+            return a.to(torch.float64)
+
+        sqrt, where, inf = torch.sqrt, torch.where, dev(np.inf)
+
+        def lookup(level):
+            return dev(table, np.float32)[(level + 1).long()]
+    else:
+        def dev(a, dtype=np.float64):
+            return np.asarray(a, dtype)
+
+        def f64_of(a):
+            return a.astype(np.float64)
+
+        sqrt, where, inf = np.sqrt, np.where, np.float64(np.inf)
+
+        def lookup(level):
+            return table[level + 1]
+
+    n_sel, deepest = stats[:, 0], stats[:, 1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cum = f64_of(covered) / f64_of(n_sel)[:, None]  # 0 / 0 = NaN
+        step = cum[:, :-1] - cum[:, 1:]
+        mean = ((step * dev(r_mid)).sum(-1) + cum[:, -1] * dev(r[-1])) / cum[:, 0]
+    res = Granulometry(
+        radii2=dev(radii2, np.int64), radii=dev(r), r_mid=dev(r_mid), covered=covered, eroded=eroded, n_selected=n_sel,
+        filling_fraction=f64_of(n_sel) / dev(n_cells), cumulative=cum, pdf=step / dev(dln), mean_radius=mean,
+        max_distance=where(deepest >= EDT_NONE, inf, sqrt(f64_of(deepest)) * dev(cell)))
+    if return_sizes:
+        res.sizes = lookup(out[3]).reshape((len(offsets),) + tuple(int(n) for n in shape))
+    return res
+
+
+_GRANULOMETRY_PER_BOX = ("covered", "eroded", "n_selected", "filling_fraction", "cumulative", "pdf", "mean_radius",
+                         "max_distance", "sizes")
+
+
+def get_distance_transform(field, boxlength, *, threshold=0.5, select="below", periodic=True, squared=False):
+    """The exact Euclidean distance transform of the 3-D ``field`` in a box of ``boxlength`` (a scalar or 3 lengths;
+    the cells must be cubic): for every cell with ``v < threshold`` (``select="below"``) or ``v >= threshold``
+    (``"above"``) the distance, centre to centre, to the nearest cell that is not selected, with the minimum image on
+    the ``periodic`` axes (a bool or three) and nothing beyond an open face -- the convention of
+    ``scipy.ndimage.distance_transform_edt``.  Returns float32 distances in the units of ``boxlength`` (0 at
+    unselected cells, inf in a box without one), or with ``squared`` the int32 squared distances in cells^2 (2^30 in
+    such a box), shaped as the field: numpy for numpy input, torch on its device for a torch CUDA field."""
+    _check_bubble_field(field)
+    shape = _shape(field)
+    cell = _cubic_cell(_lengths(boxlength), shape)
+    args = _granulometry_args(threshold, select, periodic)
+    d2 = api.granulometry(_f32(field), shape, np.zeros(0, np.int64), return_dist2=True, **args)[3].reshape(shape)
+    if squared:
+        return d2
+    if _is_torch(d2):
+        import torch
+
+        d = torch.sqrt(d2.to(torch.float64)) * torch.full((), cell, dtype=torch.float64, device=d2.device)
+        return torch.where(d2 >= EDT_NONE, torch.full_like(d, np.inf), d).to(torch.float32)
+    return np.where(d2 >= EDT_NONE, np.inf, np.sqrt(d2.astype(np.float64)) * cell).astype(np.float32)
+
+
+def get_granulometry(field, boxlength, *, threshold=0.5, select="below", radii=32, periodic=True,
+                     return_sizes=False) -> Granulometry:
+    """The granulometry bubble size distribution (Kakiichi et al. 2017; beside the mean-free-path and
+    friends-of-friends estimators in Lin et al. 2016 and Giri et al. 2018) of the 3-D ``field`` in a box of
+    ``boxlength`` (a scalar or 3 lengths; the cells must be cubic): the share of the cells with ``v < threshold``
+    (``select="below"``: for a neutral fraction the ionised phase) or ``v >= threshold`` (``"above"``) that lies in a
+    ball of radius > r which holds selected cells only, for every radius.  A ball is one inscribed at a cell centre:
+    its squared radius is the cell's squared distance D2 to the nearest unselected cell (``get_distance_transform``),
+    across the faces of the ``periodic`` axes (a bool or three).  ``radii``: an integer (``granulometry_radii``: up to
+    that many log-spaced radii) or lengths, turned into the distinct ``floor((r / cell)^2)``.  Everything counted is
+    an integer fixed by the mask: two calls give the same bytes, a radius' counts do not depend on the other radii,
+    and ``covered`` never grows with the radius.  ``return_sizes`` adds the per-cell radius."""
+    _check_bubble_field(field)
+    shape = _shape(field)
+    cell = _cubic_cell(_lengths(boxlength), shape)
+    args = _granulometry_args(threshold, select, periodic)
+    radii2 = _granulometry_radii2(radii, shape, args["periodic"], cell)
+    res = _granulometry_result(_f32(field), shape, cell, radii2, args, (0,), None, return_sizes)
+    for name in _GRANULOMETRY_PER_BOX:
+        v = getattr(res, name)
+        if v is not None:
+            setattr(res, name, v[0])
+    return res
+
+
+def lightcone_granulometry(lightcone, cell_size, *, chunk_length=None, chunk_starts=None, redshifts=None,
+                           **kw) -> Granulometry:
+    """Granulometry of the chunks of a rectilinear ``lightcone`` (nx, ny, n_slices) of cubic cells of ``cell_size``
+    [Mpc], chunked as ``lightcone_bubble_clusters`` chunks it; all chunks go through one library call and share the
+    radii.  The transverse axes are periodic and the line of sight is open, so ``periodic`` is not a keyword here; the
+    others (``threshold``, ``select``, ``radii``, ``return_sizes``) are those of ``get_granulometry``.  Every per-box
+    entry carries a leading chunk axis."""
+    _check_bubble_field(lightcone, "lightcone")
+    if "periodic" in kw:
+        raise ValueError("periodic is fixed for a lightcone: the transverse axes are, the line of sight is not")
+    unknown = set(kw) - {"threshold", "select", "radii", "return_sizes"}
+    if unknown:
+        raise ValueError(f"unknown keywords: {sorted(unknown)}")
+    nx, ny, ns = _shape(lightcone)
+    dx = float(cell_size)
+    if not (np.isfinite(dx) and dx > 0):
+        raise ValueError("cell_size must be positive and finite")
+    n, starts, z = _chunks(ns, nx, chunk_length, chunk_starts, redshifts)
+    shape = (nx, ny, n)
+    args = _granulometry_args(kw.get("threshold", 0.5), kw.get("select", "below"), (True, True, False))
+    radii2 = _granulometry_radii2(kw.get("radii", 32), shape, args["periodic"], dx)
+    res = _granulometry_result(_f32(lightcone), shape, dx, radii2, args, starts, ns, kw.get("return_sizes", False))
     res.chunk_starts, res.redshifts = starts, z
     return res

@@ -1151,6 +1151,44 @@ int c21cm_minkowski_grids(const float *field, int nx, int ny, int nz, int n_batc
                           const long long *batch_offsets, int n_thresholds, const double *thresholds,
                           int select_below, int periodic_mask, long long *counts, void *stream);
 
+/* ---- Squared distance transforms and granulometry bubble sizes of boxes and lightcone chunks (Kakiichi et al. 2017;
+ * Lin et al. 2016; Giri et al. 2018; the spec is tests/granulometry_reference.py) ----
+ * Layout and selection: as for c21cm_bubble_clusters_grids: n_batch boxes of nx x ny x nz float32 cells at
+ *   batch_offsets[b], rows of row_pitch, z fastest, host or device pointers; a cell is selected iff (double)v <
+ *   threshold (select_below = 1) or >= threshold (0).  Everything below is an integer and a function of the mask
+ *   alone; distances are in cells.
+ * Axis distance: d_a(i, j) = |i - j| on an open axis; where bit a of periodic_mask (bit 0 x, 1 y, 2 z) is set, d_a(i,
+ *   j) = min(|i - j|, n_a - |i - j|).  Nothing lies beyond an open face: the outside is neither selected nor
+ *   unselected (the convention of scipy.ndimage.distance_transform_edt).
+ * Squared distance transform: D2[c] = the minimum of d_x^2 + d_y^2 + d_z^2 over the unselected cells q of the same
+ *   box, centre to centre: 0 at unselected cells, and C21CM_EDT_NONE = 2^30 everywhere in a box without an unselected
+ *   cell.  nx^2 + ny^2 + nz^2 < 2^30 is required, so that every real distance is below the sentinel and sentinel -
+ *   d^2 stays positive in int32.
+ * Radii: radii2[n_radii], int64 on the host, 0 <= s_0 < s_1 < ...; 0 <= n_radii <= 255.
+ * Erosion curve: eroded[k] = the cells with D2[c] > s_k: the cells whose closed digital ball {o : |o|^2 <= s_k} holds
+ *   only selected cells.
+ * Granulometry: cell x is covered at s iff some centre c has D2[c] > s and |x - c|^2 < D2[c] (the same axis
+ *   distances); covered[k] = the number of such cells.  Equivalently Q_s[x] = max_c (G_s[c] - |x - c|^2) > 0 with G_s
+ *   = D2 where D2 > s and minus infinity elsewhere: the union of the inscribed balls of squared radius > s, which in
+ *   the continuum is the opening by a ball of radius sqrt(s).  Unlike the two-step digital opening it is monotone in
+ *   s, its rows do not depend on which other radii were asked for, and covered = n_selected at s = 0.
+ * Outputs (host or device): covered[n_batch][n_radii] and eroded[n_batch][n_radii], int64; stats[n_batch][4] =
+ *   {n_selected, max D2 over the selected cells (0 without one), the smallest flat index (ix ny + iy) nz + iz
+ *   attaining it (-1 without one), n_unselected}; where not NULL dist2[n_batch][nx ny nz] (int32, dense, C order) = D2
+ *   and level[n_batch][nx ny nz] (int32) = the number of asked radii at which the cell is covered, -1 at unselected
+ *   cells; the coverage being monotone, level - 1 indexes the largest such radius.  Sums are integer atomics or
+ *   fixed-order reductions: two calls give the same bytes.
+ * Errors, checked before any output is touched: C21CM_VALUE_ERROR with a message for a NULL required pointer (field,
+ *   batch_offsets, stats; with n_radii >= 1 also radii2, covered, eroded), a bad shape or nx^2 + ny^2 + nz^2 >= 2^30,
+ *   nx ny nz >= 2^31, n_batch outside [1, 65535], row_pitch < nz, a negative offset, a threshold that is not finite,
+ *   periodic_mask outside 0..7, n_radii outside [0, 255], radii negative or not strictly increasing;
+ *   C21CM_INFINITY_OR_NAN_ERROR for a non-finite field value.  Nothing is written on an error. */
+#define C21CM_EDT_NONE (1 << 30)
+int c21cm_granulometry_grids(const float *field, int nx, int ny, int nz, int n_batch, long long row_pitch,
+                             const long long *batch_offsets, double threshold, int select_below, int periodic_mask,
+                             int n_radii, const long long *radii2, long long *covered, long long *eroded,
+                             long long *stats, int *dist2, int *level, void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
