@@ -171,6 +171,9 @@ typedef struct c21hip_z_ionise_desc {
     double rec0;                  /* ... or, nrec == NULL, the homogeneous model's one number */
     int recomb;                   /* recombination model: barrier (1 + N_rec / (1 + delta)); a first crossing
                                    * leaves delta_R in g12 for c21hip_split_z_sfr_gamma12; sum_out is not used */
+    int cross_by_memory_line;     /* cross_plane is indexed by memory line of the (x-blocked) spectrum, to be resolved
+                                   * by c21hip_resolve_crossings_lines; 0: by logical line x * ny + y
+                                   * (c21hip_resolve_crossings).  Sits in what was padding: the size is unchanged */
     float *g12;                   /* recomb: dense Gamma_12 grid */
     unsigned char *first_cross;   /* uint8 [N] mask of first crossings, updated; or, instead of it, ... */
     unsigned *cross_plane;        /* ... this radius' plane of crossing bits (c21hip_z_cross_bits_supported) */
@@ -287,6 +290,11 @@ int c21hip_batched_means(const double *partials, long stride, int n_partials, in
 int c21hip_z_cross_bits_supported(int nx, int ny, int nz);
 int c21hip_resolve_crossings(const unsigned *bits, int r_hi, int r_lo, unsigned char *first_cross,
                              size_t nlines, void *stream);
+/* the same for planes indexed by memory line (c21hip_z_ionise_desc.cross_by_memory_line) of a spectrum with ny
+ * lines per x and block shift lb (c21hip_split_xblock_log2(nx)): memory line m goes to mask row
+ * c21_logical_line(m, ny, lb); the mask stays in logical order.  nlines must be a multiple of ny << lb. */
+int c21hip_resolve_crossings_lines(const unsigned *bits, int r_hi, int r_lo, unsigned char *first_cross,
+                                   size_t nlines, int ny, int lb, void *stream);
 /* passes X, Y of one grid with window a of the two-grid tables in buffer table_slot */
 int c21hip_split_filter_xy_shared(const float *src, float *work, int filter_type, int nx, int ny,
                                   int nz, double box_len, double box_len_z, float R, int apply,

@@ -84,18 +84,32 @@ __device__ __forceinline__ int fft_out_row(int g) {
 }
 
 // x-blocked split layout.  The main block is stored as [x / XB][y][x % XB][k_z] with
-// XB = 2^xb_log2(nx): 1 (the plain [x][y][k_z]) up to 512-point x-lines, 8 for 1024.  At 1024^3 the
-// rows of a pass-X tile would otherwise lie ny*nz/2*8 B = 4 MB apart, one page each, and 42 % of
-// the pass's L1-TLB requests missed; blocked, 16 consecutive x are 4 KB apart and a tile
-// touches 64 pages instead of 1024.  Memory line m = (x / XB * ny + y) * XB + x % XB holds the
+// XB = 2^split_xb_log2(nx): 1 (the plain [x][y][k_z]) below 512-point x-lines, 16 for 512, 8 for 1024.
+// At 1024^3 the rows of a pass-X tile would otherwise lie ny*nz/2*8 B = 4 MB apart, one page each, and 42 %
+// of the pass's L1-TLB requests missed; blocked, 16 consecutive x are 4 KB apart and a tile
+// touches 64 pages instead of 1024.  At 512^3 the plain rows lie 1 MB apart (512 rows on 256 pages of 2 MB
+// per buffer); blocked by 16 the two-radius pass X runs 0.600 instead of 0.669 ms in the loop.
+// Memory line m = (x / XB * ny + y) * XB + x % XB holds the
 // k_z row of the logical line x * ny + y; the Nyquist plane stays [x][y].
-#ifndef C21X_XB_MIN   // experiment switches: shortest x-line stored blocked, log2 of the block
-#define C21X_XB_MIN 1024
-#endif
-#ifndef C21X_XB_LOG2  // 8 planes per block: pass Y's rows lie 32 KB apart instead of 64 (437 against 447 ms per
-#define C21X_XB_LOG2 3  // 1024^3 call; blocks of 4: 448, of 32: 467)
-#endif
-__host__ __device__ constexpr int split_xb_log2(int nx) { return nx >= C21X_XB_MIN ? C21X_XB_LOG2 : 0; }
+// split_xb_log2 is the one place that decides the block shift of a spectrum; every launcher and
+// c21hip_split_xblock_log2 ask it.  1024-point x-lines and longer: 8 planes per block (pass Y's rows lie 32 KB
+// apart instead of 64: 437 against 447 ms per 1024^3 call; blocks of 4: 448, of 32: 467).  512-point x-lines:
+// kXb512Default, measured in profiles/xblock_512_ab.txt; C21CM_XBLOCK=0 keeps them plain, C21CM_XBLOCK=k (3, 4 or 5)
+// stores them in blocks of 2^k planes (read once per process: a spectrum must not change layout between the
+// calls that share it).  Shorter lines are always plain.
+constexpr int kXb512Default = 4;  // 16 planes: 37.10 ms per 512^3 step against 38.37 plain (blocks of 8: 37.17, of 32: 37.36)
+static int split_xb_log2(int nx) {
+    if (nx >= 1024) return 3;
+    if (nx < 512) return 0;
+    static const int k512 = [] {
+        const char *e = getenv("C21CM_XBLOCK");
+        if (!e || !*e) return kXb512Default;
+        char *end = nullptr;
+        const long k = strtol(e, &end, 10);  // the measured block sizes only; anything else is the default
+        return (*end == 0 && (k == 0 || (k >= 3 && k <= 5))) ? (int)k : kXb512Default;
+    }();
+    return k512;
+}
 __host__ __device__ __forceinline__ long logical_line(long m, int ny, int lb) {
     if (lb == 0) return m;
     const long blk = (long)ny << lb;
@@ -1986,6 +2000,8 @@ struct ZFusedArgs {
     // b of a line is what lane b of the line holds after wave_c2r<16, 16> -- bit q is cell 32 q + 2 b,
     // bit 16 + q is cell 32 q + 2 b + 1 (q = 0..15).
     unsigned *cross_bits;
+    int cb_mem;  // the plane is indexed by memory line (resolved by c21hip_resolve_crossings_lines): the four lines
+                 // of a wave are adjacent in memory, so its four 64-byte pieces form one 256-byte run under any lb
     double *partials;              // one per workgroup (nx*ny/LZ_FUSED)
     double rhocrit_omb, ion_eff, f_limit;
     int mass_dep_zeta, r_index;
@@ -2599,7 +2615,7 @@ zw_ionise_kernel(ZFusedArgs a, const float2 *__restrict__ twH_global,
         }
     }
     // the line's 64 bytes, one word per lane: the four lines of a wave are four whole 64-byte pieces
-    if constexpr (CB) a.cross_bits[lline * (NZ / 32) + b] = cb;
+    if constexpr (CB) a.cross_bits[(a.cb_mem ? line : lline) * (NZ / 32) + b] = cb;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     if (lane == 0) red[wave] = acc;
@@ -4611,6 +4627,7 @@ extern "C" int c21hip_split_z_ionise(const c21hip_z_ionise_desc *d, void *stream
         a.x_is_nrec = w.nrec;
     a.first_cross = d->first_cross;
     a.cross_bits = d->cross_plane;
+    a.cb_mem = d->cross_by_memory_line;
     a.partials = d->partials;
     a.rhocrit_omb = d->rhocrit_omb;
     a.ion_eff = d->ion_eff;
@@ -4926,7 +4943,7 @@ extern "C" int c21hip_bench_pass(int kind, int n, int filter_a, int filter_b, fl
             d.delta_work = a;
             d.stars_work = b;
             if (c21hip_z_cross_bits_supported(n, n, n))  // what the loop launches: one plane
-                d.cross_plane = reinterpret_cast<unsigned *>(mask);
+                d.cross_plane = reinterpret_cast<unsigned *>(mask), d.cross_by_memory_line = 1;
             else
                 d.first_cross = mask;
             d.partials = partials;

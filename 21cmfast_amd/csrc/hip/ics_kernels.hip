@@ -589,7 +589,7 @@ extern "C" int c21hip_gsl_words_to_deviates(void *buf, size_t n_deviates, const 
     return 0;
 }
 
-// ---- split-layout pipeline entry points (plain layout, or x-blocked where fft_native.hip blocks: nx >= 1024)
+// ---- split-layout pipeline entry points (plain layout, or x-blocked where fft_native.hip blocks: c21hip_split_xblock_log2(nx), nx >= 512)
 extern "C" int c21hip_split_kop(const float *in_split, float *out_split, int nx, int ny, int nz,
                                 double box_len, double box_len_z, int axis0, int axis1,
                                 void *stream) {

@@ -26,6 +26,7 @@
 #include "c21cm_abi.h"
 #include "c21cm_grid.h"
 #include "fcoll_device.h"
+#include "split_layout.h"
 
 namespace {
 constexpr int kBlock = 256;
@@ -1220,7 +1221,7 @@ final_sweep_kernel(IoniseParams p, float stored_z, const unsigned char *__restri
 template <int NS>
 __global__ void __launch_bounds__(kBlock)
 resolve_crossings_kernel(const unsigned *__restrict__ bits, size_t plane_words, int r_hi, int r_lo,
-                         unsigned char *__restrict__ first_cross, size_t nquads) {
+                         unsigned char *__restrict__ first_cross, size_t nquads, int ny, int lb) {
     const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (t >= nquads) return;
     unsigned seen[4] = {0u, 0u, 0u, 0u}, sl[NS][4];
@@ -1242,7 +1243,8 @@ resolve_crossings_kernel(const unsigned *__restrict__ bits, size_t plane_words, 
         }
     }
     // words 4 k .. 4 k + 3 of the line: cells 32 q + 8 k .. + 7 for every q
-    unsigned char *row = first_cross + (t >> 2) * 512 + 8 * (t & 3);
+    // (planes by memory line, lb > 0: the thread's line of the plane is row logical_line of the mask)
+    unsigned char *row = first_cross + (size_t)c21_logical_line((long)(t >> 2), ny, lb) * 512 + 8 * (t & 3);
 #pragma unroll
     for (int q = 0; q < 16; q++) {
         unsigned v[4];  // low half: the even cell's index, high half: the odd cell's
@@ -2060,22 +2062,33 @@ extern "C" int c21hip_brightness_temp(const float *density, const float *xH, con
 
 // first_cross[nlines][512] from the crossing-bit planes of the radii r_hi, r_hi - 1, ... r_lo (>= 1);
 // the plane of radius r starts at bits + (r - 1) * nlines * 16 words.  Writes every byte of the mask.
-extern "C" int c21hip_resolve_crossings(const unsigned *bits, int r_hi, int r_lo,
-                                        unsigned char *first_cross, size_t nlines, void *stream) {
+// ..._lines: the planes are indexed by memory line of a spectrum with block shift lb (split_layout.h); lb = 0 is
+// c21hip_resolve_crossings
+extern "C" int c21hip_resolve_crossings_lines(const unsigned *bits, int r_hi, int r_lo, unsigned char *first_cross,
+                                              size_t nlines, int ny, int lb, void *stream) {
     if (r_lo < 1 || r_hi > 255 || !nlines) {
         c21hip_set_error("resolve_crossings: radius indices 1..255 and at least one line");
+        return C21CM_VALUE_ERROR;
+    }
+    if (lb < 0 || lb > 8 || (lb > 0 && (ny < 1 || nlines % ((size_t)ny << lb)))) {
+        c21hip_set_error("resolve_crossings: %zu lines are not whole blocks of %d x 2^%d lines", nlines, ny, lb);
         return C21CM_VALUE_ERROR;
     }
     const size_t nquads = nlines * 4;
     const dim3 grid((unsigned)((nquads + kBlock - 1) / kBlock));
     if (r_hi < 64)
         hipLaunchKernelGGL(resolve_crossings_kernel<6>, grid, dim3(kBlock), 0, (hipStream_t)stream, bits,
-                           nlines * 16, r_hi, r_lo, first_cross, nquads);
+                           nlines * 16, r_hi, r_lo, first_cross, nquads, ny, lb);
     else
         hipLaunchKernelGGL(resolve_crossings_kernel<8>, grid, dim3(kBlock), 0, (hipStream_t)stream, bits,
-                           nlines * 16, r_hi, r_lo, first_cross, nquads);
+                           nlines * 16, r_hi, r_lo, first_cross, nquads, ny, lb);
     LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int c21hip_resolve_crossings(const unsigned *bits, int r_hi, int r_lo,
+                                        unsigned char *first_cross, size_t nlines, void *stream) {
+    return c21hip_resolve_crossings_lines(bits, r_hi, r_lo, first_cross, nlines, 1, 0, stream);
 }
 
 extern "C" int c21hip_apply_first_cross(const unsigned char *first_cross,

@@ -1,5 +1,6 @@
 // split_layout.h -- index maps of the x-blocked split k-space layout (fft_native.hip: the main block of
-// a spectrum with nx >= 1024 is stored [x / XB][y][x % XB][k_z], XB = 2^lb; lb = 0: plain [x][y][k_z];
+// a spectrum with nx >= 512 is stored [x / XB][y][x % XB][k_z], XB = 2^lb, lb = c21hip_split_xblock_log2(nx);
+// lb = 0: plain [x][y][k_z];
 // the Nyquist plane is always [x][y]).  For the element-wise kernels that walk a spectrum in memory
 // order and need the wavenumbers of a line, or look a logical line up.
 #pragma once

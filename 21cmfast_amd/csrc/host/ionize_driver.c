@@ -801,6 +801,7 @@ static int z_ionise_radius(ion_ctx *c, int R_ct, const float *dwork, const float
     } else if (c->cross_bits) { /* this radius' plane instead of the mask (two grids only, see cross_bits_begin) */
         d.first_cross = NULL;
         d.cross_plane = c->cross_bits + (size_t)(R_ct - 1) * (c->ntot / 32);
+        d.cross_by_memory_line = 1; /* (resolved through c21hip_resolve_crossings_lines below) */
     } else
         d.xe_work = xwork;
     TRY(c21hip_split_z_ionise(&d, c->stream));
@@ -2263,8 +2264,9 @@ int c21cm_ionize_grids(const c21cm_ionize_spec *spec, const PerturbedField *pert
     if (mask) {
         TRY(radii_ladder(&c, spec->n_radii - 1, 1, mask, spec->r_lowest == 0 ? 0 : -1));
         if (c.cross_bits) {
-            TRY(c21hip_resolve_crossings(c.cross_bits, spec->n_radii - 1, spec->r_lowest > 1 ? spec->r_lowest : 1,
-                                         mask, (size_t)c.nx * c.ny, stream));
+            TRY(c21hip_resolve_crossings_lines(c.cross_bits, spec->n_radii - 1, spec->r_lowest > 1 ? spec->r_lowest : 1,
+                                               mask, (size_t)c.nx * c.ny, c.ny, c21hip_split_xblock_log2(c.nx),
+                                               stream));
             c.cross_bits = NULL;
         }
         TRY(flush_deferred(&c));

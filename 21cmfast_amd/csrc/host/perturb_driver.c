@@ -28,8 +28,9 @@ _Static_assert(WS_PT_IN_LAST - WS_PT_IN0 == 6 && WS_PT_OUT_LAST - WS_PT_OUT0 == 
 static int pt_split_supported(const int lo_dim[3]) {
     const char *e = getenv("C21CM_PT");
     if (e && e[0] == 'p') return 0;
-    return c21hip_fft_is_native(lo_dim[0], lo_dim[1], lo_dim[2]) &&
-           !c21hip_split_xblock_log2(lo_dim[0]);
+    /* (low-resolution grids of 1024 points and more keep the padded route; 512-point x-lines are x-blocked too,
+     * c21hip_split_xblock_log2, and every launcher of the split route maps its lines itself) */
+    return c21hip_fft_is_native(lo_dim[0], lo_dim[1], lo_dim[2]) && lo_dim[0] < 1024;
 }
 
 #define TRY(expr)         \
