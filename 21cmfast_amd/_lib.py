@@ -107,6 +107,9 @@ def _declare(lib):
         lib.c21cm_granulometry_grids.restype = i32
         lib.c21cm_granulometry_grids.argtypes = [vp, i32, i32, i32, i32, C.c_longlong, vp, f64, i32, i32, i32, vp, vp,
                                                  vp, vp, vp, vp, vp]
+    if hasattr(lib, "c21cm_observe_smooth_grids"):
+        lib.c21cm_observe_smooth_grids.restype = i32
+        lib.c21cm_observe_smooth_grids.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]
     for name, argt in (("compute_mu_for_multiple_scattering", [f64]),
                        ("compute_eta_for_multiple_scattering", [f64]),
                        ("hyper_2F3", [f64, f64, f64])):

@@ -979,6 +979,30 @@ int c21hip_gran_cover(const int *dist2, int nx, int ny, int nz, int n_batch, int
                       int n_radii, const long long *stats, int *work_a, int *work_b, unsigned long long *covered,
                       int *level, void *stream);
 
+/* ---- observe_kernels.hip : telescope-resolution smoothing of boxes and lightcones (observe_driver.c) ----
+ * Fields are dense (nx, ny, ns) float32 with s fastest; every pointer is a device pointer and in != out. */
+#define C21HIP_OBSERVE_MAX_LW 512   /* the widest half kernel: sigma <= 128 cells */
+#define C21HIP_OBSERVE_TILE_ROWS 248 /* cells of a transverse line, halo included, a beam workgroup holds in LDS */
+#define C21HIP_OBSERVE_LDS_LW 64     /* the widest half kernel of the LDS beam kernel; wider ones read global memory */
+/* the two constants above as the library was built with them (for the tests) */
+void c21hip_observe_geometry(int *tile_rows, int *lds_lw);
+/* the parts the rows of a slice are dealt into for the means: a function of nx ny alone */
+int c21hip_observe_mean_parts(long long rows);
+/* means[s] = the fp64 mean of field[:, :, s], fixed order; partial: 4 c21hip_observe_mean_parts(nx ny) ns doubles;
+ * *bad |= 1 on a non-finite value.  Two launches */
+int c21hip_observe_means(const float *field, int nx, int ny, int ns, double *partial, double *means, int *bad,
+                         void *stream);
+/* One transverse pass of the beam of c21cm_observe_smooth_grids (include/c21cm_grid.h) along x (axis 0) or y (1),
+ * wrapping.  tab[lw_max + 1][ns]: the weight w[d] of every slice, zero beyond its lw; lw[ns]; lw_block[ceil(ns /
+ * 64)]: the largest lw of each 64 slices; 1 <= lw_max <= C21HIP_OBSERVE_MAX_LW the largest of all.  means != NULL:
+ * (float)((double)in - means[s]) is convolved instead of in.  A slice with lw = 0 is copied */
+int c21hip_observe_beam(const float *in, float *out, int nx, int ny, int ns, int axis, const float *tab,
+                        const int *lw, const int *lw_block, int lw_max, const double *means, void *stream);
+/* out[i][j][s] = the mean of in[i][j][s - below[s] .. s + above[s]], ascending, the range clipped to the line or,
+ * with periodic, wrapped (below + above + 1 <= ns); means as above */
+int c21hip_observe_channel(const float *in, float *out, int nx, int ny, int ns, const int *below, const int *above,
+                           int periodic, const double *means, void *stream);
+
 /* ---- minkowski_kernels.hip : Minkowski functionals of boxes and lightcone chunks (minkowski_driver.c) ---- */
 #define C21HIP_MINKOWSKI_MAX_THRESHOLDS 255 /* a level fits a byte; thresholds and counters of one workgroup: 10 KiB */
 /* The element counts of c21cm_minkowski_grids (include/c21cm_grid.h) for every threshold from one read of the boxes.

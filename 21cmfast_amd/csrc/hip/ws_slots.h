@@ -434,6 +434,14 @@ enum c21_ws_slot {
     WS_GR_LEVEL,  /* int32 per cell, where asked for */
     WS_GR_OUT,    /* stats, covered, eroded, the erosion histogram, deepest-cell keys */
     WS_GR_FLAG,
+    /* ---- observe_driver.c ---- */
+    WS_OB_TAB,    /* beam weights, lw per slice and per 64 slices, channel counts */
+    WS_OB_IN,     /* staged host field */
+    WS_OB_MEANS,  /* partial sums of the slices, then their means */
+    WS_OB_WORK_A, /* float per cell: what a pass leaves for the next */
+    WS_OB_WORK_B,
+    WS_OB_OUT,    /* the result on its way to a host array */
+    WS_OB_FLAG,
 
     WS_COUNT
 };

@@ -1696,3 +1696,67 @@ def granulometry(field, shape, radii2, *, threshold=0.5, select_below=True, peri
     if return_level:
         out += (level,)
     return out
+
+
+OBSERVE_MAX_SIGMA = 128.0  # C21HIP_OBSERVE_MAX_LW / 4
+
+
+def observe_geometry():
+    """``(tile_rows, lds_lw)`` of the beam kernel as the library was built: the cells of a transverse line, halo
+    included, that a workgroup holds at a time, and the widest half kernel that goes through LDS."""
+    rows, lw = C.c_int(0), C.c_int(0)
+    load().c21hip_observe_geometry(C.byref(rows), C.byref(lw))
+    return rows.value, lw.value
+
+
+def observe_smooth(field, sigma_cells, los_below=None, los_above=None, *, periodic_los=False, subtract_mean=True,
+                   out=None, stream=None):
+    """Telescope-resolution smoothing of the float32 ``field`` (nx, ny, ns), the line of sight the last and fastest
+    axis: the fp64 mean of every slice (subtracted with ``subtract_mean``), a Gaussian beam of ``sigma_cells[s]`` cells
+    across the line of sight, truncated at 4 sigma and wrapping, and the mean over the slices ``s - los_below[s] ..
+    s + los_above[s]`` along it, clipped to the line or, with ``periodic_los``, wrapped.  ``sigma_cells``: a scalar
+    or ns values; the counts: ns integers each, all 0 where left out.  Returns ``(out, slice_means)``, float32
+    shaped as the field and float64 (ns,): numpy for numpy input, torch on the field's device for a torch CUDA field,
+    which never visits the host.  ``out``: an array of the field's kind to write into; it must not overlap the field.
+    The definition is written down at ``c21cm_observe_smooth_grids`` (include/c21cm_grid.h)."""
+    if field.ndim != 3:
+        raise ValueError(f"field must be a 3-D (nx, ny, ns) array, got {field.ndim} dimensions")
+    _f32_dense(field, "field")
+    nx, ny, ns = (int(x) for x in field.shape)
+    if min(nx, ny, ns) < 1:
+        raise ValueError("every axis needs at least 1 cell")
+    if nx * ny * ns >= 2**31:
+        raise ValueError("a field must have fewer than 2^31 cells")
+    sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_cells, np.float64), (ns,)))
+
+    def counts(a, what):
+        if a is None:
+            return np.zeros(ns, np.int32)
+        a = np.asarray(a)
+        if a.shape != (ns,) or a.dtype.kind not in "iu":
+            raise ValueError(f"{what} must be {ns} integers")
+        if np.any(a > 2**31 - 1) or np.any(a < -2**31):
+            raise ValueError(f"{what} must fit 32 bits")
+        return np.ascontiguousarray(a, np.int32)
+
+    below, above = counts(los_below, "los_below"), counts(los_above, "los_above")
+    if _is_torch(field):
+        import torch
+
+        if out is None:
+            out = torch.empty_like(field)
+        means = torch.empty(ns, dtype=torch.float64, device=field.device)
+        same_kind = _is_torch(out) and out.device == field.device
+    else:
+        if out is None:
+            out = np.empty_like(field)
+        means = np.empty(ns, np.float64)
+        same_kind = not _is_torch(out)
+    if not same_kind or tuple(out.shape) != (nx, ny, ns):
+        raise ValueError("out must be an array of the field's kind, device and shape")
+    _f32_dense(out, "out")
+    check(load().c21cm_observe_smooth_grids(
+        _vptr(field), nx, ny, ns, sigma.ctypes.data_as(C.c_void_p), below.ctypes.data_as(C.c_void_p),
+        above.ctypes.data_as(C.c_void_p), int(bool(periodic_los)), int(bool(subtract_mean)), _vptr(out), _vptr(means),
+        _stream(stream)), "c21cm_observe_smooth_grids")
+    return out, means

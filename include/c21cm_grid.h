@@ -1189,6 +1189,34 @@ int c21cm_granulometry_grids(const float *field, int nx, int ny, int nz, int n_b
                              int n_radii, const long long *radii2, long long *covered, long long *eroded,
                              long long *stats, int *dist2, int *level, void *stream);
 
+/* ---- Telescope-resolution smoothing of boxes and lightcones (the smooth_coeval / smooth_lightcone convention of
+ * tools21cm; Giri et al. 2018; Kakiichi et al. 2017; the spec is tests/observe_reference.py) ----
+ * Input: field[i][j][s], nx x ny x ns float32 cells, dense, the line of sight s fastest; host or device pointer.  Per
+ *   slice a beam width sigma_cells[s] >= 0 in cells (fp64) and two counts los_below[s], los_above[s] >= 0; all three
+ *   arrays on the host.
+ * Step 1, mean: m[s] = the mean of field[:][:][s], accumulated in fp64 in a fixed order (the order depends on nx ny
+ *   alone).  With subtract_mean g = (float)((double)f - m[s]), else g = f: a slice of equal values gives exactly 0.
+ * Step 2, beam: with lw = (int)(4 sigma + 0.5) >= 1 the half kernel is w[d] = exp(-d^2 / (2 sigma^2)), d = 0 .. lw,
+ *   divided in fp64 by w[0] + 2 sum_{d >= 1} w[d] and then rounded to fp32.  The slice is convolved along x and then
+ *   along y, h[i] = sum_{d = -lw .. lw} w[|d|] g[(i + d) mod n]: both axes wrap, as often as lw asks for (lw > n is
+ *   legal).  In exact arithmetic this is scipy.ndimage.gaussian_filter(slice, sigma, mode="wrap", truncate=4.0).  In
+ *   fp32 it is acc = w[0] g[i]; acc = fma(w[d], g[i - d] + g[i + d], acc) for d = 1 .. lw: a slice's result does not
+ *   depend on the widths of the other slices.  lw = 0 (sigma < 0.125) leaves the slice as it is, bit for bit.
+ * Step 3, channel: out[i][j][s] = the mean of step 2 over the slices s - los_below[s] .. s + los_above[s], added in
+ *   ascending order in fp32 and divided by their number.  On an open line of sight (periodic_los = 0: lightcones)
+ *   the range is clipped to [0, ns - 1]; with periodic_los (coeval boxes) it wraps, and below + above + 1 <= ns is
+ *   required.  below = above = 0 copies step 2.
+ * Outputs (host or device): out[nx][ny][ns] float32, which must not overlap field; where not NULL slice_means[ns],
+ *   fp64 = m, whether or not it was subtracted.  No floating-point atomics: two calls give the same bytes.
+ * Axes of any length are convolved: a transverse line longer than a workgroup holds runs in tiles.
+ * Errors, checked before any output is touched: C21CM_VALUE_ERROR with a message for a NULL required pointer (all but
+ *   slice_means), an axis < 1, nx ny ns >= 2^31, a sigma that is negative, not finite or above 128 cells (lw > 512), a
+ *   negative count, a periodic channel longer than ns, out overlapping field; C21CM_INFINITY_OR_NAN_ERROR for a
+ *   non-finite field value. */
+int c21cm_observe_smooth_grids(const float *field, int nx, int ny, int ns, const double *sigma_cells,
+                               const int *los_below, const int *los_above, int periodic_los, int subtract_mean,
+                               float *out, double *slice_means, void *stream);
+
 /* ---- Angular lightcone (lightconers.py:541-701 AngularLightconer) ----
  * One call fills slices [i0, i1) of up to C21CM_LC_MAX_FIELDS angular lightcones from the two node
  * boxes that bracket them.  Pixel p of slice j sits at x = distance[j] nhat[:, p] + origin (cells);
